@@ -11,7 +11,16 @@ on B=16 samples x N=6 views per GPU (S=96 stacked views), small UNet 64x64, fp32
 NMR-shaped tensors resident in HBM.  `value` = view denoise-steps/s over all ranks
 (= S_per_rank * world * iterations/s); weak scaling (per-GPU work fixed).
 
-Rank 0 prints ONE JSON line.  At --gpus 1 it also carries
+Rank 0 prints ONE JSON line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step) and the
+run's configuration.  A plain run does only that: set up, warm up, time --steps iterations, print.
+
+  --dump-outputs DIR : after the timed steps, write what the last timed iteration handed its caller as DIR/<name>.npy
+                       (float32): loss.npy, and the same fixed, seeded sample of 4M elements of the updated parameters
+                       (params_sample.npy) and of that iteration's gradients (grads_sample.npy), every parameter
+                       flattened and concatenated in named_parameters() order.  Inputs, initial weights and the device
+                       RNG are seeded, so the same arguments give the same inputs in every run.
+  --full             : at --gpus 1 the line also carries the legs below (--no-roofline / --no-sampler /
+                       --no-cpu-baseline drop one of them):
   roofline     : the dominant kernel (wino_conv_kernel, forward + dgrad launches) timed with HIP events
                  on its launch stream over extra instrumented steps; `frac` = the multiplies the matrix
                  cores EXECUTE / time / the 157.3 TF fp32 matrix peak (<= 1); plus a per-kernel-family
@@ -392,6 +401,26 @@ def sampler_leg():
     return out
 
 
+DUMP_SAMPLE = 1 << 22                  # parameter / gradient elements --dump-outputs writes (16 MB each in fp32)
+
+
+def dump_outputs(path, trainer, loss):
+    """--dump-outputs: the loss of the last timed iteration, and one fixed sample (seed 0, the same elements in every
+    run) of the parameters it left behind and of the gradients it computed, over all parameters flattened in
+    named_parameters() order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p for _, p in trainer.module.named_parameters()]
+    n = sum(p.numel() for p in params)
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:min(DUMP_SAMPLE, n)].sort().values
+    idx = idx.to(params[0].device)
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    out = {"loss": loss.detach().reshape(1), "params_sample": flat_p[idx], "grads_sample": flat_g[idx]}
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -400,9 +429,14 @@ def main():
     ap.add_argument("--batch", type=int, default=16, help="samples per GPU")
     ap.add_argument("--views", type=int, default=6)
     ap.add_argument("--ragged", action="store_true", help="view_count = randint(1, N+1) per sample (experiment.py:277-279)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-sampler", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline, sampler and CPU-baseline legs (single-GPU runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed iteration's loss and a fixed sample of its parameters and gradients "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
+    ap.add_argument("--no-sampler", action="store_true", help="with --full: skip the sampler leg")
     ap.add_argument("--graph", type=int, default=int(os.environ.get("VF_STEP_GRAPH", "1")),
                     help="1 (default): single-process runs replay the iteration as one HIP graph per batch geometry -- the "
                          "same launches on the same data, host enqueue 0.4 instead of 13 ms per step; 0: eager launches. "
@@ -440,6 +474,8 @@ def main():
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
     loss_val = float(loss.item())
     # what the job looked like from every rank: the driver can see that N processes on N devices took part, over which
     # backend / RCCL version, and which launch mode each ended in (train.Trainer.mode)
@@ -482,11 +518,11 @@ def main():
             except Exception as e:          # noqa: BLE001
                 res[key] = {"error": f"{type(e).__name__}: {e}"}
 
-        if world == 1 and not args.no_roofline:
+        if args.full and world == 1 and not args.no_roofline:
             leg("roofline", roofline, trainer, batch, S, ms)
-        if world == 1 and not args.no_sampler:
+        if args.full and world == 1 and not args.no_sampler:
             leg("sampler", sampler_leg)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             leg("cpu_baseline", cpu_baseline, 64, args.views)
         print(json.dumps(res), flush=True)
     if world > 1:

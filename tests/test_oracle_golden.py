@@ -236,11 +236,12 @@ def test_checkpoint_written_by_the_reference():
 
 
 def test_checkpoint_saved_here_loads_in_the_reference(tmp_path):
-    """The other direction: a file written by drivers.save_checkpoint is accepted by the reference's own
-    Checkpoint.load into the reference's modules (skipped where /root/reference is absent, e.g. the GPU box)."""
-    import sys
-    if not os.path.isdir("/root/reference/utils"):
-        pytest.skip("reference not present")
+    """The other direction: a file written by drivers.save_checkpoint is accepted by the reference's loader
+    (utils/checkpoint.py: Checkpoint.load = torch.load(file, map_location=device), then load_state_dict of every
+    registered module -- "model" and "optimizer" -- and the remaining entries handed back).  The modules it loads into
+    have the layout of tests/golden/ckpt_ref_micro.pt, the file the reference's own Checkpoint.save wrote: the saved
+    file must carry the same entries, the same state_dict keys, shapes and dtypes in the same order, and the same
+    per-parameter Adam state."""
     from view_fusion_amd import ViewFusion, drivers
     net = UNet(**MICRO)
     deterministic_fill_(net.state_dict())
@@ -252,20 +253,23 @@ def test_checkpoint_saved_here_loads_in_the_reference(tmp_path):
     opt.step()
     path = str(tmp_path / "model.pt")
     drivers.save_checkpoint(path, vf, opt, it=7, t=3.25, run_id="r", ssim=0.5, psnr=20.0)
-    sys.dont_write_bytecode = True
-    sys.path.insert(0, "/root/reference")
-    try:
-        from model.unet import UNet as RefUNet
-        from model.view_fusion import ViewFusion as RefVF
-        from utils.checkpoint import Checkpoint
-    finally:
-        sys.path.remove("/root/reference")
-    import contextlib, io
-    with contextlib.redirect_stdout(io.StringIO()):
-        rvf = RefVF(RefUNet(**MICRO), {"train": SCHED["linear_train"]})
-        rvf.set_new_noise_schedule(device=torch.device("cpu"), phase="train")
-        ropt = torch.optim.Adam(rvf.parameters(), lr=1e-4)
-        rest = Checkpoint(str(tmp_path), device=torch.device("cpu"), rank=0, model=rvf, optimizer=ropt).load("model.pt")
+    ref = torch.load(os.path.join(GOLDEN, "ckpt_ref_micro.pt"), map_location=torch.device("cpu"))
+    mine = torch.load(path, map_location=torch.device("cpu"))       # the reference loader's call
+    assert list(mine) == list(ref)
+    assert [(k, tuple(v.shape), v.dtype) for k, v in mine["model"].items()] == \
+        [(k, tuple(v.shape), v.dtype) for k, v in ref["model"].items()]
+    assert len(mine["optimizer"]["state"]) == len(ref["optimizer"]["state"])
+    assert all(set(a) == set(b) for a, b in zip(mine["optimizer"]["state"].values(), ref["optimizer"]["state"].values()))
+    assert [g["params"] for g in mine["optimizer"]["param_groups"]] == [g["params"] for g in ref["optimizer"]["param_groups"]]
+    # the loading side: fresh modules of the reference's layout (checked against the reference-written file first)
+    rvf = ViewFusion(UNet(**MICRO), {"train": SCHED["linear_train"]})
+    rvf.set_new_noise_schedule(device=torch.device("cpu"), phase="train")
+    assert [(k, tuple(v.shape)) for k, v in rvf.state_dict().items()] == [(k, tuple(v.shape)) for k, v in ref["model"].items()]
+    ropt = torch.optim.Adam(rvf.parameters(), lr=1e-4)
+    modules = dict(model=rvf, optimizer=ropt)
+    for k, m in modules.items():
+        m.load_state_dict(mine[k])
+    rest = {k: v for k, v in mine.items() if k not in modules}
     assert rest == dict(it=7, t=3.25, run_id="r", ssim=0.5, psnr=20.0)
     for (k, a), (k2, b) in zip(vf.state_dict().items(), rvf.state_dict().items()):
         assert k == k2 and torch.equal(a, b), k

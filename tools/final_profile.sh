@@ -11,12 +11,12 @@ export TMPDIR=/tmp
 R=${1:-rXX}
 OUT=gpurun_out/${R}_final; rm -rf "$OUT"; mkdir -p "$OUT"
 export VF_PMC_COMMIT=${2:-unknown}
-export VF_PMC_COMMAND="python3 bench.py --steps 5 --warmup 2 --no-sampler --no-cpu-baseline"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --steps 20 --warmup 5 --no-sampler --no-cpu-baseline > "$OUT/bench_profiled.json" 2> "$OUT/stats.log"
+export VF_PMC_COMMAND="python3 bench.py --full --steps 5 --warmup 2 --no-sampler --no-cpu-baseline"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- python3 bench.py --full --steps 20 --warmup 5 --no-sampler --no-cpu-baseline > "$OUT/bench_profiled.json" 2> "$OUT/stats.log"
 cp "$(find "$OUT/stats" -name "*kernel_stats.csv" | head -1)" "$OUT/kernel_stats.csv"
 rm -rf "$OUT/stats"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_$c" -- python3 bench.py --steps 5 --warmup 2 --no-sampler --no-cpu-baseline > /dev/null 2> "$OUT/pmc_$c.log" || echo "PMC pass $c failed (rc $?)" >> "$OUT/pmc_failed.txt"
+  timeout -k 10 600 rocprofv3 --kernel-trace --pmc $c --output-format csv -d "$OUT/pmc_$c" -- python3 bench.py --full --steps 5 --warmup 2 --no-sampler --no-cpu-baseline > /dev/null 2> "$OUT/pmc_$c.log" || echo "PMC pass $c failed (rc $?)" >> "$OUT/pmc_failed.txt"
 done
 python3 tools/pmc_summary.py "$OUT/pmc_traffic_kib_per_launch.json" "$OUT/pmc_FETCH_SIZE" "$OUT/pmc_WRITE_SIZE" > "$OUT/pmc_summary.txt" 2>&1
 python3 tools/roofline_table.py "$OUT/kernel_stats.csv" "$OUT/pmc_traffic_kib_per_launch.json" 29 > "$OUT/kernel_roofline_table.md" 2>&1
