@@ -19,7 +19,8 @@ extern "C" {
 #endif
 
 /* ---- GroupNorm (+Swish) : nn.GroupNorm(32,C,eps) -> Swish, unet.py:211-212,254,180-182 ----
- * HW = H*W must be a power of two >= 4 (square power-of-two maps), else hipErrorInvalidValue. */
+ * Any HW >= 1 with C % groups == 0: HW a power of two >= 4 runs the register-resident kernels (norm.hip), any other
+ * HW -- or a group too large for registers -- the general one-workgroup-per-(view, group) kernels (norm_any.hip). */
 int vf_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean /*[S*G]*/,
               float* rstd /*[S*G]*/, int S, int C, int HW, int groups, float eps, int silu, void* stream);
 /* dgamma_part/dbeta_part: [S][C] per-view partials; reduce over S with vf_colsum.
@@ -34,13 +35,15 @@ int vf_gn_bwd(const float* x, const float* gamma, const float* beta, const float
 /* same on the never-materialised channel concatenation [x (C1 channels) | x2 (C - C1)] of two NCHW tensors
  * (decoder skip connections, unet.py:134); the second-consumer gradients and dx are split the same way.
  * x2 == NULL: plain input; then addend2 (or NULL) is a second full-size tensor added to dx (gradient of a third
- * consumer of x).  Backward with x2: single-pass shapes only (vf_gn_bwd_emits_rowsum). */
+ * consumer of x).  x2 != NULL: HW a power of two >= 4; backward with x2: single-pass shapes only
+ * (vf_gn_bwd_emits_rowsum, which answers 0 wherever HW is not a power of two). */
 int vf_gn_cat_fwd(const float* x, const float* x2, int C1, const float* gamma, const float* beta, float* y, float* mean,
                   float* rstd, int S, int C, int HW, int groups, float eps, int silu, void* stream);
 int vf_gn_cat_bwd(const float* x, const float* x2, int C1, const float* gamma, const float* beta, const float* mean,
                   const float* rstd, const float* dy, const float* addend, const float* addend2, float* dx, float* dx2,
                   float* dgamma_part, float* dbeta_part, float* dx_rowsum, int S, int C, int HW, int groups, int silu,
                   void* stream);
+/* any len / HW: rows whose length is a multiple of 4 take the float4 kernels, others a scalar kernel */
 int vf_rowsum(const float* x, float* out /*[rows]*/, int rows, int len, void* stream);
 /* conv epilogue gradients in one launch: db[C] (|NULL) and dvb[S][C] (|NULL) from dy[S][C][HW] */
 int vf_bias_grad(const float* dy, float* db, float* dvb, int S, int C, int HW, void* stream);
@@ -61,7 +64,10 @@ int vf_conv_pack_weights_multi(const void* desc, int nlayers, long total_blocks,
 /* mode 0 stride-1 | 1 stride-2 (x is 2Hx2W) | 2 nearest-x2 upsampled x (x is H/2xW/2) |
  * 4 sub-pixel dgrad of mode 1: x = dY (HxW), y = dX (2Hx2W), every
  * output parity gets its own taps (no zeros multiplied; w_packed = the dgrad pack; no epilogue operands).
- * H,W = OUTPUT size (mode 4: the dY size), square power of two in [8,128]. */
+ * H,W = OUTPUT size (mode 4: the dY size), any size (mode 2: both even).  The shapes the specialised kernels are
+ * compiled for (square power of two in [8,128]; mode 1 / 4 up to 64, mode 2 from 16) run them (conv.hip); every other
+ * geometry runs the general runtime-H,W kernels (conv_any.hip) from the same packed weights.  The same holds for
+ * vf_conv_fwd_gn (general geometry: conv, then a GroupNorm launch), the 1x1 cat forms and the weight gradients. */
 int vf_conv_fwd(const float* x, const float* w_packed, const float* bias /*[Cout]|NULL*/,
                 const float* view_bias /*[S][Cout]|NULL*/, const float* residual /*like y|NULL*/, float* y,
                 float* ws /*|NULL*/, long ws_floats, int S, int Cin, int Cout, int H, int W, int KS, int mode,

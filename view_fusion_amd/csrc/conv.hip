@@ -24,6 +24,7 @@
 #include "wgrad_reduce.h"
 #include <cstring>
 #include "conv1x1.h"
+#include "any_geom.h"
 #include <cstdlib>
 
 namespace {
@@ -1114,6 +1115,25 @@ inline int ilog2_exact(int v) {
 }
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
+// The (KS, output size, mode) combinations that the specialised kernels of this file are compiled for (the VF_CASE
+// tables of conv_fwd_impl / conv_wgrad_impl); every other geometry runs the general kernels of conv_any.hip.
+inline bool fwd_specialised(int KS, int H, int W, int mode) {
+    const int lw = ilog2_exact(W);
+    if (H != W || lw < 3 || lw > 7) return false;
+    if (KS == 1) return mode == 0;
+    return mode == 0 || (mode == 1 && lw <= 6) || (mode == 2 && lw >= 4) || (mode == 4 && lw <= 6);
+}
+inline bool wgrad_specialised(int KS, int H, int W, int mode) {
+    return mode != 4 && fwd_specialised(KS, H, W, mode);
+}
+// the workspace formulas below price the specialised kernels wherever the map is a square power of two in [8, 128]; on
+// such a map the general kernels (a mode the specialised ones lack: 4 -> 8 Upsample, stride 2 to 128 x 128) plan their
+// split-K / slice count by the same formulas (conv_any.hip, square_pow2_map), so the size is exact for either route
+inline bool square_pow2(int H, int W) {
+    const int lw = ilog2_exact(W);
+    return H == W && lw >= 3 && lw <= 7;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1169,11 +1189,20 @@ static int conv_fwd_impl(const float* x, const float* x2, int C1, const float* w
                          const GnFuse* gn = nullptr) {
     if (S <= 0) return 0;
     const int lw = ilog2_exact(W);
-    if (H != W || lw < 3 || lw > 7 || (KS != 1 && KS != 3)) return (int)hipErrorInvalidValue;
+    if (KS != 1 && KS != 3) return (int)hipErrorInvalidValue;
     if (KS == 1 && mode != 0) return (int)hipErrorInvalidValue;
     if ((x2 || y2) && KS != 1) return (int)hipErrorInvalidValue;
     if (x2 && (C1 <= 0 || C1 >= Cin || C1 % 32 != 0)) return (int)hipErrorInvalidValue;     // chunk-aligned split
     if (y2 && (C1o <= 0 || C1o >= Cout || C1o % TCO != 0)) return (int)hipErrorInvalidValue; // tile-aligned split
+    if (gn && (gn->groups <= 0 || Cout % gn->groups != 0 || y2 || mode == 4)) return (int)hipErrorInvalidValue;
+    if (!fwd_specialised(KS, H, W, mode)) {
+        // any other geometry: the general kernel (conv_any.hip); the GroupNorm of vf_conv_fwd_gn as its own launch
+        const int e = vfi_conv_any_fwd(x, x2, C1, w_packed, bias, view_bias, residual, y, y2, C1o, ws, ws_floats, S, Cin, Cout,
+                                       H, W, KS, mode, (hipStream_t)stream);
+        if (e || !gn) return e;
+        return vf_gn_fwd(y, gn->gamma, gn->beta, gn->out, gn->stats, gn->stats + (size_t)S * gn->groups, S, Cout, H * W,
+                         gn->groups, gn->eps, gn->silu, stream);
+    }
     ConvArgs a;
     a.x = x; a.w = w_packed; a.bias = bias; a.vbias = view_bias; a.res = residual; a.y = y;
     a.x2 = x2; a.C1 = C1; a.y2 = y2; a.C1o = C1o;
@@ -1184,7 +1213,6 @@ static int conv_fwd_impl(const float* x, const float* x2, int C1, const float* w
     a.ksplit = 1;
     a.ws = ws;
     if (gn) {
-        if (gn->groups <= 0 || Cout % gn->groups != 0 || y2 || mode == 4) return (int)hipErrorInvalidValue;
         a.gn_gamma = gn->gamma; a.gn_beta = gn->beta; a.gn_out = gn->out; a.gn_stats = gn->stats;
         a.gn_groups = gn->groups; a.gn_silu = gn->silu; a.gn_store_y = gn->store_y; a.gn_eps = gn->eps;
     }
@@ -1247,6 +1275,7 @@ int vf_conv1x1_cat_dgrad(const float* dy, const float* w_packed_bwd, float* dx1,
 // Workspace floats vf_conv_fwd wants for its split-K path at this shape (0: no split-K, the
 // natural grid already fills the chip).  Upper bound over the tile choices.
 long vf_conv_fwd_ws_floats(int S, int Cin, int Cout, int H, int W, int KS) {
+    if (!square_pow2(H, W)) return vfi_conv_any_fwd_ws_floats(S, Cin, Cout, H, W, KS);
     const long tiles64 = ((long)S * H * W + 63) / 64;
     const long nblk_min = ((long)S * H * W + 127) / 128 * (round_up(Cout, TCO) / TCO);
     (void)tiles64;
@@ -1258,6 +1287,7 @@ long vf_conv_fwd_ws_floats(int S, int Cin, int Cout, int H, int W, int KS) {
 // Workspace floats needed by vf_conv_wgrad for the preferred split (a smaller workspace is
 // accepted down to 1 slab and just reduces the split-K factor).
 long vf_conv_wgrad_ws_floats(int S, int Cin, int Cout, int H, int W, int KS) {
+    if (!square_pow2(H, W)) return vfi_conv_any_wgrad_ws_floats(S, Cin, Cout, H, W, KS);
     if (KS == 1) {
         const int tm = wgrad1_tile(Cout), tn = wgrad1_tile(Cin);
         const long slab1 = (long)round_up(Cout, tm) * round_up(Cin, tn);
@@ -1284,9 +1314,12 @@ static int conv_wgrad_impl(const float* x, const float* x2, int C1, const float*
     if (desc) *nblocks = 0;
     if (S <= 0) return 0;
     const int lw = ilog2_exact(W);
-    if (H != W || lw < 3 || lw > 7 || (KS != 1 && KS != 3)) return (int)hipErrorInvalidValue;
+    if (KS != 1 && KS != 3) return (int)hipErrorInvalidValue;
     if (KS == 1 && mode != 0) return (int)hipErrorInvalidValue;
     if (x2 && (KS != 1 || C1 <= 0 || C1 >= Cin || C1 % 64 != 0)) return (int)hipErrorInvalidValue;
+    if (!wgrad_specialised(KS, H, W, mode))               // any other geometry: conv_any.hip
+        return vfi_conv_any_wgrad(x, x2, C1, dy, dw, ws, ws_floats, S, Cin, Cout, H, W, KS, mode, (hipStream_t)stream, desc,
+                                  nblocks);
     if (KS == 1) {                                        // plain GEMM: the large-tile kernel
         Wgrad1Args g;
         g.x = x; g.x2 = x2; g.dy = dy; g.ws = ws; g.S = S; g.Cin = Cin; g.Cout = Cout; g.C1 = C1; g.HW = H * W;

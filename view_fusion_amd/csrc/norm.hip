@@ -8,6 +8,7 @@
 //   bwd : per-(view,channel) row sums (one wave per row), then a streaming dx pass.
 // Layout: NCHW fp32, a group is cpg*H*W contiguous floats.
 #include "common.h"
+#include "any_geom.h"
 
 namespace {
 
@@ -539,10 +540,15 @@ int vf_gn_cat_fwd(const float* x, const float* x2, int C1, const float* gamma, c
                   float* rstd, int S, int C, int HW, int groups, float eps, int silu, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (S <= 0) return 0;
-    // HW: a power of two >= 4 (square power-of-two maps; the kernels index channels by shifts)
-    if (C % groups != 0 || HW < 4 || (HW & (HW - 1)) || (x2 && (C1 <= 0 || C1 >= C))) return (int)hipErrorInvalidValue;
+    // HW: a power of two >= 4 (square power-of-two maps; the kernels index channels by shifts); any other HW, or a group
+    // too large for the register-resident kernels, takes the general kernel (norm_any.hip; plain input only)
+    if (groups <= 0 || C % groups != 0 || (x2 && (C1 <= 0 || C1 >= C))) return (int)hipErrorInvalidValue;
     const int cpg = C / groups;
     const long n4 = (long)cpg * HW / 4;
+    if (HW < 4 || (HW & (HW - 1)) || n4 > 32768) {
+        if (x2) return (int)hipErrorInvalidValue;
+        return vfi_gn_any_fwd(x, gamma, beta, y, mean, rstd, S, C, HW, groups, eps, silu, st);
+    }
 #define VF_GN(NV, NT) return launch_gn_fwd<NV, NT>(x, x2, C1, gamma, beta, y, mean, rstd, S, C, HW, cpg, eps, silu, st)
     if (n4 <= 64) VF_GN(1, 64);
     if (n4 <= 256) VF_GN(1, 256);
@@ -566,7 +572,7 @@ int vf_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, f
 
 // 1 when vf_gn_bwd fills `dx_rowsum` at this shape (the single-pass kernel; the two-kernel path does not)
 int vf_gn_bwd_emits_rowsum(int C, int HW, int groups) {
-    if (groups <= 0 || C % groups != 0 || (HW & 3)) return 0;
+    if (groups <= 0 || C % groups != 0 || HW < 4 || (HW & (HW - 1))) return 0;
     const long n4g = (long)(C / groups) * HW / 4;
     return ((HW >= 256 && n4g <= 8192) || (HW == 64 && n4g <= 1024)) ? 1 : 0;
 }
@@ -577,7 +583,12 @@ int vf_gn_cat_bwd(const float* x, const float* x2, int C1, const float* gamma, c
                   void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (S <= 0) return 0;
-    if (C % groups != 0 || HW < 4 || (HW & (HW - 1))) return (int)hipErrorInvalidValue;
+    if (groups <= 0 || C % groups != 0) return (int)hipErrorInvalidValue;
+    if (HW < 4 || (HW & (HW - 1))) {                     // general HW: norm_any.hip (plain input, no dx_rowsum)
+        if (x2) return (int)hipErrorInvalidValue;
+        return vfi_gn_any_bwd(x, gamma, beta, mean, rstd, dy, addend, addend2, dx, dgamma_part, dbeta_part, S, C, HW, groups,
+                              silu, st);
+    }
     if (x2 && (C1 <= 0 || C1 >= C || !dx2 || (addend && !addend2) || !vf_gn_bwd_emits_rowsum(C, HW, groups)))
         return (int)hipErrorInvalidValue;                // cat inputs: single-pass kernels only
     const int cpg = C / groups;
@@ -638,14 +649,14 @@ int vf_gn_bwd(const float* x, const float* gamma, const float* beta, const float
 
 int vf_rowsum(const float* x, float* out, int rows, int len, void* stream) {
     if (rows <= 0) return 0;
-    if (len & 3) return (int)hipErrorInvalidValue;
+    if (len & 3) return vfi_rowsum_any(x, out, rows, len, (hipStream_t)stream);     // rows of any length
     hipLaunchKernelGGL(rowsum_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, out, rows, len);
     VF_RETURN_LAST_ERROR();
 }
 
 int vf_bias_grad(const float* dy, float* db, float* dvb, int S, int C, int HW, void* stream) {
     if (S <= 0 || C <= 0) return 0;
-    if (HW & 3) return (int)hipErrorInvalidValue;
+    if (HW & 3) return vfi_bias_grad_any(dy, db, dvb, S, C, HW, (hipStream_t)stream);
     hipLaunchKernelGGL(bias_grad_kernel, dim3(C), dim3(256), 0, (hipStream_t)stream, dy, db, dvb, S, C, HW);
     VF_RETURN_LAST_ERROR();
 }

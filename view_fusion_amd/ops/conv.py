@@ -65,6 +65,8 @@ class _Conv2dFn(torch.autograd.Function):
         S, Cin, Hi, Wi = x.shape
         Cout, _, KS, _ = weight.shape
         m = _MODES[mode]
+        if m == 1 and (Hi % 2 or Wi % 2):
+            raise ValueError(f"stride-2 conv on a {Hi}x{Wi} map: both sides must be even")
         H, W = (Hi // 2, Wi // 2) if m == 1 else ((Hi * 2, Wi * 2) if m == 2 else (Hi, Wi))
         y = torch.empty(S, Cout, H, W, device=x.device, dtype=torch.float32)
         flops = 2.0 * S * Cout * Cin * KS * KS * H * W

@@ -89,30 +89,36 @@ def _packed_wino(layer, force, kind=1):
     return uf, ub
 
 
-def pack_all(root, S=None):
+def pack_all(root, S=None, hw=None):
     """Training forward: re-pack the weights of EVERY conv layer under `root` with one launch per
-    format (device-side descriptor tables, rebuilt only if a parameter moved).  Layers annotated by
-    the UNet with their output size (`_vf_geom` = (H, mode)) that will take the Winograd path at
-    batch S get the transformed pack, all others the direct pack.  Each layer's fresh pack is
-    consumed by its next training-mode conv2d call."""
+    format (device-side descriptor tables, rebuilt only if a parameter moved or the geometry changed).
+    Layers annotated by the UNet with their output scale (`_vf_geom` = (level, mode): output = input
+    H x W >> level) that will take the Winograd path at batch S and input size `hw` = (H, W) (default:
+    the network's image_size squared) get the transformed pack, all others the direct pack.  Each
+    layer's fresh pack is consumed by its next training-mode conv2d call."""
     plan = getattr(root, "_vf_pack_plan", None)
     layers = plan[0] if plan is not None else [m for m in root.modules() if isinstance(m, torch.nn.Conv2d)]
     if not layers:
         return
     _check(layers[0].weight.detach())
 
+    if hw is None:
+        size = getattr(root, "_vf_image_size", None)
+        hw = (size, size) if size is not None else None
+
     def kind_of(l):
         geom = getattr(l, "_vf_geom", None)
-        if geom is None or S is None:
+        if geom is None or S is None or hw is None:
             return 0
-        return wino_kind(S, l.weight.shape[1], l.weight.shape[0], geom[0], geom[0], l.weight.shape[2], _MODES[geom[1]],
-                         train=True)
+        H, W = hw[0] >> geom[0], hw[1] >> geom[0]
+        return wino_kind(S, l.weight.shape[1], l.weight.shape[0], H, W, l.weight.shape[2], _MODES[geom[1]], train=True)
 
-    key = tuple((l.weight.data_ptr(), kind_of(l)) for l in layers)
+    kinds = tuple((l.weight.data_ptr(), kind_of(l)) for l in layers)
+    key = (hw, kinds)
     if plan is None or plan[1] != key:
         dev = layers[0].weight.device
         rows, first = {0: [], 1: [], 2: []}, {0: 0, 1: 0, 2: 0}
-        for l, (_, kind) in zip(layers, key):
+        for l, (_, kind) in zip(layers, kinds):
             w = l.weight
             Cout, Cin, KS, _ = w.shape
             nf, nb = ctypes.c_long(), ctypes.c_long()
@@ -143,7 +149,7 @@ def pack_all(root, S=None):
     # touching `_version` (torch._fused_adam_), so after a training forward no cached pack of any format may be
     # trusted by a later no-grad forward (generate / p_sample after Trainer.step()).
     attrs = ("_vf_pack", "_vf_wpack", "_vf_w4pack")
-    for l, (_, kind) in zip(layers, plan[1]):
+    for l, (_, kind) in zip(layers, plan[1][1]):
         for k, attr in enumerate(attrs):
             c = getattr(l, attr, None)
             if c is not None and c[0] is not None:

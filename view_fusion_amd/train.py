@@ -291,7 +291,7 @@ class Trainer:
         e.view_count = torch.tensor(vc, dtype=torch.int64, device=dev)
         offs = ops.view_offsets(e.view_count, dev)   # resolved (one read-back) and remembered BEFORE the capture
         e.off, e.vc = offs[0], vc                    # the offsets table: rewritten when a replay's view_count differs
-        tables = ops.prime_tables(getattr(self.module, "denoise_fn", None), key[-1], dev)
+        tables = ops.prime_tables(getattr(self.module, "denoise_fn", None), key[-1], dev, tuple(batch["y_0"].shape[-2:]))
         self.opt.zero_grad()                           # the capture allocates the gradients in the graph's pool
         g = torch.cuda.CUDAGraph()
         kw = {} if self._pool is None else dict(pool=self._pool)

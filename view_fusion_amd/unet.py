@@ -220,39 +220,61 @@ class UNet(nn.Module):
         self._annotate_geometry(image_size)
 
     def _annotate_geometry(self, image_size):
-        """Record every conv layer's OUTPUT size and mode (`_vf_geom`) so that the per-step weight
-        packing knows which layers take the Winograd format."""
-        def mark(conv, res, mode="same"):
-            object.__setattr__(conv, "_vf_geom", (res, mode))
+        """Record every conv layer's OUTPUT scale relative to the input and its mode (`_vf_geom` = (level, mode): the
+        output map is the input's H x W divided by 2**level) so that the per-step weight packing knows, for the input
+        size at hand, which layers take the Winograd format.  Also records the levels that hold attention."""
+        attn_levels = set()
 
-        def mark_block(blk, res):
+        def mark(conv, lvl, mode="same"):
+            object.__setattr__(conv, "_vf_geom", (lvl, mode))
+
+        def mark_block(blk, lvl):
             rb = blk.res_block
-            mark(rb.block1["block"]["3"], res)
-            mark(rb.block2["block"]["3"], res)
+            mark(rb.block1["block"]["3"], lvl)
+            mark(rb.block2["block"]["3"], lvl)
             if isinstance(rb.res_conv, nn.Conv2d):
-                mark(rb.res_conv, res)
+                mark(rb.res_conv, lvl)
             if blk.with_attn:
-                mark(blk.attn.qkv, res)
-                mark(blk.attn.out, res)
+                attn_levels.add(lvl)
+                mark(blk.attn.qkv, lvl)
+                mark(blk.attn.out, lvl)
 
-        res = image_size
+        lvl = 0
         for layer in self.downs:
             if isinstance(layer, _ResAttnBlock):
-                mark_block(layer, res)
+                mark_block(layer, lvl)
             elif isinstance(layer, _Resample):
-                res //= 2
-                mark(layer.conv, res, "down2")
+                lvl += 1
+                mark(layer.conv, lvl, "down2")
             else:
-                mark(layer, res)
+                mark(layer, lvl)
         for layer in self.mid:
-            mark_block(layer, res)
+            mark_block(layer, lvl)
         for layer in self.ups:
             if isinstance(layer, _ResAttnBlock):
-                mark_block(layer, res)
+                mark_block(layer, lvl)
             else:
-                res *= 2
-                mark(layer.conv, res, "up2")
-        mark(self.final_conv["block"]["3"], res)
+                lvl -= 1
+                mark(layer.conv, lvl, "up2")
+        mark(self.final_conv["block"]["3"], lvl)
+        object.__setattr__(self, "_vf_image_size", image_size)
+        object.__setattr__(self, "_vf_depth", sum(isinstance(m, _Resample) and not m.up for m in self.downs))
+        object.__setattr__(self, "_vf_attn_levels", tuple(sorted(attn_levels)))
+
+    def check_input_size(self, H, W):
+        """Raise ValueError if an (H, W) input is outside what this network runs: both sides divisible by
+        2**(len(channel_mults) - 1) (the reference's own condition: its decoder concatenates maps of equal size),
+        H*W a multiple of 4 (the diffusion kernels' rows), attention maps of at most 4096 pixels."""
+        f = 1 << self._vf_depth
+        if H <= 0 or W <= 0 or H % f or W % f:
+            raise ValueError(f"input size {H}x{W}: both sides must be positive multiples of {f} "
+                             f"(2**(len(channel_mults) - 1)) for the encoder / decoder maps to match")
+        if (H * W) % 4:
+            raise ValueError(f"input size {H}x{W}: H*W must be a multiple of 4")
+        for lvl in self._vf_attn_levels:
+            L = (H >> lvl) * (W >> lvl)
+            if L > 4096:
+                raise ValueError(f"input size {H}x{W}: the attention at level {lvl} would span {L} > 4096 pixels")
 
     def _affine_layers(self):
         lst = getattr(self, "_vf_affine", None)
@@ -306,8 +328,10 @@ class UNet(nn.Module):
         layers in execution order, for parity runs (only consulted when dropout > 0 and self.training)."""
         from . import ops
         draws = iter(dropout_u) if dropout_u is not None else None
+        ops._check(x)                        # (a CPU tensor is refused as such, before the size check)
+        self.check_input_size(x.shape[2], x.shape[3])
         if torch.is_grad_enabled() and self.final_conv["block"]["3"].weight.requires_grad:
-            ops.pack_all(self, x.shape[0])   # training: all 103 conv layers re-packed (one launch per format)
+            ops.pack_all(self, x.shape[0], tuple(x.shape[2:]))   # training: all conv layers re-packed (one launch per format)
         mlp = self.noise_level_mlp
         inference = not torch.is_grad_enabled() and not (self.training and self._has_dropout())
 
