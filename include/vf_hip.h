@@ -221,7 +221,8 @@ int vf_bgemm(const float* A, const float* B, float* C, const float* bias /*[N]|N
              int K, long sAb, long sAm, long sAk, long sBb, long sBk, long sBn, long sCb, long sCm, long sCn,
              float alpha, float beta, void* stream);
 /* fused attention forward (unet.py:258-277 core): qkv [S][3C][L] -> out [S][C][L]; optionally
- * P [S][L][L] (softmax probabilities, saved for backward).  L in {64,256}, C % 32 == 0. */
+ * P [S][L][L] (softmax probabilities, saved for backward).  L in {64,256}, C % 32 == 0.  Other L <= 4096 run
+ * vf_bgemm + vf_softmax_fwd / _bwd on materialised S x L x L scores (cols <= 4096); L > 4096 vf_attn_stream_*. */
 int vf_attention_fwd(const float* qkv, float* out, float* P /*|NULL*/, int S, int C, int L, void* stream);
 /* attention backward (autograd of unet.py:267-274), L = 256, C % 32 == 0, first of three launches:
  * dS = P o (dP - rowsum(P o dP)) with dP = dO^T V computed in the kernel, and dQ = K dS^T / sqrt(C) -> q third of dqkv;
@@ -231,6 +232,14 @@ int vf_attention_dscore(const float* qkv, const float* dO, const float* P, float
 /* ... second launch (C % 64 == 0): dV = dO P and dK = q dS / sqrt(C) -> the v and k thirds of dqkv */
 int vf_attention_dvdk(const float* qkv, const float* dO, const float* P, const float* dS, float* dqkv, int S, int C, int L,
                       void* stream);
+/* streaming attention (unet.py:248-277 core, csrc/attention_stream.hip), any L >= 1, 1 <= C <= 512, no L x L buffer:
+ * online softmax over key blocks.  qkv [S][3C][L] -> out [S][C][L]; lse [S][L] = per-query log-sum-exp of the scaled
+ * scores (training) or NULL.  ops.attention takes this route for L > 4096. */
+int vf_attn_stream_fwd(const float* qkv, float* out, float* lse /*|NULL*/, int S, int C, int L, void* stream);
+/* ... its backward (FlashAttention-2, deterministic, no float atomics): the probabilities recomputed from lse;
+ * delta [S][L] workspace (rowsum(dO o out)); writes all of dqkv [S][3C][L].  Three launches: delta, dK + dV, dQ. */
+int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* lse, float* delta,
+                       float* dqkv, int S, int C, int L, void* stream);
 int vf_softmax_fwd(const float* x, float* y, int rows, int cols, void* stream);
 int vf_softmax_bwd(const float* y, const float* dy, float* dx, int rows, int cols, void* stream);
 

@@ -45,7 +45,7 @@ from .dense import (  # noqa: F401
     time_affine_all
 )
 from .attention import (  # noqa: F401
-    _AttentionFn, _ConcatFn, attention, concat_channels
+    _AttentionFn, _AttentionStreamFn, _ConcatFn, attention, attention_route, attention_streaming, concat_channels
 )
 from .diffusion import (  # noqa: F401
     _ComposeLossFn, compose, compose_mse_loss, gather_level, p_sample_tail, psnr, stack_views, view_offsets

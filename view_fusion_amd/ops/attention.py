@@ -75,7 +75,59 @@ class _AttentionFn(torch.autograd.Function):
         return dqkv, None
 
 
+STREAM_MIN_L = 4097          # maps of more pixels take the streaming kernels: the materialised P would not fit
+
+
+def attention_route(C, L):
+    """Which kernels ops.attention runs for a (C, L) map: "fused" (L = 64 / 256, C % 32 == 0, scores in registers),
+    "generic" (the materialised S x L x L scores, L <= 4096) or "stream" (csrc/attention_stream.hip, L > 4096)."""
+    if L >= STREAM_MIN_L:
+        return "stream"
+    if L in (64, 256) and C % 32 == 0:
+        return "fused"
+    return "generic"
+
+
+class _AttentionStreamFn(torch.autograd.Function):
+    """The same attention without any L x L buffer (csrc/attention_stream.hip): online softmax over key blocks, the
+    backward recomputes the probabilities from the saved per-query log-sum-exp.  Training saves (qkv, out, lse)."""
+
+    @staticmethod
+    def forward(ctx, qkv, need_lse):
+        _check(qkv)
+        S, C3, H, W = qkv.shape
+        C, L = C3 // 3, H * W
+        out = torch.empty(S, C, H, W, device=qkv.device, dtype=torch.float32)
+        lse = torch.empty(S, L, device=qkv.device, dtype=torch.float32) if need_lse else None
+        _launch("attn_fwd", 4.0 * S * L * L * C, "vf_attn_stream_fwd", _ptr(qkv), _ptr(out), _ptr(lse), S, C, L,
+                _stream(), nbytes=4.0 * (qkv.numel() + out.numel() + (S * L if need_lse else 0)))
+        ctx.save_for_backward(qkv, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dO):
+        qkv, out, lse = ctx.saved_tensors
+        dO = _c(dO)
+        S, C3, H, W = qkv.shape
+        C, L = C3 // 3, H * W
+        dqkv = torch.empty_like(qkv)
+        delta = torch.empty(S, L, device=qkv.device, dtype=torch.float32)
+        # executed FLOPs: 8 L^2 C per view in the dK / dV kernel (S, dP, dV, dK) + 6 L^2 C in the dQ kernel (S and dP
+        # recomputed, dQ)
+        _launch("attn_bwd", 14.0 * S * L * L * C, "vf_attn_stream_bwd", _ptr(qkv), _ptr(out), _ptr(dO), _ptr(lse),
+                _ptr(delta), _ptr(dqkv), S, C, L, _stream(),
+                nbytes=4.0 * (2 * qkv.numel() + 2 * out.numel() + 2 * S * L))
+        return dqkv, None
+
+
+def attention_streaming(qkv):
+    """Self-attention core on the streaming kernels at any L (O(L) memory); ops.attention routes L > 4096 here."""
+    return _AttentionStreamFn.apply(qkv, torch.is_grad_enabled() and qkv.requires_grad)
+
+
 def attention(qkv):
+    if attention_route(qkv.shape[1] // 3, qkv.shape[2] * qkv.shape[3]) == "stream":
+        return attention_streaming(qkv)
     return _AttentionFn.apply(qkv, torch.is_grad_enabled() and qkv.requires_grad)
 
 

@@ -59,6 +59,7 @@ def _launch(kind, flops, name, *args, tag=None, nbytes=0.0):
 # Launchers without a roofline of their own still get a family in the bench's table (so that the table sums to the
 # instrumented step): kind by entry point, "misc" otherwise.
 _CALL_KIND = {"vf_wino44_pack_weights": "pack", "vf_wino44_pack_weights_multi": "pack", "vf_bgemm": "bgemm", "vf_softmax_bwd": "attn_bwd", "vf_softmax_fwd": "attn_fwd",
+              "vf_attn_stream_fwd": "attn_fwd", "vf_attn_stream_bwd": "attn_bwd",
               "vf_colsum": "reduce", "vf_colsum_multi": "reduce", "vf_rowsum": "reduce", "vf_bias_grad": "reduce",
               "vf_sumpool2": "reduce", "vf_conv_pack_weights": "pack", "vf_wino_pack_weights": "pack",
               "vf_conv_pack_weights_multi": "pack", "vf_wino_pack_weights_multi": "pack",

@@ -263,18 +263,15 @@ class UNet(nn.Module):
 
     def check_input_size(self, H, W):
         """Raise ValueError if an (H, W) input is outside what this network runs: both sides divisible by
-        2**(len(channel_mults) - 1) (the reference's own condition: its decoder concatenates maps of equal size),
-        H*W a multiple of 4 (the diffusion kernels' rows), attention maps of at most 4096 pixels."""
+        2**(len(channel_mults) - 1) (the reference's own condition: its decoder concatenates maps of equal size) and
+        H*W a multiple of 4 (the diffusion kernels' rows).  Attention runs at any map size (above 4096 pixels on the
+        streaming kernels, ops.attention_route)."""
         f = 1 << self._vf_depth
         if H <= 0 or W <= 0 or H % f or W % f:
             raise ValueError(f"input size {H}x{W}: both sides must be positive multiples of {f} "
                              f"(2**(len(channel_mults) - 1)) for the encoder / decoder maps to match")
         if (H * W) % 4:
             raise ValueError(f"input size {H}x{W}: H*W must be a multiple of 4")
-        for lvl in self._vf_attn_levels:
-            L = (H >> lvl) * (W >> lvl)
-            if L > 4096:
-                raise ValueError(f"input size {H}x{W}: the attention at level {lvl} would span {L} > 4096 pixels")
 
     def _affine_layers(self):
         lst = getattr(self, "_vf_affine", None)
