@@ -198,12 +198,13 @@ def test_deferred_slab_sums_share_one_arena_across_passes_and_graphs(dev):
                     angle=(torch.rand(B, 1, generator=g) * 6).to(dev), view_count=torch.full((B,), N))
 
     seen_entries = []
-    orig = ops.deferred._flush_wred
+    slab = ops.st.slab_sums
+    orig = slab.flush
 
     def spy():
-        seen_entries.extend(ops.st._PENDING_WRED)
+        seen_entries.extend(slab.pending)
         orig()
-    ops.deferred._flush_wred = spy
+    slab.flush = spy
     try:
         b3 = batch(3)
         for _ in range(train.Trainer.GRAPH_AFTER + 2):      # eager sightings, capture, one replay
@@ -224,7 +225,7 @@ def test_deferred_slab_sums_share_one_arena_across_passes_and_graphs(dev):
         # workspaces would add ~0.25 GB per graph at these sizes on top
         assert grown < 2.0e9, grown
     finally:
-        ops.deferred._flush_wred = orig
+        del slab.flush
     assert len(seen_entries) >= 20
     for row, nblk, keep in seen_entries:
         assert len(keep) == 4 and keep[0]._base is not None and keep[0].dim() == 1      # (ws = a slice of the arena, dw, db, db2)

@@ -297,6 +297,28 @@ def test_deferred_slab_sum_table_is_host_logic():
     assert pend[1][0][8] == 7 << 32                                  # the registered rows themselves stay as they were
 
 
+def test_deferred_column_sum_table_is_host_logic():
+    """The rows of the one GroupNorm column-sum launch per flush (ops._colsum_rows): [partials, destination, S, C, batch,
+    first], where `first` is the running sum of the preceding rows' workgroup counts -- ceil(C / 64) workgroups for each of
+    the `batch` sums of a row.  The builder reads nothing of a tensor but its address."""
+    from view_fusion_amd import ops
+
+    class At:
+        def __init__(self, addr):
+            self.addr = addr
+
+        def data_ptr(self):
+            return self.addr
+
+    pend = [(At(0x1000), At(0x2000), 2, 96, 64), (At(0x3000), At(0x4000), 2, 96, 65), (At(0x5000), At(0x6000), 1, 7, 192),
+            (At(0x7000), At(0x8000), 2, 96, 1)]
+    rows, total = ops._colsum_rows(pend)
+    assert rows == [[0x1000, 0x2000, 96, 64, 2, 0], [0x3000, 0x4000, 96, 65, 2, 2], [0x5000, 0x6000, 7, 192, 1, 6],
+                    [0x7000, 0x8000, 96, 1, 2, 9]]
+    assert total == 2 * 1 + 2 * 2 + 1 * 3 + 2 * 1
+    assert ops._colsum_rows([]) == ([], 0)
+
+
 def test_attention_kernel_choice_mirrors_the_launcher():
     """The L = 256 attention forward picks between 8 S workgroups of the 32-query kernel (three per compute unit) and 2 S
     workgroups of the 128-query kernel by a two-term cost model (attention.hip, vf_attention_fwd); this restates it so that a

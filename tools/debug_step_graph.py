@@ -42,7 +42,7 @@ with torch.cuda.graph(g, capture_error_mode="relaxed"):
         if stage == "adam":
             tr.opt.step_captured(adam, scal)
 fix = ops.end_capture()
-print("captured", stage, "table rows", fix[1], flush=True)
+print("captured", stage, "table rows", fix[0].used, flush=True)
 if stage == "adam":
     tr.opt.graph_end(adam)
 for i in range(4):

@@ -3,7 +3,7 @@
     state      the one object (`st`) that holds every knob and every piece of per-process mutable state
     policy     which kernel runs a conv layer at a given shape (the kernel-choice policy, in one place)
     core       pointers / streams / C-ABI call wrappers / kernel log
-    deferred   gradient destinations, deferred GroupNorm column sums and Winograd slab sums, capture tables
+    deferred   gradient destinations, deferred GroupNorm column sums and weight-gradient slab sums, capture tables
     packing    packed-weight caches, `pack_all`
     norm, conv, dense, attention, diffusion    the ops themselves
     bf16x3     experiment (default off)
@@ -16,9 +16,8 @@ from .core import (  # noqa: F401
     _CALL_KIND, _MODES, _WS_MAX, _c, _call, _check, _launch, _ptr, _raw_stream, _stream, _workspace
 )
 from .deferred import (  # noqa: F401
-    _CS_RING, _colsum, _defer_begin, _defer_ok, _flush_colsums, _flush_wred, _gout, _gslot, _rowsum_get,
-    _rowsum_put, _wred_rows, _wred_ws, begin_capture, drop_pending_colsums, end_capture, flush_colsums,
-    wred_arena_bytes
+    _CS_RING, _colsum, _colsum_rows, _defer_begin, _defer_ok, _gout, _gslot, _rowsum_get, _rowsum_put, _wred_rows,
+    _wred_ws, begin_capture, drop_deferred, end_capture, flush_deferred, wred_arena_bytes
 )
 from .capture import (  # noqa: F401
     prime_tables

@@ -14,6 +14,28 @@ from .packing import _WINO_ABI, _conv_ws, _packed, _packed_small, _packed_wino, 
 from .policy import use_small_conv, use_winograd, use_winograd_wgrad, wino_kind
 
 
+def _wgrad(entry, front, back, need, owners, keep, generic, flops, tag, strm):
+    """One layer's weight gradient through C-ABI entry `entry`(*front, ws, ws_floats, *back, stream), with `need` floats
+    of workspace -- or, when the destinations keep = (dw, db, db2) of parameters `owners` may be filled later
+    (deferred._defer_begin), through `entry`_main(..., row, workgroups, stream): the main kernel only, into this layer's
+    slice of the slab arena, and the slab sum joins the pass's one multi launch.  generic: the direct / 1x1 kernels
+    (round 6), which st.WRED_DEFER_GENERIC gates as well.  Returns whether it deferred: the caller then hands autograd
+    fresh views of the destinations."""
+    dev = keep[0].device
+    ws = _wred_ws(dev, need) if (st.WRED_DEFER and (st.WRED_DEFER_GENERIC or not generic)
+                                 and _defer_begin(owners, st.slab_sums)) else None
+    if ws is None:
+        ws = _workspace(dev, need)
+        _launch("conv_wgrad", flops, entry, *front, _ptr(ws), ws.numel(), *back, strm, tag=tag)
+        return False
+    row, nblk = (ctypes.c_longlong * 9)(), ctypes.c_int(0)
+    _launch("conv_wgrad", flops, entry + "_main", *front, _ptr(ws), ws.numel(), *back, ctypes.cast(row, ctypes.c_void_p),
+            ctypes.cast(ctypes.pointer(nblk), ctypes.c_void_p), strm, tag=tag)
+    # (the layer input and dy are not kept: the main kernel has consumed them in stream order; the flush reads ws only)
+    st.slab_sums.add(dev, (list(row), nblk.value, (ws, *keep)))
+    return True
+
+
 def _conv_small(x, x2, weight, bias, view_bias, residual, S, Cin, Cout, H, W, KS, m):
     wd = weight.detach()
     _check(wd)
@@ -150,7 +172,6 @@ class _Conv2dFn(torch.autograd.Function):
         db2 = None            # this dY's channel sums for the residual 1x1 conv, in a tensor of its own
         if ctx.needs_input_grad[1] and use_winograd_wgrad(S, Cin, Cout, H, W, KS, m):
             need = _lib.load().vf_wino_wgrad_ws_floats(S, Cin, Cout, H, W)
-            ws = _workspace(x.device, need)
             dw = _gout(ctx.pw, Cout, Cin, 3, 3, like=x)
             db_here = None
             if want_b and db is None:
@@ -161,43 +182,21 @@ class _Conv2dFn(torch.autograd.Function):
                     db2 = _gout(ctx.twin, Cout, like=x)
             owners = [ctx.pw] + ([ctx.pb] if db_here is not None else []) + \
                      ([ctx.twin] if (db2 is not None and ctx.twin is not None) else [])   # (identity residual: nobody owns db2)
-            ws_own = _wred_ws(x.device, need) if (st.WRED_DEFER and _defer_begin(owners, st._CAPTURE_TABLE_W)) else None
-            if ws_own is not None:
-                # main kernel only, into this layer's slice of the slab arena; the slab sum joins the pass's one multi launch
-                ws = ws_own
-                row, nblk = (ctypes.c_longlong * 9)(), ctypes.c_int(0)
-                _launch("conv_wgrad", ctx.flops, "vf_wino_wgrad_main", _ptr(x), _ptr(dy), _ptr(dw), _ptr(db_here), _ptr(db2),
-                        _ptr(ws), ws.numel(), S, Cin, Cout, H, W, m, ctypes.cast(row, ctypes.c_void_p),
-                        ctypes.cast(ctypes.pointer(nblk), ctypes.c_void_p), strm, tag=ctx.tag)
-                # (x and dy are not kept: the main kernel has consumed them in stream order; the flush reads ws only)
-                st._PENDING_WRED.append((list(row), nblk.value, (ws, dw, db_here, db2)))
+            if _wgrad("vf_wino_wgrad", (_ptr(x), _ptr(dy), _ptr(dw), _ptr(db_here), _ptr(db2)), (S, Cin, Cout, H, W, m),
+                      need, owners, (dw, db_here, db2), False, ctx.flops, ctx.tag, strm):
                 # AccumulateGrad adopts an incoming gradient only while nobody else references that tensor OBJECT; any
-                # other reference (the entry above; a view's ._base) makes it clone the -- still unfilled -- tensor.  So
+                # other reference (the pending entry; a view's ._base) makes it clone the -- still unfilled -- tensor.  So
                 # autograd gets fresh views (as the GroupNorm sums do with dgb[0] / dgb[1]); db2 reaches the residual conv
                 # through _rowsum_put and is re-viewed there.
                 dw = dw.view_as(dw)
                 if db_here is not None:
                     db = db_here.view_as(db_here)
-            else:
-                _launch("conv_wgrad", ctx.flops, "vf_wino_wgrad", _ptr(x), _ptr(dy), _ptr(dw), _ptr(db_here), _ptr(db2),
-                        _ptr(ws), ws.numel(), S, Cin, Cout, H, W, m, strm, tag=ctx.tag)
         elif ctx.needs_input_grad[1]:
             need = _lib.load().vf_conv_wgrad_ws_floats(S, Cin, Cout, H, W, KS)
             dw = _gout(ctx.pw, Cout, Cin, KS, KS, like=x)
-            # (round 6) the direct / 1x1 kernels' slab sums join the pass's deferred multi launch too
-            ws_own = _wred_ws(x.device, need) if (st.WRED_DEFER and st.WRED_DEFER_GENERIC
-                                                 and _defer_begin([ctx.pw], st._CAPTURE_TABLE_W)) else None
-            if ws_own is not None:
-                row, nblk = (ctypes.c_longlong * 9)(), ctypes.c_int(0)
-                _launch("conv_wgrad", ctx.flops, "vf_conv_wgrad_main", _ptr(x), _ptr(dy), _ptr(dw), _ptr(ws_own), ws_own.numel(),
-                        S, Cin, Cout, H, W, KS, m, ctypes.cast(row, ctypes.c_void_p),
-                        ctypes.cast(ctypes.pointer(nblk), ctypes.c_void_p), strm, tag=ctx.tag)
-                st._PENDING_WRED.append((list(row), nblk.value, (ws_own, dw, None, None)))
+            if _wgrad("vf_conv_wgrad", (_ptr(x), _ptr(dy), _ptr(dw)), (S, Cin, Cout, H, W, KS, m), need, [ctx.pw],
+                      (dw, None, None), True, ctx.flops, ctx.tag, strm):
                 dw = dw.view_as(dw)                   # (a fresh object for autograd: see the Winograd branch above)
-            else:
-                ws = _workspace(x.device, need)
-                _launch("conv_wgrad", ctx.flops, "vf_conv_wgrad", _ptr(x), _ptr(dy), _ptr(dw), _ptr(ws), ws.numel(), S,
-                        Cin, Cout, H, W, KS, m, strm, tag=ctx.tag)
         if want_b or want_v:
             if (want_v and dvb is None) or (want_b and db is None and dvb is None):
                 if Cout >= 192:                  # one launch, one workgroup per channel (enough channels to fill the chip)
@@ -272,19 +271,9 @@ class _Conv1x1CatFn(torch.autograd.Function):
         if ctx.needs_input_grad[2]:
             need = _lib.load().vf_conv_wgrad_ws_floats(S, Cin, Cout, H, W, 1)
             dw = _gout(ctx.pw, Cout, Cin, 1, 1, like=x1)
-            ws_own = _wred_ws(x1.device, need) if (st.WRED_DEFER and st.WRED_DEFER_GENERIC
-                                                  and _defer_begin([ctx.pw], st._CAPTURE_TABLE_W)) else None
-            if ws_own is not None:                    # slab sum deferred to the pass's one multi launch (see _Conv2dFn)
-                row, nblk = (ctypes.c_longlong * 9)(), ctypes.c_int(0)
-                _launch("conv_wgrad", flops, "vf_conv1x1_cat_wgrad_main", _ptr(x1), _ptr(x2), C1, _ptr(dy), _ptr(dw),
-                        _ptr(ws_own), ws_own.numel(), S, Cin, Cout, H, W, ctypes.cast(row, ctypes.c_void_p),
-                        ctypes.cast(ctypes.pointer(nblk), ctypes.c_void_p), strm, tag=tag)
-                st._PENDING_WRED.append((list(row), nblk.value, (ws_own, dw, None, None)))
-                dw = dw.view_as(dw)
-            else:
-                ws = _workspace(x1.device, need)
-                _launch("conv_wgrad", flops, "vf_conv1x1_cat_wgrad", _ptr(x1), _ptr(x2), C1, _ptr(dy), _ptr(dw), _ptr(ws),
-                        ws.numel(), S, Cin, Cout, H, W, strm, tag=tag)
+            if _wgrad("vf_conv1x1_cat_wgrad", (_ptr(x1), _ptr(x2), C1, _ptr(dy), _ptr(dw)), (S, Cin, Cout, H, W), need,
+                      [ctx.pw], (dw, None, None), True, flops, tag, strm):
+                dw = dw.view_as(dw)                   # (a fresh object for autograd: see _Conv2dFn)
         if ctx.has_bias and ctx.needs_input_grad[3]:
             hit = _rowsum_get(dy)                     # the 3x3 conv this output is added to has summed this dY
             db = hit[2].view_as(hit[2]) if (hit is not None and hit[2] is not None) else None     # (a fresh object: see _fresh)

@@ -2,6 +2,7 @@
 and the Winograd weight-gradient slab sums (one table-driven launch per flush instead of ~70 / ~65 small ones), the
 gradient-arena slot lookup, and the descriptor tables a HIP-graph capture of the iteration records its launches on."""
 import ctypes
+import functools
 
 import torch
 
@@ -46,7 +47,7 @@ def _gout(p, *shape, like):
 # emits: ~70 launches of 5 us per backward pass.  They are deferred: every GroupNorm backward only registers its
 # (partials, destination) pair, and ONE multi-tensor launch fills all destinations -- at the end of the backward pass (an
 # autograd engine callback) in single-process training, or, with the data-parallel gradient arena, right before a
-# segment's all-reduce is issued (reducer.GradArena calls flush_colsums(): ~6 launches per pass instead of 73).
+# segment's all-reduce is issued (reducer.GradArena calls flush_deferred(): ~6 launches per pass instead of 73).
 # Deferral hands autograd a destination that is FILLED LATER, so it is only taken when nothing can read the gradient
 # before the flush:
 #   * both parameters' .grad is None (AccumulateGrad then adopts the tensor without reading it; zero_grad(set_to_none=
@@ -61,7 +62,7 @@ def _gout(p, *shape, like):
 # A backward pass that raises never runs its engine callbacks, and a re-entrant backward pass (torch.utils.checkpoint)
 # starts a new graph task while the outer one still has entries pending: entries of another task are recognised by their
 # graph-task id and FLUSHED by the next pass (filling a destination nobody will read is harmless; dropping one autograd
-# still hands out is not).  A capture that aborts drops them explicitly (drop_pending_colsums).
+# still hands out is not).  A capture that aborts drops them explicitly (drop_deferred).
 # Round 5: the slab sums behind the Winograd weight-gradient kernels (65 launches of ~7 us per iteration) are deferred the
 # same way -- every layer runs only its main kernel into a workspace of its own (vf_wino_wgrad_main) and registers a
 # descriptor row; ONE vf_wino44_reduce_multi launch per flush fills dW (and the bias gradients that ride along).  Same
@@ -75,26 +76,34 @@ def _gout(p, *shape, like):
 # non-deferred launch instead.
 
 
+class _Arena:
+    """The slab arena of one device: the tensor (None until the first deferred layer) and the floats handed out in the
+    running backward pass."""
+
+    def __init__(self):
+        self.buf, self.used = None, 0
+
+
 def _wred_ws(device, need):
     """`need` floats of the slab arena for one layer of the running backward pass, or None (inside a capture, arena
     too small: the caller launches the non-deferred kernel pair)."""
-    ent = st._WRED_ARENA.setdefault(device, [None, 0])
+    a = st._WRED_ARENA.setdefault(device, _Arena())
     n = (int(need) + 63) // 64 * 64
-    cap = 0 if ent[0] is None else ent[0].numel()
-    if ent[1] + n > cap:
+    cap = 0 if a.buf is None else a.buf.numel()
+    if a.used + n > cap:
         if torch.cuda.is_current_stream_capturing():
             return None
         # (the slices of the old arena stay valid: the pending entries reference them)
-        ent[0] = torch.empty(max(2 * cap, ent[1] + n, 1 << 24), device=device, dtype=torch.float32)
-        ent[1] = 0
-    ws = ent[0][ent[1]:ent[1] + n]
-    ent[1] += n
+        a.buf = torch.empty(max(2 * cap, a.used + n, 1 << 24), device=device, dtype=torch.float32)
+        a.used = 0
+    ws = a.buf[a.used:a.used + n]
+    a.used += n
     return ws
 
 
 def wred_arena_bytes(device=None):
     """Bytes of the slab arena(s) currently allocated (tools/long_run.py reports it)."""
-    return sum(4 * e[0].numel() for d, e in st._WRED_ARENA.items() if e[0] is not None and (device is None or d == device))
+    return sum(4 * a.buf.numel() for d, a in st._WRED_ARENA.items() if a.buf is not None and (device is None or d == device))
 
 
 _CS_RING = 16           # staging buffers in rotation (the gradient arena flushes once per segment: ~6 tables per pass)
@@ -108,29 +117,95 @@ _CS_RING = 16           # staging buffers in rotation (the gradient arena flushe
 # therefore allocates the table BEFORE the capture starts.
 
 
+class _CaptureTable:
+    def __init__(self, table):
+        self.table = table      # device rows, allocated before the capture
+        self.used = 0           # rows the flushes of the capture have taken so far
+        self.rows = []          # their contents, uploaded by end_capture
+        self.keep = []          # the flushed pending lists: their tensors live as long as the graph's owner keeps this
 
 
-def begin_capture(device, max_rows, max_conv_rows=0):
-    st._CAPTURE_TABLE = [torch.empty(max(1, max_rows), 6, dtype=torch.int64, device=device), 0, [], []]
-    st._CAPTURE_TABLE_W = [torch.empty(max(1, max_conv_rows), 9, dtype=torch.int64, device=device), 0, [], []] if max_conv_rows else None
+class _Slot:
+    """One staging table of a family's ring: the rows of one flush, uploaded once and launched on for as long as the
+    caching allocator hands the same addresses back."""
+
+    def __init__(self):
+        self.pinned = self.table = self.key = None
+        self.event = torch.cuda.Event()     # recorded behind the upload
+        self.rows = self.workgroups = 0
 
 
-def end_capture():
-    """Upload the tables of the capture that just ended; returns what the graph's owner must keep referenced for as
-    long as it replays the graph."""
-    ct, st._CAPTURE_TABLE = st._CAPTURE_TABLE, None
-    cw, st._CAPTURE_TABLE_W = st._CAPTURE_TABLE_W, None
-    drop_pending_colsums()          # (only a capture that failed half-way leaves any)
-    if ct is not None and ct[1]:
-        ct[0][:ct[1]].copy_(torch.tensor(ct[2], dtype=torch.int64))
-    if cw is not None and cw[1]:
-        cw[0][:cw[1]].copy_(torch.tensor(cw[2], dtype=torch.int64))
-    return ct, cw
+class _Deferred:
+    """One family of deferred launches: the entries registered by the running backward pass, and the ONE table-driven
+    launch per flush that serves them all.
+        width      int64 words per table row
+        launch     launch(table pointer, rows, workgroups, stream): the family's C-ABI entry point
+        rows_of    pure function: pending list -> (rows, total workgroups)
+        key_of     pending list -> what an uploaded table is recognised by (the addresses and sizes in its rows)
+        full       the error of a capture whose table is missing or too small"""
 
+    def __init__(self, width, launch, rows_of, key_of, full):
+        self.width, self.launch, self.rows_of, self.key_of, self.full = width, launch, rows_of, key_of, full
+        self.pending = []       # entries of the running backward pass (of graph task st._PENDING_TASK)
+        self.device = None      # ... and the device their tensors live on
+        self.capture = None     # _CaptureTable while a Trainer is capturing
+        self.rings = {}         # device -> [_Slot], at most _CS_RING, the one the next miss overwrites first
+        self.keep = None        # the entries of the last eager flush: what its launch still reads
 
+    def add(self, device, entry):
+        self.pending.append(entry)
+        self.device = device
+
+    def begin_capture(self, device, max_rows):
+        self.capture = _CaptureTable(torch.empty(max(1, max_rows), self.width, dtype=torch.int64, device=device))
+
+    def end_capture(self):
+        ct, self.capture = self.capture, None
+        if ct is not None and ct.used:
+            ct.table[:ct.used].copy_(torch.tensor(ct.rows, dtype=torch.int64))
+        return ct
+
+    def flush(self):
+        pend, self.pending = self.pending, []
+        if not pend:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            # (several flushes per capture with the gradient arena: each takes the next rows of the pre-allocated table)
+            ct = self.capture
+            rows, total = self.rows_of(pend)
+            if ct is None or ct.used + len(rows) > ct.table.shape[0]:
+                raise _lib.VFHipError(self.full)
+            self.launch(ctypes.c_void_p(ct.table.data_ptr() + 8 * self.width * ct.used), len(rows), total, _stream())
+            ct.used += len(rows)
+            ct.rows += rows
+            ct.keep.append(pend)
+            return
+        key = self.key_of(pend)
+        ring = self.rings.setdefault(self.device, [])
+        # the caching allocator cycles through a few address sets: reuse an uploaded table
+        slot = next((s for s in ring if s.key == key), None)
+        if slot is None:
+            rows, total = self.rows_of(pend)
+            if len(ring) < _CS_RING:
+                slot = _Slot()
+            else:
+                slot = ring.pop(0)
+                slot.event.synchronize()      # that buffer's last upload is at least _CS_RING flushes old: no wait
+            ring.append(slot)
+            if slot.pinned is None or slot.pinned.shape[0] < len(rows):
+                n = max(128, len(rows))
+                slot.pinned = torch.empty(n, self.width, dtype=torch.int64).pin_memory()
+                slot.table = torch.empty(n, self.width, dtype=torch.int64, device=self.device)
+            slot.pinned[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
+            slot.table[:len(rows)].copy_(slot.pinned[:len(rows)], non_blocking=True)
+            slot.event.record()
+            slot.key, slot.rows, slot.workgroups = key, len(rows), total
+        self.launch(ctypes.c_void_p(slot.table.data_ptr()), slot.rows, slot.workgroups, _stream())
+        self.keep = pend                # partials / workspaces / destinations stay referenced until the next flush
 
 
 def _wred_rows(pend):
+    """Slab sums, entries (row the main kernel's launcher wrote, its workgroups, (ws, dw, db, db2) to keep alive)."""
     rows, first = [], 0
     for row, nblk, _ in pend:
         r = list(row)
@@ -140,105 +215,48 @@ def _wred_rows(pend):
     return rows, first
 
 
-def _flush_wred():
-    pend, st._PENDING_WRED = st._PENDING_WRED, []
-    for ent in st._WRED_ARENA.values():     # the next pass fills the arena from its start again (stream order)
-        ent[1] = 0
-    if not pend:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        cw = st._CAPTURE_TABLE_W
-        rows, total = _wred_rows(pend)
-        if cw is None or cw[1] + len(rows) > cw[0].shape[0]:
-            raise _lib.VFHipError("deferred weight-gradient slab sums inside a stream capture need ops.begin_capture() "
-                                  "with max_conv_rows >= the number of 3x3 layers (one backward pass per capture)")
-        _launch("conv_wgrad", 0.0, "vf_wino44_reduce_multi", ctypes.c_void_p(cw[0].data_ptr() + 72 * cw[1]), len(rows),
-                total, _stream())
-        cw[1] += len(rows)
-        cw[2] += rows
-        cw[3].append(pend)
-        return
-    key = tuple(v for e in pend for v in e[0])
-    dev = pend[0][2][0].device
-    ent = st._WR_TABLE.setdefault(dev, {"ring": [], "next": 0})
-    slot = None
-    for r in ent["ring"]:          # the caching allocator cycles through a few address sets: reuse an uploaded table
-        if r[3] == key:
-            slot = r
-            break
-    if slot is None:
-        rows, total = _wred_rows(pend)
-        n = max(128, len(rows))
-        if len(ent["ring"]) < _CS_RING:
-            slot = [torch.empty(n, 9, dtype=torch.int64).pin_memory(), torch.empty(n, 9, dtype=torch.int64, device=dev),
-                    torch.cuda.Event(), None, 0, 0]
-            ent["ring"].append(slot)
-        else:
-            slot = ent["ring"][ent["next"] % _CS_RING]
-            ent["next"] += 1
-            if slot[0].shape[0] < n:
-                slot[0], slot[1] = (torch.empty(n, 9, dtype=torch.int64).pin_memory(),
-                                    torch.empty(n, 9, dtype=torch.int64, device=dev))
-            slot[2].synchronize()
-        slot[0][:len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
-        slot[1][:len(rows)].copy_(slot[0][:len(rows)], non_blocking=True)
-        slot[2].record()
-        slot[3], slot[4], slot[5] = key, len(rows), total
-    _launch("conv_wgrad", 0.0, "vf_wino44_reduce_multi", ctypes.c_void_p(slot[1].data_ptr()), slot[4], slot[5], _stream())
-    st.keep_wred = pend             # workspaces / destinations stay referenced until the next flush
+def _colsum_rows(pend):
+    """Column sums, entries (parts, dgb, batch, S, C): `batch` sums of C columns over S rows each, 64 columns a workgroup."""
+    rows, first = [], 0
+    for parts, dgb, batch, S, C in pend:
+        rows.append([parts.data_ptr(), dgb.data_ptr(), S, C, batch, first])
+        first += ((C + 63) // 64) * batch
+    return rows, first
 
 
-def _flush_colsums():
-    _flush_wred()
-    pend, st._PENDING_COLSUMS, st._PENDING_TASK = st._PENDING_COLSUMS, [], None
-    if not pend:
-        return
-    if torch.cuda.is_current_stream_capturing():
-        # (several flushes per capture with the gradient arena: each takes the next rows of the pre-allocated table)
-        ct = st._CAPTURE_TABLE
-        rows, first = [], 0
-        for parts, dgb, batch, S, C in pend:
-            rows.append([parts.data_ptr(), dgb.data_ptr(), S, C, batch, first])
-            first += ((C + 63) // 64) * batch
-        if ct is None or ct[1] + len(rows) > ct[0].shape[0]:
-            raise _lib.VFHipError("deferred GroupNorm parameter sums inside a stream capture need ops.begin_capture() "
-                                  "with room for every GroupNorm layer (one backward pass per capture)")
-        _call("vf_colsum_multi", ctypes.c_void_p(ct[0].data_ptr() + 48 * ct[1]), len(rows), first, _stream())
-        ct[1] += len(rows)
-        ct[2] += rows
-        ct[3].append(pend)
-        return
-    key = tuple(v for e in pend for v in (e[0].data_ptr(), e[1].data_ptr(), e[3], e[4]))
-    dev = pend[0][0].device
-    ent = st._CS_TABLE.setdefault(dev, {"ring": [], "next": 0})
-    slot = None
-    for r in ent["ring"]:          # the caching allocator cycles through a few address sets: reuse an uploaded table
-        if r[3] == key:
-            slot = r
-            break
-    if slot is None:
-        rows, first = [], 0
-        for parts, dgb, batch, S, C in pend:
-            rows.append([parts.data_ptr(), dgb.data_ptr(), S, C, batch, first])
-            first += ((C + 63) // 64) * batch
-        n = max(128, len(rows))
-        if len(ent["ring"]) < _CS_RING:
-            slot = [torch.empty(n, 6, dtype=torch.int64).pin_memory(), torch.empty(n, 6, dtype=torch.int64, device=dev),
-                    torch.cuda.Event(), None, 0, 0]
-            ent["ring"].append(slot)
-        else:
-            slot = ent["ring"][ent["next"] % _CS_RING]
-            ent["next"] += 1
-            if slot[0].shape[0] < n:
-                slot[0], slot[1] = (torch.empty(n, 6, dtype=torch.int64).pin_memory(),
-                                    torch.empty(n, 6, dtype=torch.int64, device=dev))
-            slot[2].synchronize()      # that buffer's last upload is at least _CS_RING backward passes old: no wait
-        slot[0][:len(rows)].copy_(torch.tensor(rows, dtype=torch.int64))
-        slot[1][:len(rows)].copy_(slot[0][:len(rows)], non_blocking=True)
-        slot[2].record()
-        slot[3], slot[4], slot[5] = key, len(rows), first
-    _call("vf_colsum_multi", ctypes.c_void_p(slot[1].data_ptr()), slot[4], slot[5], _stream())
-    st.keep_colsums = pend          # the partials / destinations stay referenced until the next flush
+st.slab_sums = _Deferred(
+    9, functools.partial(_launch, "conv_wgrad", 0.0, "vf_wino44_reduce_multi"), _wred_rows,
+    lambda pend: tuple(v for row, _, _ in pend for v in row),
+    "deferred weight-gradient slab sums inside a stream capture need ops.begin_capture() "
+    "with max_conv_rows >= the number of 3x3 layers (one backward pass per capture)")
+st.col_sums = _Deferred(
+    6, functools.partial(_call, "vf_colsum_multi"), _colsum_rows,
+    lambda pend: tuple(v for parts, dgb, _, S, C in pend for v in (parts.data_ptr(), dgb.data_ptr(), S, C)),
+    "deferred GroupNorm parameter sums inside a stream capture need ops.begin_capture() "
+    "with room for every GroupNorm layer (one backward pass per capture)")
+
+
+def begin_capture(device, max_rows, max_conv_rows=0):
+    st.col_sums.begin_capture(device, max_rows)
+    if max_conv_rows:
+        st.slab_sums.begin_capture(device, max_conv_rows)
+    else:
+        st.slab_sums.capture = None
+
+
+def end_capture():
+    """Upload the tables of the capture that just ended; returns what the graph's owner must keep referenced for as
+    long as it replays the graph."""
+    drop_deferred()                 # (only a capture that failed half-way leaves any)
+    return st.col_sums.end_capture(), st.slab_sums.end_capture()
+
+
+def _flush():
+    st.slab_sums.flush()
+    for a in st._WRED_ARENA.values():       # the next pass fills the arena from its start again (stream order)
+        a.used = 0
+    st._PENDING_TASK = None
+    st.col_sums.flush()
 
 
 def _defer_ok(params):
@@ -260,42 +278,43 @@ def _colsum(parts, dgb, batch, S, C, params):
     # (entries of another graph task: a backward pass that failed (its callback never ran) -- or the OUTER pass of a
     # re-entrant backward (torch.utils.checkpoint, autograd.grad inside a backward), whose destinations autograd will still
     # hand out.  Outside a capture filling them now is always right (the entries keep their tensors alive); inside a
-    # capture the abort path has already dropped them (drop_pending_colsums).  _defer_begin does that.)
-    if _defer_begin(params, st._CAPTURE_TABLE):
-        st._PENDING_COLSUMS.append((parts, dgb, batch, S, C))
+    # capture the abort path has already dropped them (drop_deferred).  _defer_begin does that.)
+    if _defer_begin(params, st.col_sums):
+        st.col_sums.add(parts.device, (parts, dgb, batch, S, C))
         return
     _call("vf_colsum", _ptr(parts), _ptr(dgb), batch, S, C, _stream())
 
 
-def _defer_begin(params, capture_table):
+def _defer_begin(params, family):
     """Common entry of the two deferrals: True when a destination may be filled at the flush of the running backward
     pass; makes sure that flush is queued and that entries of another graph task are dealt with first."""
     task = torch._C._current_graph_task_id()
     if not (st.COLSUM_DEFER and task != -1 and _defer_ok(params)
-            and (capture_table is not None or not torch.cuda.is_current_stream_capturing())):
+            and (family.capture is not None or not torch.cuda.is_current_stream_capturing())):
         return False
-    if (st._PENDING_COLSUMS or st._PENDING_WRED) and st._PENDING_TASK != task:
+    if (st.col_sums.pending or st.slab_sums.pending) and st._PENDING_TASK != task:
         if torch.cuda.is_current_stream_capturing():
-            st._PENDING_COLSUMS.clear()
-            st._PENDING_WRED.clear()
+            st.col_sums.pending.clear()
+            st.slab_sums.pending.clear()
         else:
-            _flush_colsums()
-    if not st._PENDING_COLSUMS and not st._PENDING_WRED:
+            _flush()
+    if not st.col_sums.pending and not st.slab_sums.pending:
         st._PENDING_TASK = task
-        torch.autograd.Variable._execution_engine.queue_callback(_flush_colsums)
+        torch.autograd.Variable._execution_engine.queue_callback(_flush)
     return True
 
 
-def flush_colsums():
-    """Fill the destinations registered so far (the gradient arena calls this before a segment's all-reduce)."""
-    if st._PENDING_COLSUMS or st._PENDING_WRED:
-        _flush_colsums()
+def flush_deferred():
+    """Fill the destinations registered so far, GroupNorm sums and weight gradients alike (the gradient arena calls
+    this before a segment's all-reduce)."""
+    if st.col_sums.pending or st.slab_sums.pending:
+        _flush()
 
 
-def drop_pending_colsums():
+def drop_deferred():
     """Forget deferred sums of a backward pass that did not complete (capture failure paths)."""
-    st._PENDING_COLSUMS.clear()
-    st._PENDING_WRED.clear()
+    st.col_sums.pending.clear()
+    st.slab_sums.pending.clear()
     st._PENDING_TASK = None
-    for ent in st._WRED_ARENA.values():
-        ent[1] = 0
+    for a in st._WRED_ARENA.values():
+        a.used = 0

@@ -19,6 +19,18 @@ def _gn_forward(x, gamma, beta, groups, silu):
     return y, mean, rstd
 
 
+def _gb_grads(parts, gb):
+    """(dgamma, dbeta) of the parameter pair gb = the column sums over the views of the backward kernel's partials
+    parts (2, S, C), written into the pair's slots of the gradient arena where there is one; filled now or at the flush
+    of the running backward pass (deferred._colsum)."""
+    _, S, C = parts.shape
+    dgb = reducer.ACTIVE.slot_pair(*gb) if reducer.ACTIVE is not None else None
+    if dgb is None:
+        dgb = torch.empty(2, C, device=parts.device, dtype=torch.float32)
+    _colsum(parts, dgb, 2, S, C, gb)
+    return dgb[0], dgb[1]
+
+
 def _gn_backward(ctx, dy, addend, addend2=None):
     x, gamma, beta, mean, rstd = ctx.saved_tensors
     dy = _c(dy)
@@ -36,11 +48,7 @@ def _gn_backward(ctx, dy, addend, addend2=None):
             nbytes=4.0 * x.numel() * (3 + (addend is not None) + (addend2 is not None)))
     if rowsum is not None:
         _rowsum_put(dx, rowsum, None)
-    dgb = reducer.ACTIVE.slot_pair(*ctx.gb) if reducer.ACTIVE is not None else None
-    if dgb is None:
-        dgb = torch.empty(2, C, device=x.device, dtype=torch.float32)
-    _colsum(parts, dgb, 2, S, C, ctx.gb)
-    return dx, dgb[0], dgb[1]
+    return (dx, *_gb_grads(parts, ctx.gb))
 
 
 class _GroupNormFn(torch.autograd.Function):
@@ -110,11 +118,7 @@ class _GroupNormCatSkipFn(torch.autograd.Function):
         _launch("gn_bwd", 0.0, "vf_gn_cat_bwd", _ptr(x1), _ptr(x2), C1, _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(rstd),
                 _ptr(dy), _ptr(d1), _ptr(d2), _ptr(dx1), _ptr(dx2), _ptr(parts[0]), _ptr(parts[1]), None, S, C, H * W,
                 ctx.groups, ctx.silu, _stream(), nbytes=4.0 * dy.numel() * (3 + (d1 is not None)))
-        dgb = reducer.ACTIVE.slot_pair(*ctx.gb) if reducer.ACTIVE is not None else None
-        if dgb is None:
-            dgb = torch.empty(2, C, device=x1.device, dtype=torch.float32)
-        _colsum(parts, dgb, 2, S, C, ctx.gb)
-        return dx1, dx2, dgb[0], dgb[1], None, None
+        return (dx1, dx2, *_gb_grads(parts, ctx.gb), None, None)
 
 
 def cat_fusable(C1, C, HW, groups):

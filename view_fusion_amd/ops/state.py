@@ -39,23 +39,18 @@ class State:
         self.COLSUM_DEFER = True
         self.WRED_DEFER = os.environ.get("VF_WRED_DEFER", "1") != "0"
         self.WRED_DEFER_GENERIC = os.environ.get("VF_WRED_DEFER_GENERIC", "1") != "0"   # the direct / 1x1 kernels' slabs too (round 6)
-        self._PENDING_COLSUMS = []
+        # the two families of deferred launches (deferred._Deferred, set when ops/deferred.py is imported): each owns its
+        # pending entries, its capture table, its per-device ring of staging tables and what its last flush keeps alive
+        self.col_sums = None           # GroupNorm gamma / beta column sums: entries (parts, dgb, batch, S, C)
+        self.slab_sums = None          # weight-gradient slab sums: entries (row of 9 int64, workgroups, (ws, dw, db, db2))
         self._PENDING_TASK = None      # torch._C._current_graph_task_id() of the backward pass the pending entries belong to
-        self._PENDING_WRED = []        # [(row: list of 9 int64, workgroups, keep-alive tensors)]
-        self._CAPTURE_TABLE = None   # [device table (rows x 6 int64), rows used, host rows, keep-alive] while a Trainer is capturing
-        self._CAPTURE_TABLE_W = None  # the same for the deferred slab sums: [device table (rows x 9 int64), rows used, host rows, keep-alive]
-        self._WRED_ARENA = {}          # device -> [arena tensor or None, floats handed out in the running pass]
-        self._CS_TABLE = {}          # device -> {"rows": last uploaded table, "ring": [[pinned, device table, event, rows], ...], "next": i}
-        self._WR_TABLE = {}          # device -> {"ring": [[pinned, device table, event, key, rows, workgroups], ...], "next": i}
+        self._WRED_ARENA = {}          # device -> deferred._Arena (tensor or None, floats handed out in the running pass)
         # ---- Caches
         self._ws = {}
         self._WINO_KIND_CACHE = {}
         self._TA_DESC = {}
         self._TA_GDST = {}
         self._VC_CACHE = []            # [(device view_count tensor, version, (off, S, maxV))], most recent first, bounded
-        # tensors the last flush launches still read (kept until the next flush)
-        self.keep_wred = None
-        self.keep_colsums = None
 
 
 st = State()

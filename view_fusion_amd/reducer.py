@@ -34,8 +34,9 @@ train.Trainer reads the accumulator at iteration numbers every rank computes ali
 step down together (captured collectives -> split replay -> eager): agreement about the launch mode without an extra
 collective and without a per-step host sync.
 
-Deferred GroupNorm column sums (ops._colsum): with the arena the ~70 per-layer launches of a backward pass collapse into
-one multi-tensor launch per SEGMENT -- `_ready` flushes what is pending right before it lets a segment's all-reduce go.
+Deferred GroupNorm column sums and weight-gradient slab sums (ops/deferred.py): with the arena the ~135 per-layer launches
+of a backward pass collapse into one multi-tensor launch of each family per SEGMENT -- `_ready` flushes what is pending
+right before it lets a segment's all-reduce go.
 
 Captured iteration (train.Trainer with a HIP graph, world > 1): the forward runs on leaf aliases of the parameters and
 the gradients come from autograd.grad, so AccumulateGrad and its hooks never run.  `capture_begin(leaves)` maps the
@@ -58,7 +59,7 @@ _ALIGN_IN = 4            # ... and within a layer every slot is 16-byte aligned 
 
 
 class GradArena:
-    flushes_colsums = True      # ops._colsum may defer: every path that releases a gradient flushes first
+    flushes_colsums = True      # ops._colsum and the weight gradients may defer: every path that releases a gradient flushes first
 
     def __init__(self, module, world, segments=6, group=None):
         self.params = [p for p in module.parameters() if p.requires_grad]
@@ -194,7 +195,7 @@ class GradArena:
         self.got[i] = True
         if g.data_ptr() != self.base + 4 * self.off[i] or not g.is_contiguous():
             from . import ops
-            ops.flush_colsums()                               # g may be a deferred destination: fill it before reading
+            ops.flush_deferred()                              # g may be a deferred destination: fill it before reading
             s = self._view(i)
             s.copy_(g)
             g = s
@@ -217,7 +218,7 @@ class GradArena:
 
     def _launch(self, k):
         from . import ops
-        ops.flush_colsums()                                   # deferred GroupNorm sums of this (and earlier) segments
+        ops.flush_deferred()                                  # deferred GroupNorm sums and weight gradients of this (and earlier) segments
         assert k == self.next_seg, (k, self.next_seg)       # the order every rank relies on
         lo, hi = self.seg_range[k]
         if k == len(self.seg_range) - 1:
@@ -289,7 +290,7 @@ class GradArena:
             self.reduce_all()
         else:
             from . import ops
-            ops.flush_colsums()
+            ops.flush_deferred()
             self._reset()
         return out
 
@@ -488,7 +489,7 @@ class XgmiArena(GradArena):
 
     def _launch(self, k):
         from . import _lib, ops
-        ops.flush_colsums()
+        ops.flush_deferred()
         assert k == self.next_seg, (k, self.next_seg)
         nseg = len(self.seg_range)
         if k == nseg - 1:
