@@ -276,6 +276,14 @@ int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, co
 
 /* eval metric next to the path: utils/metrics.py:6-8; out[b] = PSNR of image b (n floats each) */
 int vf_psnr(const float* generated, const float* target, float* out /*[B]*/, int B, int n, void* stream);
+/* ... and utils/metrics.py:11-12 (csrc/ssim.hip): out[b] = SSIM of image b, [B][C][H][W] inputs, any H, W >= 11 and
+ * C >= 1 -- pytorch_msssim.ssim(X, Y, data_range, size_average=False) with its defaults (11-tap Gaussian sigma 1.5,
+ * separable "valid" filtering, K = (0.01, 0.03), no clamp).  window11: DEVICE [11], the normalised fp32 window the
+ * host computed.  workspace: vf_ssim_workspace_floats(B, C, H, W) floats (one partial per 32 x 32 tile), 0 when the
+ * geometry is refused.  Two launches, no atomics: bit-reproducible. */
+long vf_ssim_workspace_floats(int B, int C, int H, int W);
+int vf_ssim(const float* generated, const float* target, float* out /*[B]*/, float* workspace, int B, int C, int H,
+            int W, const float* window11, float data_range, void* stream);
 
 /* ---- optimizer step next to the path: torch.optim.Adam, experiment.py:118-120,293 ----
  * desc = device int64 [ntensors][6] rows {p, g, exp_avg, exp_avg_sq, numel, first_block}, block = 1024 elems */

@@ -5,8 +5,8 @@ MI355X engine (no dataset / wandb / image-grid plumbing):
     7..23 conditioning views), :516-544 (autoregressive 24-step rollout, view_count 1 -> 24),
     :580-599 (weight animation: B=24 target angles x N=6 views in one call)
   * checkpoint wire format ................................. utils/checkpoint.py:31-72
-  * eval reduction: PSNR + all_reduce(AVG) + barriers ...... utils/metrics.py:6-8, utils/dist.py:69-91,
-    experiment.py:314-370
+  * eval reduction: PSNR, SSIM + all_reduce(AVG) + barriers  utils/metrics.py:6-12, utils/dist.py:69-91,
+    experiment.py:314-370 (SSIM is the metric the reference selects best_model_ssim.pt by, :375-380)
 """
 import contextlib
 import math
@@ -115,6 +115,13 @@ def compute_psnr(generated, target):
     return ops.psnr(generated, target)
 
 
+def compute_ssim(generated, target):
+    """pytorch_msssim.ssim(generated, target, data_range=1.0, size_average=False) per image (utils/metrics.py:11-12)
+    as our own kernel: two HIP launches, no third-party package."""
+    from . import ops
+    return ops.ssim(generated, target, data_range=1.0)
+
+
 def reduce_dict(d, average=True):
     """all_reduce every tensor of `d` across ranks (AVG by default), keys in sorted order as the reference
     (utils/dist.py:69-91); identity without a process group.  RCCL has ncclAvg; gloo only SUM, so there the mean is
@@ -141,12 +148,14 @@ def _barrier():
 
 
 @torch.no_grad()
-def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, **inject):
+def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, **inject):
     """The eval reduction of Experiment.eval (experiment.py:314-370): every rank generates its shard of the validation
     batches (view_count ~ U[1, max_views] per sample), PSNR per image on the GPU (utils/metrics.py:6-8), mean over the
     rank's images, barrier, all_reduce(AVG) of the scalars, barrier.  `batches`: iterable of dicts with target (B,3,H,W),
-    cond (B,>=max_views,3,H,W), angle (B,1) and optionally view_count.  extra_metrics: {name: fn(generated, target) ->
-    (B,)} for third-party metrics (the reference's SSIM).  Returns the reduced dict of 0-d tensors."""
+    cond (B,>=max_views,3,H,W), angle (B,1) and optionally view_count.  ssim=True adds the reference's second metric
+    (utils/metrics.py:11-12, images of at least 11 x 11) under "ssim", through the same reduction; the default reports
+    PSNR alone.  extra_metrics: {name: fn(generated, target) -> (B,)} for anything else (merged on top).  Returns the
+    reduced dict of 0-d tensors."""
     gen, gt = [], []
     with _eval_mode(model):                        # Experiment.eval: self.model.eval() (experiment.py:316)
         for b in batches:
@@ -158,6 +167,8 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, **
             gt.append(b["target"])
     _barrier()
     metrics = {"psnr": compute_psnr}
+    if ssim:
+        metrics["ssim"] = compute_ssim                 # module global, looked up now: a host stand-in can be patched in
     metrics.update(extra_metrics or {})
     out = {k: torch.cat([fn(a, t) for a, t in zip(gen, gt)]).mean() for k, fn in metrics.items()}
     _barrier()

@@ -1,11 +1,12 @@
 """The ViewFusion ops around the UNet: view stacking + q_sample, compose / weighted-noise loss, the sampler tail, PSNR
-(reference model/view_fusion.py:70-177, 229-300; utils/metrics.py:6-8)."""
+and SSIM (reference model/view_fusion.py:70-177, 229-300; utils/metrics.py:6-12)."""
 import ctypes
 
 import torch
 
+from .. import _lib
 from .state import st
-from .core import _c, _call, _check, _ptr, _stream
+from .core import _c, _call, _check, _ptr, _stream, _workspace
 
 
 # ---------------------------------------------------------------------------------------------
@@ -146,4 +147,43 @@ def psnr(generated, target):
     B = generated.shape[0]
     out = torch.empty(B, device=generated.device, dtype=torch.float32)
     _call("vf_psnr", _ptr(generated), _ptr(target), _ptr(out), B, generated[0].numel(), _stream())
+    return out
+
+
+SSIM_WIN, SSIM_SIGMA = 11, 1.5
+
+
+def _ssim_window(device):
+    """The normalised 11-tap Gaussian of pytorch_msssim (`_fspecial_gauss_1d`), built with the same fp32 torch
+    operations on the host and kept on the device.  The first call per device copies it there, so it must not be a
+    call inside a graph capture."""
+    win = st._SSIM_WINDOW.get(device)
+    if win is None:
+        coords = torch.arange(SSIM_WIN, dtype=torch.float32)
+        coords -= SSIM_WIN // 2
+        g = torch.exp(-(coords ** 2) / (2 * SSIM_SIGMA ** 2))
+        g /= g.sum()
+        win = st._SSIM_WINDOW[device] = g.to(device)
+    return win
+
+
+def ssim(generated, target, data_range=1.0):
+    """Per-image SSIM (B,) of (B,C,H,W) tensors: pytorch_msssim.ssim(generated, target, data_range,
+    size_average=False) with its defaults, H, W >= 11 (the package skips the smoothing along a shorter side; that
+    quantity is not SSIM and is refused here)."""
+    if generated.dim() != 4 or generated.shape != target.shape:
+        raise ValueError(f"ssim needs two (B,C,H,W) tensors of one shape, got {tuple(generated.shape)} and "
+                         f"{tuple(target.shape)}")
+    B, C, H, W = generated.shape
+    if H < SSIM_WIN or W < SSIM_WIN or C < 1:
+        raise ValueError(f"ssim needs at least one channel and H, W >= {SSIM_WIN} (the window), got "
+                         f"{tuple(generated.shape)}")
+    generated, target = _c(generated), _c(target)
+    _check(generated, target)
+    out = torch.empty(B, device=generated.device, dtype=torch.float32)
+    if B == 0:
+        return out
+    ws = _workspace(generated.device, _lib.load().vf_ssim_workspace_floats(B, C, H, W))
+    _call("vf_ssim", _ptr(generated), _ptr(target), _ptr(out), _ptr(ws), B, C, H, W,
+          _ptr(_ssim_window(generated.device)), float(data_range), _stream())
     return out

@@ -50,7 +50,8 @@ class State:
         self._WINO_KIND_CACHE = {}
         self._TA_DESC = {}
         self._TA_GDST = {}
-        self._VC_CACHE = []            # [(device view_count tensor, version, (off, S, maxV))], most recent first, bounded
+        self._SSIM_WINDOW = {}         # device -> the 11-tap Gaussian window of ops.ssim
+        self._VC_CACHE = []          # [(device view_count tensor, version, (off, S, maxV))], most recent first, bounded
 
 
 st = State()
