@@ -274,6 +274,34 @@ int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, co
                      float* weights /*|NULL*/, int B, int Cout, int HW, int maxV, int weighting, int clip,
                      void* stream);
 
+/* ---- seeded counter-based draws (csrc/rng.h holds the specification: Philox4x32-10, key = seed, counter =
+ *      (float4 block, id lo, id hi, kind << 28 | step)).  ids: DEVICE int64 [B], one identifier per sample; a draw
+ *      depends on (seed, id, kind, step, element) only, never on the sample's row or on the rest of the batch.
+ *      kinds: 0 training scalars, 1 training noise, 2 sampler start noise, 3 reverse-step noise (step = t[b]). ---- */
+/* t[b] = 1 + mulhi32(w0, T-1) (int64, the reference's randint(1, T)), u[b] = (w1 >> 8) 2^-24 (|NULL),
+ * level[b] = (g[t] - g[t-1]) u + g[t-1]; gammas [T], 2 <= T <= 2^28 */
+int vf_draw_train(unsigned long long seed, const long long* ids, const float* gammas, int T, long long* t,
+                  float* u /*[B]|NULL*/, float* level /*[B]*/, int B, void* stream);
+/* out [B][n] standard normals (Box-Muller, cut at 6.76 sigma), n % 4 == 0, 0 <= step < 2^28 */
+int vf_randn_ids(unsigned long long seed, const long long* ids, int kind, int step, float* out, int B, int n,
+                 void* stream);
+/* out [B][n] the raw 32-bit words of the same counters (four per float4 block) */
+int vf_philox_ids(unsigned long long seed, const long long* ids, int kind, int step, unsigned* out, int B, int n,
+                  void* stream);
+/* vf_p_sample_tail with z computed in the kernel from (seed, ids[b], kind 3, t[b], float4 index) instead of loaded;
+ * z = 0 where t[b] == 0.  No step-dependent argument: a captured launch replays for every step. */
+int vf_p_sample_tail_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                         const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                         const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                         const float* posterior_mean_coef1, const float* posterior_mean_coef2,
+                         float* y_next /*|NULL*/, float* mean_out /*|NULL*/, float* weights /*|NULL*/, int B, int Cout,
+                         int HW, int maxV, int weighting, int clip, void* stream);
+/* Host mirrors: the same inline functions run on the CPU.  HOST pointers, no stream, no GPU needed. */
+int vf_rng_host_philox(const unsigned* counter /*[4]*/, const unsigned* key /*[2]*/, unsigned* out /*[4]*/);
+int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, int step, float* out /*[B][n]*/,
+                       int B, int n);
+int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int T, long long* t, float* u, int B);
+
 /* eval metric next to the path: utils/metrics.py:6-8; out[b] = PSNR of image b (n floats each) */
 int vf_psnr(const float* generated, const float* target, float* out /*[B]*/, int B, int n, void* stream);
 /* ... and utils/metrics.py:11-12 (csrc/ssim.hip): out[b] = SSIM of image b, [B][C][H][W] inputs, any H, W >= 11 and

@@ -23,6 +23,7 @@ elif os.environ.get("VF_HIP_LIB"):
     warnings.warn("VF_HIP_LIB is ignored unless VF_DEBUG_AB=1 (kernel-tuning aid)", stacklevel=2)
 
 _P, _I, _L, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
+_U64 = ctypes.c_uint64       # the seed of the counter-based draws (csrc/rng.h)
 
 # name -> argtypes (restype is int unless listed in _RESTYPE)
 SIGNATURES = {
@@ -115,6 +116,13 @@ SIGNATURES = {
     "vf_compose_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vf_compose_mse_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vf_p_sample_tail": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vf_draw_train": [_U64, _P, _P, _I, _P, _P, _P, _I, _P],
+    "vf_randn_ids": [_U64, _P, _I, _I, _P, _I, _I, _P],
+    "vf_philox_ids": [_U64, _P, _I, _I, _P, _I, _I, _P],
+    "vf_p_sample_tail_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vf_rng_host_philox": [_P, _P, _P],
+    "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
+    "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],
 }
 _RESTYPE = {"vf_conv1x1_bf16x3_pack_dwords": _L, "vf_conv_wgrad_ws_floats": _L, "vf_time_affine_ws_floats": _L, "vf_wino_conv_ws_floats": _L, "vf_wino44_conv_ws_floats": _L, "vf_wino_wgrad_ws_floats": _L, "vf_conv_fwd_ws_floats": _L,
             "vf_conv_small_pack_floats": _L, "vf_ssim_workspace_floats": _L}

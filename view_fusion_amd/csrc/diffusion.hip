@@ -5,7 +5,11 @@
 //
 // All HBM-bound and tiny next to the UNet; their point is that NOTHING here needs a host
 // sync: ragged view counts come in as a device prefix-sum array `off[B+1]`.
+//
+// Seeded draws (rng.h: Philox4x32-10 keyed by seed and a per-sample id): draw_train, randn_ids and the reverse-step
+// tail that computes its own z.  Opt-in; the unseeded kernels and entry points are untouched.
 #include "common.h"
+#include "rng.h"
 
 namespace {
 
@@ -192,12 +196,14 @@ __global__ __launch_bounds__(256) void compose_mse_bwd_kernel(const float* __res
 
 // One reverse step after the UNet: compose -> y0_hat = a_t y_t - b_t eps -> clamp ->
 // mean = c1 y0_hat + c2 y_t -> y_{t-1} = mean + z * exp(0.5 logvar).
-__global__ __launch_bounds__(256) void p_sample_tail_kernel(
+// `noise(i, o)` gives z for float4 i of the sample (o = its float offset in [B][3][HW]): a load, or a Philox draw.
+template <class Noise>
+__device__ __forceinline__ void p_sample_tail_body(
     const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
+    const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
     const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
     const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
+    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip, Noise noise) {
     const int b = blockIdx.y;
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
@@ -214,8 +220,7 @@ __global__ __launch_bounds__(256) void p_sample_tail_kernel(
                        a_t * y.w - b_t * eps.w};
         const float ys[4] = {y.x, y.y, y.z, y.w};
         float m[4], r[4];
-        float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (z) zz = *reinterpret_cast<const float4*>(z + o);
+        const float4 zz = noise(i, o);
         const float zs[4] = {zz.x, zz.y, zz.z, zz.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -238,6 +243,79 @@ __global__ __launch_bounds__(256) void p_sample_tail_kernel(
                 *reinterpret_cast<float4*>(weights + (((size_t)b * maxV + j) * 3) * HW + 4 * (size_t)i) = w;
             }
         }
+    }
+}
+
+__global__ __launch_bounds__(256) void p_sample_tail_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
+    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
+    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
+    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
+    p_sample_tail_body(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out, weights, Cout,
+                       HW, maxV, weighting, clip, [z](int, size_t o) {
+                           float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+                           if (z) zz = *reinterpret_cast<const float4*>(z + o);
+                           return zz;
+                       });
+}
+
+// The same step with z drawn in the kernel: kind 3, step = t[b], block = the float4 index; z = 0 where t[b] == 0.
+// t and ids come from device memory, so a captured launch replays for every step.
+__global__ __launch_bounds__(256) void p_sample_tail_rng_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
+    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
+    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
+    float* __restrict__ mean_out, float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    const long long tb = t[blockIdx.y];
+    p_sample_tail_body(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out, weights, Cout,
+                       HW, maxV, weighting, clip, [seed, id, tb](int i, size_t) {
+                           float n[4] = {0.f, 0.f, 0.f, 0.f};
+                           if (tb != 0) vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
+                           return make_float4(n[0], n[1], n[2], n[3]);
+                       });
+}
+
+// Training draws of sample b (kind 0): t[b] in [1, T-1] as int64, u[b] in [0, 1) (optional output) and
+// level[b] = (g[t] - g[t-1]) u + g[t-1]  (view_fusion.py:229-237).
+__global__ void draw_train_kernel(unsigned long long seed, const long long* __restrict__ ids,
+                                  const float* __restrict__ gammas, int T, long long* __restrict__ t,
+                                  float* __restrict__ u, float* __restrict__ level, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t w[4];
+    vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+    const long long tb = vf_rng_timestep(w[0], T);
+    const float ub = vf_rng_uniform24(w[1]);
+    const float hi = gammas[tb], lo = gammas[tb - 1];
+    t[b] = tb;
+    if (u) u[b] = ub;
+    level[b] = (hi - lo) * ub + lo;
+}
+
+// out[b][4 i .. 4 i + 3] = the four normals of (seed, ids[b], kind, step, block i); grid (chunks, B)
+__global__ __launch_bounds__(256) void randn_ids_kernel(unsigned long long seed, const long long* __restrict__ ids,
+                                                        int kind, int step, float4* __restrict__ out, int n4) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    float4* o = out + (size_t)blockIdx.y * n4;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        float n[4];
+        vf_rng_normal4(seed, id, (uint32_t)kind, (uint32_t)step, (uint32_t)i, n);
+        o[i] = make_float4(n[0], n[1], n[2], n[3]);
+    }
+}
+
+// the raw words of the same counters (tests: device against host)
+__global__ __launch_bounds__(256) void philox_ids_kernel(unsigned long long seed, const long long* __restrict__ ids,
+                                                         int kind, int step, uint4* __restrict__ out, int n4) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    uint4* o = out + (size_t)blockIdx.y * n4;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        uint32_t w[4];
+        vf_rng_words(seed, id, (uint32_t)kind, (uint32_t)step, (uint32_t)i, w);
+        o[i] = make_uint4(w[0], w[1], w[2], w[3]);
     }
 }
 
@@ -347,6 +425,77 @@ int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, co
                        posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV,
                        weighting, clip);
     VF_RETURN_LAST_ERROR();
+}
+
+// ---- seeded draws (rng.h) ----
+static inline bool rng_args_ok(int kind, int step) { return kind >= 0 && kind <= 3 && step >= 0 && step < (1 << 28); }
+
+int vf_draw_train(unsigned long long seed, const long long* ids, const float* gammas, int T, long long* t, float* u,
+                  float* level, int B, void* stream) {
+    if (B <= 0) return 0;
+    if (T < 2 || T > (1 << 28)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(draw_train_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, seed, ids, gammas, T,
+                       t, u, level, B);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_randn_ids(unsigned long long seed, const long long* ids, int kind, int step, float* out, int B, int n,
+                 void* stream) {
+    if (B <= 0 || n == 0) return 0;
+    if (n < 0 || (n & 3) || !rng_args_ok(kind, step)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(randn_ids_kernel, dim3(chunks_for(n / 4), B), dim3(256), 0, (hipStream_t)stream, seed, ids, kind,
+                       step, (float4*)out, n / 4);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_philox_ids(unsigned long long seed, const long long* ids, int kind, int step, unsigned* out, int B, int n,
+                  void* stream) {
+    if (B <= 0 || n == 0) return 0;
+    if (n < 0 || (n & 3) || !rng_args_ok(kind, step)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(philox_ids_kernel, dim3(chunks_for(n / 4), B), dim3(256), 0, (hipStream_t)stream, seed, ids, kind,
+                       step, (uint4*)out, n / 4);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_p_sample_tail_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                         const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                         const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                         const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
+                         float* mean_out, float* weights, int B, int Cout, int HW, int maxV, int weighting, int clip,
+                         void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(p_sample_tail_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       unet_out, off, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
+                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV, weighting,
+                       clip);
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirrors: the same inline functions on the CPU, HOST pointers, no stream (the CPU suite's side of the parity).
+int vf_rng_host_philox(const unsigned* counter, const unsigned* key, unsigned* out) {
+    vf_philox4x32_10(counter, key, out);
+    return 0;
+}
+
+int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, int step, float* out, int B, int n) {
+    if (B < 0 || n < 0 || (n & 3) || !rng_args_ok(kind, step)) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b)
+        for (int i = 0; i < n / 4; ++i)
+            vf_rng_normal4(seed, (unsigned long long)ids[b], (uint32_t)kind, (uint32_t)step, (uint32_t)i,
+                           out + (size_t)b * n + 4 * (size_t)i);
+    return 0;
+}
+
+int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int T, long long* t, float* u, int B) {
+    if (B < 0 || T < 2 || T > (1 << 28)) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b) {
+        uint32_t w[4];
+        vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+        t[b] = vf_rng_timestep(w[0], T);
+        u[b] = vf_rng_uniform24(w[1]);
+    }
+    return 0;
 }
 
 }  // extern "C"

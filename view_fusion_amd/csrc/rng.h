@@ -1,0 +1,90 @@
+// Seeded counter-based random draws for training and sampling: Philox4x32-10 (Salmon et al., "Parallel random
+// numbers: as easy as 1, 2, 3", SC'11; the Random123 constants).  This comment is the ONE written specification of
+// the layout; tests/rng_ref.py restates it in numpy, and the host mirrors at the end of diffusion.hip run these very
+// functions on the CPU.
+//
+// A draw is a pure function of (seed, sample id, kind, step, block): no state, no communication, so the noise a
+// sample receives does not depend on its row in the batch, on the rest of the batch or on the rank that holds it.
+//
+//   key     = (seed & 0xffffffff, seed >> 32)                 of the 64-bit `seed`
+//   counter = (block, id & 0xffffffff, id >> 32, stream)      `id`: the sample's 64-bit identifier (device int64[B])
+//   stream  = (kind << 28) | step                             step < 2^28
+//   block   = the float4 index inside the sample's (3, H, W) image; 0 for kind 0
+//
+//   kind 0  training scalars, step 0: word 0 -> t, word 1 -> u
+//   kind 1  training noise, step 0
+//   kind 2  sampler start noise y_T, step 0
+//   kind 3  reverse-step noise z, step = the timestep index t[b]
+//
+// One Philox call gives four 32-bit words w0..w3.
+//   t = 1 + mulhi32(w0, T - 1)          in [1, T - 1] = the reference's randint(1, T); exact integer arithmetic
+//   u = (w1 >> 8) * 2^-24               in [0, 1) as torch.rand; exact in fp32
+//   normals, four per call (Box-Muller): with U(w) = float(w) * 2^-32 + 2^-33 (round to nearest; in (0, 1], so the
+//   logarithm never sees 0; the scale is a power of two, so contracting the multiply-add cannot change the result)
+//     r = sqrtf(-2 * logf(U(w0))), a = 6.283185307179586f * U(w1)  ->  (r * cosf(a), r * sinf(a))
+//     (w2, w3) give the next pair the same way.
+//   The smallest U is 2^-33, so |normal| <= sqrt(66 ln 2) = 6.76: the tails are cut at about 6.7 sigma.
+//   logf / cosf / sinf / sqrtf are the accurate library functions, not the fast `__` intrinsics: the host and the
+//   device libraries then agree to their last-place errors (the tests bound device - float64 by 4 x the float32
+//   restatement's own error).
+//
+// Plain C++: no inline assembly, every value leaves a kernel through an ordinary vector store.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define VF_RNG_HD __host__ __device__ inline
+#else
+#define VF_RNG_HD inline
+#endif
+
+enum { VF_RNG_TRAIN_SCALARS = 0, VF_RNG_TRAIN_NOISE = 1, VF_RNG_START_NOISE = 2, VF_RNG_STEP_NOISE = 3 };
+
+VF_RNG_HD void vf_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// the four words of (seed, id, kind, step, block)
+VF_RNG_HD void vf_rng_words(uint64_t seed, uint64_t id, uint32_t kind, uint32_t step, uint32_t block, uint32_t w[4]) {
+    const uint32_t ctr[4] = {block, (uint32_t)id, (uint32_t)(id >> 32), (kind << 28) | step};
+    const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    vf_philox4x32_10(ctr, key, w);
+}
+
+VF_RNG_HD long long vf_rng_timestep(uint32_t w0, int T) {
+    return 1 + (long long)(((uint64_t)w0 * (uint32_t)(T - 1)) >> 32);
+}
+
+VF_RNG_HD float vf_rng_uniform24(uint32_t w1) { return (float)(w1 >> 8) * 5.9604644775390625e-8f; }   // 2^-24
+
+VF_RNG_HD float vf_rng_open_uniform(uint32_t w) {                                                      // (0, 1]
+    return (float)w * 2.3283064365386963e-10f + 1.1641532182693481e-10f;                               // 2^-32, 2^-33
+}
+
+VF_RNG_HD void vf_rng_box_muller(uint32_t wa, uint32_t wb, float* n0, float* n1) {
+    const float r = sqrtf(-2.0f * logf(vf_rng_open_uniform(wa)));
+    const float a = 6.283185307179586f * vf_rng_open_uniform(wb);
+    *n0 = r * cosf(a);
+    *n1 = r * sinf(a);
+}
+
+// four normals: the float4 `block` of sample `id`
+VF_RNG_HD void vf_rng_normal4(uint64_t seed, uint64_t id, uint32_t kind, uint32_t step, uint32_t block, float n[4]) {
+    uint32_t w[4];
+    vf_rng_words(seed, id, kind, step, block, w);
+    vf_rng_box_muller(w[0], w[1], &n[0], &n[1]);
+    vf_rng_box_muller(w[2], w[3], &n[2], &n[3]);
+}

@@ -34,7 +34,8 @@ def _eval_mode(model):
 # ---- sampler drivers ---------------------------------------------------------------------------
 # Each driver reaches the sampler through model(..., generate=True), like the reference's (DDP wraps forward), and
 # takes the optional injected randomness of ViewFusion.forward (y_t = the start noise, z_seq[i] = the noise of
-# reverse step i) so that its output can be compared with the CPU oracle.
+# reverse step i) so that its output can be compared with the CPU oracle.  seed= (and sample_ids=) reach generate() the
+# same way: the draws then come from the counter-based generator of csrc/rng.h, keyed per sample.
 @torch.no_grad()
 def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None, **inject):
     """Generate with MORE views than the model was trained on (view_count ~ U[max_views+1, 24)),
@@ -50,19 +51,26 @@ def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None
 
 
 @torch.no_grad()
-def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None):
+def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, seed=None, sample_ids=None):
     """Start from ONE view and synthesise the orbit view by view, feeding every sample back as an
     extra conditioning view (count = 1 .. steps; angle = 2*pi/24 * count), experiment.py:516-544.
-    first_view (B,3,H,W) -> samples (B,steps,3,H,W).  y_t / z_seq: per-count lists of injected randomness."""
+    first_view (B,3,H,W) -> samples (B,steps,3,H,W).  y_t / z_seq: per-count lists of injected randomness.
+    seed: the draws of rollout step `count` of object b use the id sample_ids[b] * steps + count - 1 (sample_ids
+    defaults to arange(B)), so every step of every object has noise of its own, independent of the batch."""
     cond = first_view[:, None].contiguous()
     B = cond.shape[0]
     out = []
+    if seed is not None:
+        base = torch.arange(B) if sample_ids is None else torch.as_tensor(sample_ids).reshape(-1).cpu()
+        base = (base.to(torch.int64) * steps).to(cond.device)
     with _eval_mode(model):
         for count in range(1, steps + 1):
             view_count = torch.full((B,), count)
             angle = torch.full((B, 1), 2 * math.pi / 24 * count, device=cond.device)
             inject = dict(y_t=None if y_t is None else y_t[count - 1],
                           z_seq=None if z_seq is None else z_seq[count - 1])
+            if seed is not None:
+                inject.update(seed=seed, sample_ids=base + (count - 1))
             *_, sample = model(y_cond=cond, view_count=view_count, angle=angle, generate=True, **inject)
             cond = torch.cat((cond, sample[:, None]), dim=1)
             out.append(sample)
@@ -148,20 +156,32 @@ def _barrier():
 
 
 @torch.no_grad()
-def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, **inject):
+def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, seed=None, **inject):
     """The eval reduction of Experiment.eval (experiment.py:314-370): every rank generates its shard of the validation
     batches (view_count ~ U[1, max_views] per sample), PSNR per image on the GPU (utils/metrics.py:6-8), mean over the
     rank's images, barrier, all_reduce(AVG) of the scalars, barrier.  `batches`: iterable of dicts with target (B,3,H,W),
     cond (B,>=max_views,3,H,W), angle (B,1) and optionally view_count.  ssim=True adds the reference's second metric
     (utils/metrics.py:11-12, images of at least 11 x 11) under "ssim", through the same reduction; the default reports
     PSNR alone.  extra_metrics: {name: fn(generated, target) -> (B,)} for anything else (merged on top).  Returns the
-    reduced dict of 0-d tensors."""
+    reduced dict of 0-d tensors.
+    seed (default None: torch's device generator, as before): the sampler's noise comes from the counter-based generator
+    keyed by batch["ids"] (B,) -- dataset indices -- so an image's sample, and with it the metrics, do not depend on how
+    the validation set is batched or sharded over ranks.  Without "ids" a running index over this rank's images is
+    used: independent of the batch size, but NOT of the sharding."""
     gen, gt = [], []
+    seen = 0
     with _eval_mode(model):                        # Experiment.eval: self.model.eval() (experiment.py:316)
         for b in batches:
             vc = b.get("view_count")
             if vc is None:
                 vc = torch.randint(1, max_views + 1, (b["target"].shape[0],), generator=generator)
+            n = b["target"].shape[0]
+            if seed is not None:
+                ids = b.get("ids")
+                if ids is None:
+                    ids = torch.arange(seen, seen + n)
+                inject = dict(inject, seed=seed, sample_ids=ids)
+            seen += n
             *_, samples = model(y_cond=b["cond"], view_count=vc, angle=b["angle"], generate=True, **inject)
             gen.append(samples)
             gt.append(b["target"])

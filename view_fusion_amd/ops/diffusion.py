@@ -57,6 +57,73 @@ def gather_level(gammas, t, u=None):
     return level
 
 
+# ---- seeded draws (csrc/rng.h): pure functions of (seed, sample id, kind, step, element) ----
+RNG_TRAIN_NOISE, RNG_START_NOISE, RNG_STEP_NOISE = 1, 2, 3        # kinds (0 = the training scalars of draw_train)
+
+
+def _seed(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def sample_ids(device, B, ids=None):
+    """The per-sample identifiers of the seeded draws as a contiguous device int64 (B,): `ids` (tensor / list) when
+    given, else arange(B), kept per (device, B).  A host-side `ids` is copied to the device here, so hand a device
+    tensor to anything that is captured into a graph."""
+    if ids is None:
+        ids = st._RNG_IDS.get((device, B))
+        if ids is None:
+            ids = st._RNG_IDS[(device, B)] = torch.arange(B, dtype=torch.int64, device=device)
+        return ids
+    ids = torch.as_tensor(ids).reshape(-1)
+    if ids.numel() != B:
+        raise ValueError(f"sample_ids needs one id per sample: {ids.numel()} ids for a batch of {B}")
+    return _c(ids.to(device=device, dtype=torch.int64))
+
+
+def _check_ids(ids, B):
+    if not ids.is_cuda or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.numel() != B:
+        raise _lib.VFHipError(f"ids must be a contiguous device int64 tensor of {B} elements (ops.sample_ids)")
+
+
+def draw_train(seed, ids, gammas, want_u=False):
+    """The training scalars of samples `ids`: -> t (B,) int64 in [1, T-1], level (B,) = (g[t]-g[t-1]) u + g[t-1],
+    u (B,) in [0, 1) | None.  One launch; replaces randint + rand + gather_level."""
+    _check(gammas)
+    B = ids.numel()
+    _check_ids(ids, B)
+    t = torch.empty(B, device=gammas.device, dtype=torch.int64)
+    level = torch.empty(B, device=gammas.device, dtype=torch.float32)
+    u = torch.empty(B, device=gammas.device, dtype=torch.float32) if want_u else None
+    _call("vf_draw_train", _seed(seed), ctypes.c_void_p(ids.data_ptr()), _ptr(gammas), gammas.numel(),
+          ctypes.c_void_p(t.data_ptr()), _ptr(u), _ptr(level), B, _stream())
+    return t, level, u
+
+
+def randn_ids(seed, ids, kind, step, shape, out=None):
+    """Standard normals (B, *shape) for samples `ids`: element e of a sample is normal e % 4 of float4 block e // 4."""
+    B = ids.numel()
+    _check_ids(ids, B)
+    n = 1
+    for d in shape:
+        n *= int(d)
+    if out is None:
+        out = torch.empty(B, *shape, device=ids.device, dtype=torch.float32)
+    _check(out)
+    _call("vf_randn_ids", _seed(seed), ctypes.c_void_p(ids.data_ptr()), int(kind), int(step), _ptr(out), B, n,
+          _stream())
+    return out
+
+
+def philox_ids(seed, ids, kind, step, n):
+    """The raw 32-bit words behind randn_ids (as int32 bit patterns, (B, n)): tests compare them with the host."""
+    B = ids.numel()
+    _check_ids(ids, B)
+    out = torch.empty(B, n, device=ids.device, dtype=torch.int32)
+    _call("vf_philox_ids", _seed(seed), ctypes.c_void_p(ids.data_ptr()), int(kind), int(step),
+          ctypes.c_void_p(out.data_ptr()), B, n, _stream())
+    return out
+
+
 def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True):
     """Ragged stacking (+ optional q_sample): -> x (S,Cc+3,H,W), level_s (S,1), angle_s (S,1); Cc = y_cond's
     channel count (3, or 6 for the `relative` configs)."""
@@ -121,10 +188,13 @@ def compose(unet_out, off, B, max_views, weighting, want_weights=True):
 
 
 def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip=True, want_weights=True,
-                  want_mean=False, inplace=False):
+                  want_mean=False, inplace=False, seed=None, ids=None):
     """Fused compose -> y0_hat -> clamp -> posterior mean -> + z*sigma.
-    Returns (y_next, mean | None, weights | None)."""
+    Returns (y_next, mean | None, weights | None).  seed= (with z=None): z is drawn inside the kernel from
+    (seed, ids[b], t[b], element) and is 0 where t[b] == 0; ids defaults to arange(B)."""
     _check(unet_out, y_t, z)
+    if seed is not None and z is not None:
+        raise ValueError("p_sample_tail takes either z or seed=, not both")
     S, Cout, H, W = unet_out.shape
     t = _c(t.to(torch.int64))
     y_next = y_t if inplace else torch.empty_like(y_t)     # elementwise: safe to overwrite y_t
@@ -132,6 +202,15 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
     wts = None
     if weighting and want_weights:
         wts = torch.empty(B, max_views, 3, H, W, device=y_t.device, dtype=torch.float32)
+    if seed is not None:
+        ids = sample_ids(y_t.device, B, ids)
+        _check_ids(ids, B)
+        _call("vf_p_sample_tail_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _seed(seed),
+              ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(t.data_ptr()), _ptr(sched["sqrt_recip_gammas"]),
+              _ptr(sched["sqrt_recipm1_gammas"]), _ptr(sched["posterior_log_variance_clipped"]),
+              _ptr(sched["posterior_mean_coef1"]), _ptr(sched["posterior_mean_coef2"]), _ptr(y_next), _ptr(mean),
+              _ptr(wts), B, Cout, H * W, max_views, int(weighting), int(clip), _stream())
+        return y_next, mean, wts
     _call("vf_p_sample_tail", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _ptr(z),
               ctypes.c_void_p(t.data_ptr()), _ptr(sched["sqrt_recip_gammas"]), _ptr(sched["sqrt_recipm1_gammas"]),
               _ptr(sched["posterior_log_variance_clipped"]), _ptr(sched["posterior_mean_coef1"]),

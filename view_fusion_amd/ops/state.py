@@ -51,6 +51,7 @@ class State:
         self._TA_DESC = {}
         self._TA_GDST = {}
         self._SSIM_WINDOW = {}         # device -> the 11-tap Gaussian window of ops.ssim
+        self._RNG_IDS = {}             # (device, B) -> arange(B) int64: the default sample ids of the seeded draws
         self._VC_CACHE = []          # [(device view_count tensor, version, (off, S, maxV))], most recent first, bounded
 
 

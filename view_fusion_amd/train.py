@@ -96,6 +96,17 @@ def build_model(unet_params=None, beta_schedule=None, device="cuda", phase="trai
     return vf
 
 
+def step_sample_ids(it, B, rank=0, world=1, global_batch=None):
+    """First sample id of this rank's batch at iteration `it` of a seeded run; sample b of the batch has id + b.
+    id = it * global_batch + rank * B + b with global_batch = world * B by default: the ids of an iteration are the
+    same set however the global batch is split over ranks, and no id repeats across iterations."""
+    if global_batch is None:
+        global_batch = world * B
+    if (rank + 1) * B > global_batch:
+        raise ValueError(f"rank {rank} with a batch of {B} does not fit a global batch of {global_batch}")
+    return it * global_batch + rank * B
+
+
 class _StepGraph:
     """One captured training iteration (forward, backward, Adam) for one batch geometry."""
     __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads")
@@ -116,7 +127,7 @@ class Trainer:
     captured after it has run eagerly `GRAPH_AFTER` times (descriptor tables, packed-weight buffers and optimizer
     state then exist and are only re-used); up to `GRAPH_MAX` graphs share one memory pool (each keeps its own
     gradient tensors, 136 MB for the small UNet).  Eager as before: injected arguments other than the draws t / u /
-    noise (which are graph inputs), a device-resident view_count (reading it back would be a sync per step), a
+    noise and the seeded draws' sample_ids (which are graph inputs; their seed is part of the geometry key), a device-resident view_count (reading it back would be a sync per step), a
     kernel log, torch DDP as the reducer (VF_REDUCER=ddp).  world > 1 with the gradient arena has three launch modes
     (`self.mode`): "split" (the default: forward + backward replayed, the six segment all-reduces and the Adam launch
     issued eagerly after each replay), "captured" (VF_CAPTURE_COLLECTIVES=1: the collectives recorded into the graph on
@@ -134,8 +145,13 @@ class Trainer:
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
     inject_capture_failure = None   # set by tests (class or instance attribute), never read from the environment
 
-    def __init__(self, model, world=1, local_rank=0, lr_warmup=2500, decay_it=4000000, bucket_cap_mb=32, graph=None):
+    def __init__(self, model, world=1, local_rank=0, lr_warmup=2500, decay_it=4000000, bucket_cap_mb=32, graph=None,
+                 seed=None, global_batch=None):
         self.module = model
+        # seed: the training draws come from the counter-based generator (csrc/rng.h) keyed by a global sample index
+        # (step_sample_ids), not from torch's device generator; None (default): as before
+        self.seed, self.global_batch = seed, global_batch
+        self._ids = {}              # B -> (arange(B), this iteration's ids): device int64, rewritten in place per step
         self.model = model
         self.arena = None
         kind = os.environ.get("VF_REDUCER", "arena")
@@ -251,8 +267,12 @@ class Trainer:
         from . import ops
         if not self.use_graph or ops.st.KERNEL_LOG is not None or (self.arena is not None and self.arena.flat is None):
             return None
-        if any(k not in ("t", "u", "noise") for k in extra):       # injected draws are graph inputs, nothing else is
+        # injected draws are graph inputs, and so are the sample ids of the seeded draws; the seed is a constant of the
+        # captured launches, so it is part of the key; nothing else is
+        if any(k not in ("t", "u", "noise", "seed", "sample_ids") for k in extra):
             return None
+        seed = extra.get("seed")
+        extra = {k: v for k, v in extra.items() if k != "seed" and v is not None}
         vc = batch["view_count"]
         if torch.is_tensor(vc):
             if vc.is_cuda:          # reading it back would be a device sync per step
@@ -270,7 +290,7 @@ class Trainer:
         # schedule buffer -- set_new_noise_schedule() makes new tensors -- and the parameter storage)
         g = getattr(self.module, "gammas", None)
         anchors = (g.data_ptr() if torch.is_tensor(g) else 0, self._params[0].data_ptr(), self._params[-1].data_ptr())
-        return tuple((k, tuple(t.shape), t.dtype) for k, t in ts) + (anchors, sum(vc)), vc
+        return tuple((k, tuple(t.shape), t.dtype) for k, t in ts) + (anchors + (seed,), sum(vc)), vc
 
     def _capture(self, e, key, vc, batch, extra):
         from . import ops
@@ -310,7 +330,9 @@ class Trainer:
                     leaves = {n: p.detach().requires_grad_(True) for n, p in self._named}
                     if arena is not None:              # gradients are born in (or moved into) the all-reduce buffer
                         arena.capture_begin(list(leaves.values()))
-                    loss = torch.func.functional_call(self.model, leaves, (), dict(view_count=e.view_count, **e.inputs))
+                    seeded = {} if extra.get("seed") is None else dict(seed=extra["seed"])
+                    loss = torch.func.functional_call(self.model, leaves, (),
+                                                      dict(view_count=e.view_count, **e.inputs, **seeded))
                     grads = torch.autograd.grad(loss, list(leaves.values()), allow_unused=True)
                     if arena is not None:
                         grads = arena.capture_finish(grads)
@@ -360,9 +382,24 @@ class Trainer:
         self.graph_steps += 1
         return e.loss.clone()
 
+    def _step_ids(self, batch):
+        """This iteration's sample ids, written (one launch, no host buffer) into the per-B device tensor."""
+        B, dev = batch["y_0"].shape[0], batch["y_0"].device
+        ent = self._ids.get(B)
+        if ent is None:
+            ent = self._ids[B] = (torch.arange(B, dtype=torch.int64, device=dev),
+                                  torch.empty(B, dtype=torch.int64, device=dev))
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        torch.add(ent[0], step_sample_ids(self.it, B, rank, self.world, self.global_batch), out=ent[1])
+        return ent[1]
+
     def step(self, batch, **extra):
         """One reference iteration; returns the (device) loss tensor, no host sync."""
         self.it += 1
+        if self.seed is not None and "seed" not in extra:
+            extra = dict(extra, seed=self.seed)
+            if extra.get("sample_ids") is None:
+                extra["sample_ids"] = self._step_ids(batch)
         lr = self.sched.get_cur_lr(self.it)
         for gparam in self.opt.param_groups:
             gparam["lr"] = lr

@@ -14,6 +14,11 @@ Extras (default None = reference behaviour): `forward(..., t=, u=)` and
 `generate(..., z_seq=)` / `forward(generate=True, y_t=, z_seq=)` inject the random draws so that
 runs -- also the sampler drivers, which reach generate() through forward() as the reference's
 do -- can be compared against the CPU oracle; `sample()` is an alias of `generate()`.
+
+`seed=` (with optional `sample_ids=`, default arange(B)) on `forward` / `generate` takes every draw that was not
+injected from the counter-based generator of csrc/rng.h instead of torch's device generator: a draw is then a function
+of (seed, sample id, purpose, step, element) alone -- the same for a sample whatever its row, its batch or its rank --
+and tests/rng_ref.py can restate it on the CPU.
 """
 import torch
 from torch import nn
@@ -91,19 +96,27 @@ class ViewFusion(nn.Module):
         return y, (out[:, 3:, ...] if w_on else None), weights
 
     @torch.no_grad()
-    def generate(self, y_cond, view_count, angle, y_t=None, sample_num=8, z_seq=None, use_graph=None):
+    def generate(self, y_cond, view_count, angle, y_t=None, sample_num=8, z_seq=None, use_graph=None, seed=None,
+                 sample_ids=None):
         """Reverse diffusion over all T steps (reference view_fusion.py:179-214).
 
         use_graph (default: on for GPU tensors with S <= 16 stacked views): one reverse step -- level gather, re-stack of
         y_t, the whole UNet forward and the fused compose/posterior tail (~260 launches) -- is
         captured once into a HIP graph and replayed T times, so the loop is not launch-bound at
         small S.  Per step the host only refreshes the step index and the noise buffer.
+
+        seed (default None: torch's device generator): y_T and every step's z come from the counter-based generator
+        (csrc/rng.h), keyed by `sample_ids` (default arange(B)); z is computed inside the tail kernel, so the host
+        only refreshes the step index.  An injected y_t / z_seq still wins, each on its own.
         """
         from . import ops
         b = y_cond.shape[0]
         assert self.num_timesteps > sample_num, "num_timesteps must greater than sample_num"
         every = self.num_timesteps // sample_num
-        if y_t is None:
+        ids = None if seed is None else ops.sample_ids(y_cond.device, b, sample_ids)
+        if y_t is None and seed is not None:
+            y_t = ops.randn_ids(seed, ids, ops.diffusion.RNG_START_NOISE, 0, (3,) + tuple(y_cond.shape[-2:]))
+        elif y_t is None:
             y_t = torch.randn_like(y_cond[:, :1, :3, ...]).squeeze(dim=1)
         y = y_t.contiguous().clone()                      # updated in place, step after step
         dev = y.device
@@ -113,7 +126,8 @@ class ViewFusion(nn.Module):
         if use_graph is None:                             # measured: replay wins while the step is launch-bound
             use_graph = y.is_cuda and S <= 16   # (at S = 12 replay and eager tie, but replay is immune to host jitter)
         t = torch.full((b,), self.num_timesteps - 1, device=dev, dtype=torch.long)
-        z = torch.zeros_like(y)
+        z_seed = seed if z_seq is None else None          # the tail draws z itself: no noise buffer
+        z = None if z_seed is not None else torch.zeros_like(y)
         y_cond = y_cond.contiguous()
         angle = angle.contiguous()
         # the conditioning half of the stacked input never changes: copy it once
@@ -121,7 +135,8 @@ class ViewFusion(nn.Module):
 
         def step():
             _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False)
-            _, _, weights = ops.p_sample_tail(out, off, y, z, t, sched, b, max_v, w_on, inplace=True)
+            _, _, weights = ops.p_sample_tail(out, off, y, z, t, sched, b, max_v, w_on, inplace=True, seed=z_seed,
+                                              ids=ids)
             return out, weights
 
         graph = None
@@ -141,7 +156,9 @@ class ViewFusion(nn.Module):
         ret, logit_arr, weight_arr = [y_t], [], []
         for i in reversed(range(self.num_timesteps)):
             t.fill_(i)
-            if i == 0:
+            if z is None:                                  # seeded: the tail kernel draws z (0 at step 0) itself
+                pass
+            elif i == 0:
                 z.zero_()
             elif z_seq is not None:
                 z.copy_(z_seq[i])
@@ -166,20 +183,35 @@ class ViewFusion(nn.Module):
 
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
-                z_seq=None, use_graph=None):
+                z_seq=None, use_graph=None, seed=None, sample_ids=None):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
-            return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph)
+            return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
+                                 sample_ids=sample_ids)
         from . import ops
         b = y_0.shape[0]
         dev = y_0.device
+        level = None
+        if seed is not None:              # whatever was not injected comes from the counter-based generator
+            ids = ops.sample_ids(dev, b, sample_ids)
+            if t is None or u is None:
+                t_d, level_d, u_d = ops.draw_train(seed, ids, self.gammas, want_u=t is not None)
+                if t is None and u is None:
+                    t, level = t_d, level_d
+                elif t is None:
+                    t = t_d
+                else:
+                    u = u_d
+            if noise is None:             # a launch of its own in front of the stacking kernel (which is unchanged)
+                noise = ops.randn_ids(seed, ids, ops.diffusion.RNG_TRAIN_NOISE, 0, tuple(y_0.shape[1:]))
         # same draw order as the reference: t, u, noise
         if t is None:
             t = torch.randint(1, self.num_timesteps, (b,), device=dev).long()
-        if u is None:
+        if u is None and level is None:
             u = torch.rand((b, 1), device=dev)
         if noise is None:
             noise = torch.randn_like(y_0)
-        level = ops.gather_level(self.gammas, t, u.reshape(-1).contiguous())
+        if level is None:
+            level = ops.gather_level(self.gammas, t, u.reshape(-1).contiguous())
         off, S, _ = ops.view_offsets(view_count, dev)
         x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S)
         out = self.denoise_fn(x, angle_s, level_s)
