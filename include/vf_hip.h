@@ -324,6 +324,28 @@ int vf_adam_multi_dev(const void* desc, int ntensors, long total_blocks, const f
 /* scalars[0..2] = {lr, bc1, bc2}, enqueued on `stream` (values carried as launch arguments) */
 int vf_adam_set_scalars(float* scalars, float lr, float bc1, float bc2, void* stream);
 
+/* ---- opt-in extras of the fused step (optim.FusedAdam(ema_decay=, max_grad_norm=)): global-norm gradient clipping and an
+ *      exponential moving average of the weights; the three entry points above are what runs when both are off ----
+ * partial[b] = sum of squares, in double, of the gradient elements of block b (b < total_blocks) of one descriptor table */
+int vf_grad_sumsq_multi(const void* desc, int ntensors, long total_blocks, double* partial, void* stream);
+/* one workgroup, fixed order, double: out[0] = norm = sqrt(sum of partial[0..n)), out[1] = scale =
+ * min(1, max_norm[0] / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_); max_norm: DEVICE float, or NULL for scale = 1 */
+int vf_grad_norm_finish(const double* partial, long n, const float* max_norm, float* out, void* stream);
+/* vf_adam_multi with gscale (device float or NULL): the update reads g * gscale[0], the stored gradient stays raw; and
+ * ema_tab (device float*[ntensors], one EMA tensor per descriptor row, or NULL) + ema_scal (device {d, 1 - d}):
+ * ema = fma(d, ema, (1 - d) p_new) after the parameter update */
+int vf_adam_multi_ex(const void* desc, const void* ema_tab, int ntensors, long total_blocks, float lr, float beta1,
+                     float beta2, float eps, float bias_correction1, float bias_correction2, const float* gscale,
+                     const float* ema_scal, void* stream);
+/* the same with {lr, 1-beta1^t, 1-beta2^t} read from device memory, as vf_adam_multi_dev */
+int vf_adam_multi_ex_dev(const void* desc, const void* ema_tab, int ntensors, long total_blocks, const float* scalars,
+                         float beta1, float beta2, float eps, const float* gscale, const float* ema_scal, void* stream);
+/* scalars[0..2] = {lr, bc1, bc2} (skipped when scalars is NULL) and xs[0..2] = {ema decay d, 1 - d, max_norm} */
+int vf_adam_set_scalars_ex(float* scalars, float lr, float bc1, float bc2, float* xs, float ema_d, float ema_omd,
+                           float max_norm, void* stream);
+/* exchange p <-> ema in place for every row (desc: only p, numel, first_block are read) */
+int vf_swap_multi(const void* desc, const void* ema_tab, int ntensors, long total_blocks, void* stream);
+
 /* ---- gradient exchange next to the path: replaces DistributedDataParallel's bucketed NCCL
  *      all-reduce + optimizer.step(), experiment.py:104-107, 118-120, 292-293 -- a one-shot all-reduce over IPC-mapped
  *      peer gradient arenas fused with the Adam update (csrc/xgmi.hip; host side reducer.XgmiArena, VF_REDUCER=xgmi).

@@ -15,3 +15,12 @@ __device__ __forceinline__ void vf_adam_update(float& p, float g, float& m, floa
     const float den = __builtin_fmaf(sqrtf(v), rs, eps);
     p = p - (step * m) / den;
 }
+
+// The weight average kept beside the live parameters (optim.FusedAdam(ema_decay=...)), applied to ONE element after the
+// parameter update:  ema = fma(d, ema, (1 - d) p_new).  Two roundings: the product (1 - d) p_new is rounded to float,
+// then d * ema + that product is rounded once by the fused multiply-add.  d and omd = 1 - d are each rounded from the
+// host's double to float before the launch (omd is NOT recomputed from the rounded d).
+__device__ __forceinline__ void vf_ema_update(float& ema, float p_new, float d, float omd) {
+#pragma clang fp contract(off)
+    ema = __builtin_fmaf(d, ema, omd * p_new);
+}

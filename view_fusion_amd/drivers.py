@@ -108,11 +108,15 @@ def save_checkpoint(path, model, optimizer, **extra):
 
 
 def load_checkpoint(path, model, optimizer=None, device=None):
-    """Loads "model" (and "optimizer" if given and present); returns the remaining entries."""
+    """Loads "model" (and "optimizer" if given and present); returns the remaining entries.
+    An "ema" entry (save_checkpoint(..., ema=trainer.ema_state_dict())) is restored into an optimizer that keeps a
+    weight EMA (optim.FusedAdam(ema_decay=...)) and, like every extra entry, also returned."""
     sd = torch.load(path, map_location=device, weights_only=False)
     model.load_state_dict(sd["model"])
     if optimizer is not None and "optimizer" in sd and sd["optimizer"].get("state"):
         optimizer.load_state_dict(sd["optimizer"])
+    if sd.get("ema") and getattr(optimizer, "ema_decay", None) is not None:
+        optimizer.load_ema_state_dict(sd["ema"])
     return {k: v for k, v in sd.items() if k not in ("model", "optimizer")}
 
 

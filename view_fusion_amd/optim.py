@@ -9,6 +9,20 @@ Step counts are per parameter, as in torch: the parameters of a group that share
 "bucket" = one launch (in the ViewFusion UNet every parameter receives a gradient every iteration, so
 there is exactly one bucket); a parameter that joins later (first gradient at iteration k) gets a bucket
 of its own with its own bias corrections.
+
+Two opt-in extras ride the same launch (both off by default: the step is then exactly the launch described above):
+
+  * `max_grad_norm`: global-norm gradient clipping, `torch.nn.utils.clip_grad_norm_`'s arithmetic.  Two extra launches
+    take the L2 norm of ALL gradients of the step (per-block partial sums in double, one workgroup adds them in a fixed
+    order: no atomics, bit-reproducible) and leave {norm, scale = min(1, max_norm / (norm + 1e-6))} in device memory; the
+    update reads g * scale.  The STORED gradients are not scaled: `p.grad` after a step is the raw gradient.
+    `grad_norm` is a 0-d device tensor with the last step's pre-clip norm (reading it is the caller's sync, the step has
+    none).  `max_grad_norm=float("inf")` measures the norm without ever clipping (scale == 1: bit-identical updates).
+  * `ema_decay`: an exponential moving average of the weights, ema = fma(d, ema, (1 - d) p_new) per element in the same
+    launch (csrc/adam_update.h states the rounding).  The EMA tensors start as copies of the parameters at a
+    parameter's first step; with `ema_warmup` the decay of the update number t (0 for the first) is
+    min(ema_decay, (1 + t) / (10 + t)).  `ema_state_dict()` / `load_ema_state_dict()` keep them OUTSIDE `state_dict()`,
+    which stays torch's.  `swap_ema()` exchanges parameters and EMA in place (see train.Trainer.ema_weights).
 """
 import ctypes
 
@@ -18,10 +32,139 @@ from . import _lib, ops
 
 
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, ema_decay=None, ema_warmup=False,
+                 max_grad_norm=None):
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
+        if ema_warmup and ema_decay is None:
+            raise ValueError("ema_warmup needs ema_decay")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"max_grad_norm must be positive, got {max_grad_norm}")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         self._plans = {}          # per param group: buckets of {descriptor rows, staging buffers, step count}
         self.graph_epoch = 0      # bumped whenever the state tensors a captured step addresses are replaced
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self._max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self._ema = {}            # parameter -> its EMA tensor (kept out of self.state: state_dict() stays torch's)
+        self._ema_t = 0           # EMA updates so far
+        self._xs = None           # device float[8]: {d, 1 - d, max_norm, norm, scale, -, -, -}
+        self._partials = None     # device double[blocks]: the norm pass' per-block sums
+        self._swap = None         # swap_ema()'s descriptor table
+
+    # -- the opt-in extras: weight EMA, global-norm clipping ------------------------------------------------------------
+    @property
+    def _extras(self):
+        return self.ema_decay is not None or self.max_grad_norm is not None
+
+    def _xs_buf(self, dev):
+        if self._xs is None or self._xs.device != dev:
+            self._xs = torch.zeros(8, device=dev, dtype=torch.float32)
+        return self._xs
+
+    def _xs_ptr(self, i):
+        return ctypes.c_void_p(self._xs.data_ptr() + 4 * i)
+
+    @property
+    def max_grad_norm(self):
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        """The VALUE may change at any time (the kernels read it from device memory, a captured step included); whether
+        the norm launches exist at all is fixed at construction, and with it what a captured step contains."""
+        if (value is None) != (self._max_grad_norm is None):
+            raise ValueError("max_grad_norm cannot be switched on or off after construction (the norm launches are part "
+                             "of the step a graph captured); pass float('inf') to measure the norm without clipping")
+        if value is not None and not float(value) > 0.0:
+            raise ValueError(f"max_grad_norm must be positive, got {value}")
+        self._max_grad_norm = None if value is None else float(value)
+
+    @property
+    def grad_norm(self):
+        """0-d device tensor: the global L2 norm of the last step's gradients before clipping (a view of memory the
+        norm pass writes: it follows every step, captured ones included).  None without max_grad_norm."""
+        if self.max_grad_norm is None:
+            return None
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.is_cuda:
+                    return self._xs_buf(p.device)[3]
+        return None
+
+    def _ema_scalars(self):
+        """(d, 1 - d) of the coming EMA update, in double."""
+        if self.ema_decay is None:
+            return 0.0, 0.0
+        d = self.ema_decay
+        if self.ema_warmup:
+            d = min(d, (1.0 + self._ema_t) / (10.0 + self._ema_t))
+        return d, 1.0 - d
+
+    def _ema_of(self, p):
+        e = self._ema.get(p)
+        if e is None:
+            e = self._ema[p] = p.detach().clone(memory_format=torch.contiguous_format)
+        return e
+
+    def _all_params(self):
+        return [p for group in self.param_groups for p in group["params"]]
+
+    def ema_state_dict(self):
+        """{"num_updates": EMA updates so far, "state": {index: EMA tensor}} with the index = the parameter's position
+        over all groups, like torch's optimizer state.  The tensors are the live ones, not copies (as in torch's
+        state_dict()): between two swap_ema() calls -- inside train.Trainer.ema_weights() -- they hold the LIVE weights."""
+        return dict(num_updates=self._ema_t,
+                    state={i: self._ema[p] for i, p in enumerate(self._all_params()) if p in self._ema})
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd):
+        if self.ema_decay is None:
+            raise _lib.VFHipError("load_ema_state_dict: this optimizer was built without ema_decay")
+        params, created = self._all_params(), False
+        for i, t in sd["state"].items():
+            p = params[int(i)]
+            if tuple(t.shape) != tuple(p.shape):
+                raise _lib.VFHipError(f"load_ema_state_dict: entry {i} has shape {tuple(t.shape)}, the parameter "
+                                      f"{tuple(p.shape)}")
+            if p in self._ema:                        # in place: captured steps keep addressing this tensor
+                self._ema[p].copy_(t)
+            else:
+                self._ema[p] = t.detach().to(device=p.device, dtype=torch.float32, copy=True).contiguous()
+                created = True
+        self._ema_t = int(sd["num_updates"])
+        if created:
+            for gi in self._plans:
+                self._flush_steps(gi)
+            self._plans = {}
+            self.graph_epoch += 1
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange parameters and EMA IN PLACE, one launch: the contents move, every address stays (captured graphs and
+        the packed-weight caches address parameter memory by raw pointer; the version counters are bumped so the packs
+        refresh).  Calling it twice restores both bit for bit."""
+        if self.ema_decay is None:
+            raise _lib.VFHipError("swap_ema: this optimizer was built without ema_decay")
+        params = self._all_params()
+        for p in params:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.VFHipError("FusedAdam needs contiguous float32 GPU parameters")
+        key = tuple((p.data_ptr(), self._ema_of(p).data_ptr()) for p in params)
+        sw = self._swap
+        if sw is None or sw["key"] != key:
+            rows, first = [], 0
+            for p in params:
+                rows.append([p.data_ptr(), 0, 0, 0, p.numel(), first])
+                first += (p.numel() + 1023) // 1024
+            dev = params[0].device
+            sw = self._swap = dict(key=key, blocks=first, numel=sum(p.numel() for p in params),
+                                   dev=torch.tensor(rows, dtype=torch.int64).to(dev),
+                                   ema=torch.tensor([e for _, e in key], dtype=torch.int64).to(dev))
+        ops._launch("adam", 0.0, "vf_swap_multi", ctypes.c_void_p(sw["dev"].data_ptr()),
+                    ctypes.c_void_p(sw["ema"].data_ptr()), len(params), sw["blocks"],
+                    ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), nbytes=16.0 * sw["numel"])
+        torch.autograd.graph.increment_version(params)
 
     # -- descriptor tables ---------------------------------------------------------------------------------------
     def _flush_steps(self, gi):
@@ -40,6 +183,9 @@ class FusedAdam(torch.optim.Optimizer):
         parameter (created if missing), one common step count, advanced by one here.  Returns (handle, (lr, 1-b1^t,
         1-b2^t, b1, b2, eps)); the caller's kernels update p / exp_avg / exp_avg_sq in place (adam.hip's arithmetic), so
         `state_dict()` stays torch's and a later plain `step()` continues from the same counters."""
+        if self._extras:
+            raise _lib.VFHipError("FusedAdam.external_begin: ema_decay / max_grad_norm are not part of an external "
+                                  "reducer's fused update (the xgmi all-reduce + Adam kernel); leave both off there")
         if len(self.param_groups) != 1:
             raise _lib.VFHipError("FusedAdam.external_begin: one parameter group")
         group = self.param_groups[0]
@@ -99,6 +245,9 @@ class FusedAdam(torch.optim.Optimizer):
                                 host=[torch.tensor(rows, dtype=torch.int64).pin_memory() for _ in range(2)],
                                 dev=[torch.empty(len(rows), 6, dtype=torch.int64, device=dev) for _ in range(2)],
                                 ptrs=[None, None], done=[None, None], flip=0))
+            if self.ema_decay is not None:             # one EMA pointer per descriptor row (a table of its own: the
+                # row layout above is shared with csrc/xgmi.hip); EMA tensors are born as copies of the parameters
+                buckets[-1]["ema_dev"] = torch.tensor([self._ema_of(p).data_ptr() for p in ps], dtype=torch.int64).to(dev)
         plan = dict(key=key, buckets=buckets)
         self._plans[gi] = plan
         return plan
@@ -128,7 +277,13 @@ class FusedAdam(torch.optim.Optimizer):
         if len(b["params"]) != len(self.param_groups[0]["params"]):
             return None
         rows = b["host"][0].clone()
-        return dict(bucket=b, rows=rows, epoch=self.graph_epoch, dev=torch.empty(rows.shape, dtype=torch.int64, device=b["params"][0].device))
+        h = dict(bucket=b, rows=rows, epoch=self.graph_epoch, dev=torch.empty(rows.shape, dtype=torch.int64, device=b["params"][0].device))
+        if self._extras:                               # what the extra launches of the captured step address
+            dev = b["params"][0].device
+            h["xs"] = self._xs_buf(dev)
+            if self.max_grad_norm is not None:
+                h["partials"] = torch.empty(b["blocks"], dtype=torch.float64, device=dev)
+        return h
 
     @torch.no_grad()
     def step_captured(self, h, scalars):
@@ -136,6 +291,17 @@ class FusedAdam(torch.optim.Optimizer):
         gradient addresses this capture allocated) are uploaded by `graph_end` once the capture has ended."""
         b, group = h["bucket"], self.param_groups[0]
         b1, b2 = group["betas"]
+        if self._extras:
+            raw = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            desc, n, clip, ema = ctypes.c_void_p(h["dev"].data_ptr()), len(b["params"]), "partials" in h, "ema_dev" in b
+            if clip:
+                part = ctypes.c_void_p(h["partials"].data_ptr())
+                _lib.call("vf_grad_sumsq_multi", desc, n, b["blocks"], part, raw)
+                _lib.call("vf_grad_norm_finish", part, b["blocks"], self._xs_ptr(2), self._xs_ptr(3), raw)
+            _lib.call("vf_adam_multi_ex_dev", desc, ctypes.c_void_p(b["ema_dev"].data_ptr()) if ema else None, n,
+                      b["blocks"], ctypes.c_void_p(scalars.data_ptr()), float(b1), float(b2), float(group["eps"]),
+                      self._xs_ptr(4) if clip else None, self._xs_ptr(0) if ema else None, raw)
+            return
         _lib.call("vf_adam_multi_dev", ctypes.c_void_p(h["dev"].data_ptr()), len(b["params"]), b["blocks"],
                   ctypes.c_void_p(scalars.data_ptr()), float(b1), float(b2), float(group["eps"]),
                   ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
@@ -154,8 +320,16 @@ class FusedAdam(torch.optim.Optimizer):
         b, group = h["bucket"], self.param_groups[0]
         b["t"] += 1
         b1, b2 = group["betas"]
-        _lib.call("vf_adam_set_scalars", ctypes.c_void_p(scalars.data_ptr()), float(group["lr"]), 1.0 - b1 ** b["t"],
-                  1.0 - b2 ** b["t"], ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        if self._extras:
+            d, omd = self._ema_scalars()
+            _lib.call("vf_adam_set_scalars_ex", ctypes.c_void_p(scalars.data_ptr()), float(group["lr"]),
+                      1.0 - b1 ** b["t"], 1.0 - b2 ** b["t"], self._xs_ptr(0), d, omd, self.max_grad_norm or 0.0,
+                      ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+            if self.ema_decay is not None:
+                self._ema_t += 1
+        else:
+            _lib.call("vf_adam_set_scalars", ctypes.c_void_p(scalars.data_ptr()), float(group["lr"]), 1.0 - b1 ** b["t"],
+                      1.0 - b2 ** b["t"], ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         torch.autograd.graph.increment_version(b["params"])
 
     # -- the step ------------------------------------------------------------------------------------------------
@@ -167,6 +341,9 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         stream = torch.cuda.current_stream()
         raw = ctypes.c_void_p(stream.cuda_stream)
+        if self._extras:
+            self._step_extras(stream, raw)
+            return loss
         for gi, group in enumerate(self.param_groups):
             if not any(p.grad is not None for p in group["params"]):
                 continue
@@ -174,22 +351,7 @@ class FusedAdam(torch.optim.Optimizer):
             for b in self._plan(gi, group)["buckets"]:
                 b["t"] += 1
                 t = b["t"]
-                grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in b["params"]]
-                ptrs = [g.data_ptr() for g in grads]
-                f = b["flip"]
-                if b["ptrs"][f] != ptrs:               # gradient arena / stable allocations: the table is reused as is
-                    f = b["flip"] = f ^ 1
-                    if b["ptrs"][f] != ptrs:
-                        # two staging buffers, each guarded by an event: the H2D copy that last read this pinned
-                        # buffer (two steps ago) must have executed before the host overwrites it -- the host may
-                        # run several iterations ahead of the GPU
-                        if b["done"][f] is not None:
-                            b["done"][f].synchronize()
-                        b["host"][f][:, 1] = torch.tensor(ptrs, dtype=torch.int64)
-                        b["dev"][f].copy_(b["host"][f], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record(stream)
-                        b["done"][f], b["ptrs"][f] = ev, ptrs
+                f, grads = self._grad_table(b, stream)    # (grads: a .contiguous() copy lives until the launch is enqueued)
                 ops._launch("adam", 0.0, "vf_adam_multi", ctypes.c_void_p(b["dev"][f].data_ptr()), len(grads), b["blocks"],
                             float(group["lr"]), float(b1), float(b2), float(group["eps"]), 1.0 - b1 ** t, 1.0 - b2 ** t,
                             raw, nbytes=28.0 * b["numel"])   # 4 reads + 3 writes
@@ -197,3 +359,66 @@ class FusedAdam(torch.optim.Optimizer):
                 # which are keyed on the version counter) that the parameters changed
                 torch.autograd.graph.increment_version(b["params"])
         return loss
+
+    def _grad_table(self, b, stream):
+        """Bucket b's descriptor table with this step's gradient addresses -> (which of its two copies, the gradient
+        tensors the table points at: the caller keeps them until every launch that reads the table is enqueued)."""
+        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in b["params"]]
+        ptrs = [g.data_ptr() for g in grads]
+        f = b["flip"]
+        if b["ptrs"][f] != ptrs:               # gradient arena / stable allocations: the table is reused as is
+            f = b["flip"] = f ^ 1
+            if b["ptrs"][f] != ptrs:
+                # two staging buffers, each guarded by an event: the H2D copy that last read this pinned
+                # buffer (two steps ago) must have executed before the host overwrites it -- the host may
+                # run several iterations ahead of the GPU
+                if b["done"][f] is not None:
+                    b["done"][f].synchronize()
+                b["host"][f][:, 1] = torch.tensor(ptrs, dtype=torch.int64)
+                b["dev"][f].copy_(b["host"][f], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(stream)
+                b["done"][f], b["ptrs"][f] = ev, ptrs
+        return f, grads
+
+    def _step_extras(self, stream, raw):
+        """step() with max_grad_norm and / or ema_decay: the norm over ALL gradients of the step first (every group and
+        bucket), then one update launch per bucket that reads the scale and carries the EMA."""
+        work = []
+        for gi, group in enumerate(self.param_groups):
+            if not any(p.grad is not None for p in group["params"]):
+                continue
+            for b in self._plan(gi, group)["buckets"]:
+                b["t"] += 1
+                work.append((group, b) + self._grad_table(b, stream))
+        if not work:
+            return
+        dev = work[0][1]["params"][0].device
+        self._xs_buf(dev)
+        clip = self.max_grad_norm is not None
+        d, omd = self._ema_scalars()
+        ops._launch("adam", 0.0, "vf_adam_set_scalars_ex", None, 0.0, 0.0, 0.0, self._xs_ptr(0), d, omd,
+                    self.max_grad_norm or 0.0, raw)
+        if clip:
+            total = sum(w[1]["blocks"] for w in work)
+            if self._partials is None or self._partials.numel() < total or self._partials.device != dev:
+                self._partials = torch.empty(total, dtype=torch.float64, device=dev)
+            off = 0
+            for _, b, f, grads in work:
+                ops._launch("adam", 0.0, "vf_grad_sumsq_multi", ctypes.c_void_p(b["dev"][f].data_ptr()), len(grads), b["blocks"],
+                            ctypes.c_void_p(self._partials.data_ptr() + 8 * off), raw, nbytes=4.0 * b["numel"])
+                off += b["blocks"]
+            ops._launch("adam", 0.0, "vf_grad_norm_finish", ctypes.c_void_p(self._partials.data_ptr()), total,
+                        self._xs_ptr(2), self._xs_ptr(3), raw, nbytes=8.0 * total)
+        for group, b, f, grads in work:           # (work keeps every bucket's gradient tensors alive up to here)
+            b1, b2 = group["betas"]
+            t, n = b["t"], len(grads)
+            ema = b.get("ema_dev")
+            ops._launch("adam", 0.0, "vf_adam_multi_ex", ctypes.c_void_p(b["dev"][f].data_ptr()),
+                        None if ema is None else ctypes.c_void_p(ema.data_ptr()), n, b["blocks"], float(group["lr"]),
+                        float(b1), float(b2), float(group["eps"]), 1.0 - b1 ** t, 1.0 - b2 ** t,
+                        self._xs_ptr(4) if clip else None, None if ema is None else self._xs_ptr(0), raw,
+                        nbytes=(28.0 if ema is None else 36.0) * b["numel"])
+            torch.autograd.graph.increment_version(b["params"])
+        if self.ema_decay is not None:
+            self._ema_t += 1

@@ -7,6 +7,7 @@ dataset, wandb and checkpoint plumbing.  One process per GPU; gradients are aver
 communication buffer, one all-reduce per segment overlaps the rest of the backward pass -- or, with
 VF_REDUCER=ddp, by torch's DistributedDataParallel as in the reference.
 """
+import contextlib
 import math
 import os
 
@@ -139,14 +140,21 @@ class Trainer:
     corrections are read from device memory refreshed before each replay; torch's device RNG advances per replay
     exactly as it does per eager step.  The capture runs the forward on fresh leaf aliases of the parameters and takes
     the gradients with autograd.grad, so autograd state that callers keep alive (a loss with history) cannot pull
-    another stream into it."""
+    another stream into it.
+
+    ema_decay / ema_warmup / max_grad_norm (all off by default: nothing above changes) go to optim.FusedAdam, which
+    keeps an exponential moving average of the weights and clips the gradients by their global norm inside the fused
+    update, in every launch mode (in a multi-rank run the norm is taken after the exchange, on the averaged gradients,
+    so the replicas stay identical).  `grad_norm` is the last step's pre-clip norm as a 0-d device tensor (no sync);
+    `with trainer.ema_weights(): drivers.evaluate(model, ...)` samples from the EMA.  The xgmi reducer applies Adam
+    inside its own all-reduce kernel and has neither: VF_REDUCER=xgmi with either option raises ValueError."""
     GRAPH_AFTER = 2
     GRAPH_MAX = 96
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
     inject_capture_failure = None   # set by tests (class or instance attribute), never read from the environment
 
     def __init__(self, model, world=1, local_rank=0, lr_warmup=2500, decay_it=4000000, bucket_cap_mb=32, graph=None,
-                 seed=None, global_batch=None):
+                 seed=None, global_batch=None, ema_decay=None, ema_warmup=False, max_grad_norm=None):
         self.module = model
         # seed: the training draws come from the counter-based generator (csrc/rng.h) keyed by a global sample index
         # (step_sample_ids), not from torch's device generator; None (default): as before
@@ -155,6 +163,13 @@ class Trainer:
         self.model = model
         self.arena = None
         kind = os.environ.get("VF_REDUCER", "arena")
+        extras = ema_decay is not None or max_grad_norm is not None
+        if extras and kind == "xgmi":
+            raise ValueError("VF_REDUCER=xgmi applies Adam inside its all-reduce kernel, which has neither the weight EMA "
+                             "nor gradient clipping: use the default reducer (or VF_REDUCER=ddp) with ema_decay / "
+                             "max_grad_norm")
+        if extras and not next(model.parameters()).is_cuda:
+            raise ValueError("ema_decay / max_grad_norm are part of the fused HIP Adam step: the model must be on the GPU")
         if world > 1 and kind != "ddp":
             try:
                 # "xgmi": the hand-written one-shot all-reduce over IPC-mapped peer arenas fused with Adam (correctness-
@@ -185,7 +200,8 @@ class Trainer:
         params = self._params = [p for _, p in self._named]
         if params[0].is_cuda:       # one multi-tensor HIP launch per step
             from .optim import FusedAdam
-            self.opt = FusedAdam(params, lr=self.sched.get_cur_lr(0))
+            self.opt = FusedAdam(params, lr=self.sched.get_cur_lr(0), ema_decay=ema_decay, ema_warmup=ema_warmup,
+                                 max_grad_norm=max_grad_norm)
         else:                       # CPU harness tests (gloo) only
             self.opt = torch.optim.Adam(params, lr=self.sched.get_cur_lr(0))
         self.it = -1
@@ -213,6 +229,30 @@ class Trainer:
         if self.arena is None:
             return "graph"
         return "captured" if self.arena.capturable else "split"
+
+    @property
+    def grad_norm(self):
+        """Global L2 norm of the last step's (averaged) gradients before clipping: a 0-d device tensor that every
+        step rewrites, never a sync.  None without max_grad_norm."""
+        return getattr(self.opt, "grad_norm", None)
+
+    def ema_state_dict(self):
+        return self.opt.ema_state_dict()
+
+    def load_ema_state_dict(self, sd):
+        self.opt.load_ema_state_dict(sd)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model holds the EMA weights (and the EMA tensors hold the live ones): one in-place
+        exchange on entry, one on exit, after which the live weights are what they were, bit for bit.  The contents
+        move, not the tensors -- captured graphs and packed weights address parameter memory by raw pointer -- and the
+        parameters' version counters are bumped so the packed-weight caches refresh.  Do not call step() inside."""
+        self.opt.swap_ema()
+        try:
+            yield self.module
+        finally:
+            self.opt.swap_ema()
 
     def dist_info(self):
         """What a multi-rank run looks like from this rank (bench.py prints it)."""
