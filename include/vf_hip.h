@@ -312,6 +312,25 @@ int vf_psnr(const float* generated, const float* target, float* out /*[B]*/, int
 long vf_ssim_workspace_floats(int B, int C, int H, int W);
 int vf_ssim(const float* generated, const float* target, float* out /*[B]*/, float* workspace, int B, int C, int H,
             int W, const float* window11, float data_range, void* stream);
+/* ... and utils/compute_metrics.py (csrc/lpips.hip): what LPIPS (vgg, version 0.1) needs around the 3x3 convolutions of
+ * its VGG16 trunk, which run through vf_conv_fwd / the Winograd entries like any other layer.
+ * vf_lpips_prep: out [2B][3][HW] = ((2 x - 1) - shift_c) / scale_c of [generated | target], each [B][3][HW].
+ * vf_relu: in place.  vf_relu_maxpool2: y [planes][H][W] (H, W even) is ReLU'd in place and pooled [planes][H/2][W/2]
+ * receives its 2x2 maxima, in one read.
+ * vf_lpips_layer: one tap; feat [2B][C][HW] (image b against image B + b), lin [C]; per pixel
+ * sum_c lin_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, one partial sum / HW per workgroup at
+ * workspace[b * slots + slot0 + tile], tile < vf_lpips_layer_tiles(C, HW).  vf_lpips_finish: out[b] = the sum of the
+ * image's `slots` partials in index order (in double).  vf_lpips_workspace_floats: B * the slots of the five VGG16 taps
+ * (64, 128, 256, 512, 512 channels at H x W ... H/16 x W/16); 0 unless H and W are multiples of 16.
+ * No atomics, fixed summation order: bit-reproducible. */
+int vf_lpips_prep(const float* generated, const float* target, float* out, int B, int HW, void* stream);
+int vf_relu(float* x, long n, void* stream);
+int vf_relu_maxpool2(float* y, float* pooled, long planes, int H, int W, void* stream);
+int vf_lpips_layer_tiles(int C, int HW);
+long vf_lpips_workspace_floats(int B, int H, int W);
+int vf_lpips_layer(const float* feat, const float* lin, float* workspace, int B, int C, int HW, int slot0, int slots,
+                   void* stream);
+int vf_lpips_finish(const float* workspace, float* out /*[B]*/, int B, int slots, void* stream);
 
 /* ---- optimizer step next to the path: torch.optim.Adam, experiment.py:118-120,293 ----
  * desc = device int64 [ntensors][6] rows {p, g, exp_avg, exp_avg_sq, numel, first_block}, block = 1024 elems */

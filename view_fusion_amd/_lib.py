@@ -117,6 +117,13 @@ SIGNATURES = {
     "vf_psnr": [_P, _P, _P, _I, _I, _P],
     "vf_ssim_workspace_floats": [_I, _I, _I, _I],
     "vf_ssim": [_P, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P],
+    "vf_lpips_prep": [_P, _P, _P, _I, _I, _P],
+    "vf_relu": [_P, _L, _P],
+    "vf_relu_maxpool2": [_P, _P, _L, _I, _I, _P],
+    "vf_lpips_layer_tiles": [_I, _I],
+    "vf_lpips_workspace_floats": [_I, _I, _I],
+    "vf_lpips_layer": [_P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vf_lpips_finish": [_P, _P, _I, _I, _P],
     "vf_gather_level": [_P, _P, _P, _P, _I, _P],
     "vf_stack_views": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vf_compose_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
@@ -131,7 +138,7 @@ SIGNATURES = {
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],
 }
 _RESTYPE = {"vf_conv1x1_bf16x3_pack_dwords": _L, "vf_conv_wgrad_ws_floats": _L, "vf_time_affine_ws_floats": _L, "vf_wino_conv_ws_floats": _L, "vf_wino44_conv_ws_floats": _L, "vf_wino_wgrad_ws_floats": _L, "vf_conv_fwd_ws_floats": _L,
-            "vf_conv_small_pack_floats": _L, "vf_ssim_workspace_floats": _L}
+            "vf_conv_small_pack_floats": _L, "vf_ssim_workspace_floats": _L, "vf_lpips_workspace_floats": _L}
 
 _lib = None
 N_CALLS = 0          # C-ABI launcher invocations so far (bench.py: launches per sampler step)

@@ -7,10 +7,12 @@ MI355X engine (no dataset / wandb / image-grid plumbing):
   * checkpoint wire format ................................. utils/checkpoint.py:31-72
   * eval reduction: PSNR, SSIM + all_reduce(AVG) + barriers  utils/metrics.py:6-12, utils/dist.py:69-91,
     experiment.py:314-370 (SSIM is the metric the reference selects best_model_ssim.pt by, :375-380)
+  * LPIPS (vgg), the third number of the paper's tables ..... utils/compute_metrics.py (the user brings the weights)
 """
 import contextlib
 import math
 import os
+import re
 
 import torch
 import torch.distributed as dist
@@ -134,6 +136,84 @@ def compute_ssim(generated, target):
     return ops.ssim(generated, target, data_range=1.0)
 
 
+# torchvision's index of the 13 convolutions inside vgg16().features, and their widths
+_VGG_CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)
+_VGG_KEY = re.compile(r"^(?:net\.slice\d+\.|features\.)?(\d+)\.(weight|bias)$")
+
+
+class LPIPS(torch.nn.Module):
+    """lpips.LPIPS(net="vgg") (version 0.1) for eval: the VGG16 trunk as 13 frozen nn.Conv2d holders (`features.N`, N =
+    torchvision's index) and the five bias-free 1x1 "lin" layers as (1,C,1,1) parameters `lin0` ... `lin4`.  No weights
+    ship with the package: build it from the two state dicts the user already has, move it to the
+    device, and call it -- or hand it to evaluate(lpips=...) -- with images in [0, 1]."""
+
+    def __init__(self):
+        super().__init__()
+        from .ops import LPIPS_TAPS, LPIPS_WIDTHS
+        convs, cin = {}, 3
+        for idx, cout in zip(_VGG_CONVS, LPIPS_WIDTHS):
+            convs[str(idx)] = torch.nn.Conv2d(cin, cout, 3, padding=1)
+            cin = cout
+        self.features = torch.nn.ModuleDict(convs)
+        for l, i in enumerate(LPIPS_TAPS):
+            self.register_parameter(f"lin{l}", torch.nn.Parameter(torch.zeros(1, LPIPS_WIDTHS[i], 1, 1)))
+        self.requires_grad_(False)
+
+    @property
+    def convs(self):
+        return [self.features[str(i)] for i in _VGG_CONVS]
+
+    @property
+    def lins(self):
+        return [getattr(self, f"lin{l}") for l in range(5)]
+
+    @classmethod
+    def from_state_dicts(cls, vgg_sd, lin_sd):
+        """vgg_sd: torchvision vgg16 keys `features.N.{weight,bias}` (also `N.…` or the package's `net.sliceK.N.…`);
+        lin_sd: the package's `lin{0..4}.model.1.weight` of shape (1,C,1,1).  Every shape is checked; the first missing
+        or mis-shaped key is named."""
+        net = cls()
+        found = {}
+        for k, v in vgg_sd.items():
+            m = _VGG_KEY.match(k)
+            if m and int(m.group(1)) in _VGG_CONVS:
+                found[f"features.{m.group(1)}.{m.group(2)}"] = (k, v)
+        own = {}
+        for name, p in net.named_parameters():
+            if name.startswith("features."):
+                src = found.get(name)
+                shown = src[0] if src is not None else name
+                val = src[1] if src is not None else None
+            else:
+                shown = f"{name}.model.1.weight"
+                val = lin_sd.get(shown)
+            if val is None:
+                raise KeyError(f"LPIPS: missing key {shown!r}")
+            if not torch.is_tensor(val) or tuple(val.shape) != tuple(p.shape):
+                raise ValueError(f"LPIPS: key {shown!r} has shape {tuple(getattr(val, 'shape', ()))}, expected "
+                                 f"{tuple(p.shape)}")
+            own[name] = val.detach().to(torch.float32)
+        net.load_state_dict(own)
+        return net
+
+    @classmethod
+    def from_files(cls, vgg_path, lin_path):
+        return cls.from_state_dicts(torch.load(vgg_path, map_location="cpu", weights_only=True),
+                                    torch.load(lin_path, map_location="cpu", weights_only=True))
+
+    @torch.no_grad()
+    def forward(self, generated, target):
+        from . import ops
+        return ops.lpips(generated, target, self)
+
+
+def compute_lpips(generated, target, net):
+    """lpips.LPIPS(net="vgg")(2 * generated - 1, 2 * target - 1) per image pair, (B,): `net` is an LPIPS module on the
+    images' device.  The trunk runs on the engine's conv kernels, the rest in csrc/lpips.hip."""
+    from . import ops
+    return ops.lpips(generated, target, net)
+
+
 def reduce_dict(d, average=True):
     """all_reduce every tensor of `d` across ranks (AVG by default), keys in sorted order as the reference
     (utils/dist.py:69-91); identity without a process group.  RCCL has ncclAvg; gloo only SUM, so there the mean is
@@ -160,13 +240,15 @@ def _barrier():
 
 
 @torch.no_grad()
-def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, seed=None, **inject):
+def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, seed=None, lpips=None,
+             **inject):
     """The eval reduction of Experiment.eval (experiment.py:314-370): every rank generates its shard of the validation
     batches (view_count ~ U[1, max_views] per sample), PSNR per image on the GPU (utils/metrics.py:6-8), mean over the
     rank's images, barrier, all_reduce(AVG) of the scalars, barrier.  `batches`: iterable of dicts with target (B,3,H,W),
     cond (B,>=max_views,3,H,W), angle (B,1) and optionally view_count.  ssim=True adds the reference's second metric
     (utils/metrics.py:11-12, images of at least 11 x 11) under "ssim", through the same reduction; the default reports
-    PSNR alone.  extra_metrics: {name: fn(generated, target) -> (B,)} for anything else (merged on top).  Returns the
+    PSNR alone.  lpips=<an LPIPS module on the device> adds "lpips" (images a multiple of 16 and at least 32 a side) the
+    same way.  extra_metrics: {name: fn(generated, target) -> (B,)} for anything else (merged on top).  Returns the
     reduced dict of 0-d tensors.
     seed (default None: torch's device generator, as before): the sampler's noise comes from the counter-based generator
     keyed by batch["ids"] (B,) -- dataset indices -- so an image's sample, and with it the metrics, do not depend on how
@@ -193,6 +275,8 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ss
     metrics = {"psnr": compute_psnr}
     if ssim:
         metrics["ssim"] = compute_ssim                 # module global, looked up now: a host stand-in can be patched in
+    if lpips is not None:
+        metrics["lpips"] = lambda a, t: compute_lpips(a, t, lpips)     # (a module global too, looked up at call time)
     metrics.update(extra_metrics or {})
     out = {k: torch.cat([fn(a, t) for a, t in zip(gen, gt)]).mean() for k, fn in metrics.items()}
     _barrier()

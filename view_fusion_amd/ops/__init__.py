@@ -5,7 +5,7 @@
     core       pointers / streams / C-ABI call wrappers / kernel log
     deferred   gradient destinations, deferred GroupNorm column sums and weight-gradient slab sums, capture tables
     packing    packed-weight caches, `pack_all`
-    norm, conv, dense, attention, diffusion    the ops themselves
+    norm, conv, dense, attention, diffusion, lpips    the ops themselves
     bf16x3     experiment (default off)
 
 There is no CPU / eager fallback: CPU tensors raise VFHipError."""
@@ -49,4 +49,7 @@ from .attention import (  # noqa: F401
 from .diffusion import (  # noqa: F401
     _ComposeLossFn, compose, compose_mse_loss, draw_train, gather_level, p_sample_tail, philox_ids, psnr, randn_ids,
     sample_ids, ssim, stack_views, view_offsets
+)
+from .lpips import (  # noqa: F401
+    LPIPS_TAPS, LPIPS_WIDTHS, lpips
 )
