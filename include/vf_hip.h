@@ -296,6 +296,22 @@ int vf_p_sample_tail_rng(const float* unet_out, const int* off, const float* y_t
                          const float* posterior_mean_coef1, const float* posterior_mean_coef2,
                          float* y_next /*|NULL*/, float* mean_out /*|NULL*/, float* weights /*|NULL*/, int B, int Cout,
                          int HW, int maxV, int weighting, int clip, void* stream);
+/* ---- few-step samplers (strided DDIM, DPM-Solver++ 2M): the reverse-step tail with a table-driven update.
+ *      k = kidx[b] (DEVICE int64 [B]) indexes the K-entry fp32 DEVICE tables of schedule.sampler_tables:
+ *        y0 = clamp(a[k] y - b[k] eps, -1, 1);  y_next = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z;
+ *        y0_prev <- y0 (when given).
+ *      sigma[k] == 0: z is neither loaded nor drawn; c1[k] == 0: y0_prev is not read.  y_next may be y_t. ---- */
+int vf_sampler_step(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,
+                    const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                    const float* c1, const float* sigma, float* y0_prev /*[B][3][HW]|NULL*/, float* y_next,
+                    float* weights /*|NULL*/, int B, int Cout, int HW, int maxV, int weighting, void* stream);
+/* ... with z drawn in the kernel from (seed, ids[b], kind 3, tau[k], float4 index): tau (DEVICE int64 [K]) holds the
+ * model timestep of every entry, so the draw at one noise level is the same for every K. */
+int vf_sampler_step_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                        const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                        const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                        float* y0_prev /*|NULL*/, float* y_next, float* weights /*|NULL*/, int B, int Cout, int HW,
+                        int maxV, int weighting, void* stream);
 /* Host mirrors: the same inline functions run on the CPU.  HOST pointers, no stream, no GPU needed. */
 int vf_rng_host_philox(const unsigned* counter /*[4]*/, const unsigned* key /*[2]*/, unsigned* out /*[4]*/);
 int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, int step, float* out /*[B][n]*/,

@@ -133,6 +133,8 @@ SIGNATURES = {
     "vf_randn_ids": [_U64, _P, _I, _I, _P, _I, _I, _P],
     "vf_philox_ids": [_U64, _P, _I, _I, _P, _I, _I, _P],
     "vf_p_sample_tail_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vf_sampler_step": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vf_sampler_step_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

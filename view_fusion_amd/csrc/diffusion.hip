@@ -8,6 +8,9 @@
 //
 // Seeded draws (rng.h: Philox4x32-10 keyed by seed and a per-sample id): draw_train, randn_ids and the reverse-step
 // tail that computes its own z.  Opt-in; the unseeded kernels and entry points are untouched.
+//
+// Few-step sampling: sampler_step(_rng)_kernel is the same tail with a table-driven linear-multistep update
+// (strided DDIM / DPM-Solver++ 2M) instead of the one-step DDPM posterior; the p_sample_tail kernels stay as they are.
 #include "common.h"
 #include "rng.h"
 
@@ -278,6 +281,98 @@ __global__ __launch_bounds__(256) void p_sample_tail_rng_kernel(
                        });
 }
 
+// One linear-multistep reverse step after the UNet (strided DDIM, DPM-Solver++ 2M; schedule.sampler_tables):
+//   y0 = clamp(a[k] y - b[k] eps, -1, 1);  y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z;  y0_prev <- y0
+// with k = kidx[b] read from device memory.  sigma[k] == 0: `noise` is never called (no load, no draw);
+// c1[k] == 0 or no history buffer: y0_prev is not read (it may hold anything before the first multistep step).
+// Elementwise: y_next may be y, and y0_prev is read and written by the same thread.
+template <class Noise>
+__device__ __forceinline__ void sampler_step_body(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    const long long* __restrict__ kidx, const float* __restrict__ ta, const float* __restrict__ tb,
+    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
+    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
+    int Cout, int HW, int maxV, int weighting, Noise noise) {
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const long long k = kidx[b];
+    const float a_k = ta[k], b_k = tb[k], cy = tcy[k], c0 = tc0[k], c1 = tc1[k], sg = tsigma[k];
+    const bool hist = y0_prev != nullptr && c1 != 0.0f, noisy = sg != 0.0f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        float4 mx, inv;
+        const float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        const float4 y = *reinterpret_cast<const float4*>(y_t + o);
+        const float ys[4] = {y.x, y.y, y.z, y.w};
+        const float es[4] = {eps.x, eps.y, eps.z, eps.w};
+        float y0[4], r[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            y0[j] = fminf(fmaxf(a_k * ys[j] - b_k * es[j], -1.0f), 1.0f);
+            r[j] = cy * ys[j] + c0 * y0[j];
+        }
+        if (hist) {
+            const float4 h = *reinterpret_cast<const float4*>(y0_prev + o);
+            r[0] += c1 * h.x; r[1] += c1 * h.y; r[2] += c1 * h.z; r[3] += c1 * h.w;
+        }
+        if (noisy) {
+            const float4 z = noise(i, o);
+            r[0] += sg * z.x; r[1] += sg * z.y; r[2] += sg * z.z; r[3] += sg * z.w;
+        }
+        if (y0_prev) *reinterpret_cast<float4*>(y0_prev + o) = make_float4(y0[0], y0[1], y0[2], y0[3]);
+        *reinterpret_cast<float4*>(y_next + o) = make_float4(r[0], r[1], r[2], r[3]);
+        if (weights && weighting) {
+            const size_t vs = (size_t)Cout * HW;
+            for (int j = 0; j < maxV; ++j) {
+                float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (v0 + j < v1) {
+                    const float4 l = *reinterpret_cast<const float4*>(out + (size_t)(v0 + j) * vs +
+                                                                     (size_t)(3 + c) * HW + p);
+                    w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
+                                    expf(l.w - mx.w) * inv.w);
+                }
+                *reinterpret_cast<float4*>(weights + (((size_t)b * maxV + j) * 3) * HW + 4 * (size_t)i) = w;
+            }
+        }
+    }
+}
+
+// z loaded from a buffer; z == null is "no noise" whatever sigma says
+__global__ __launch_bounds__(256) void sampler_step_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    const float* __restrict__ z, const long long* __restrict__ kidx, const float* __restrict__ ta,
+    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
+    const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next,
+    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting) {
+    sampler_step_body(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW, maxV,
+                      weighting, [z](int, size_t o) {
+                          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+                          if (z) zz = *reinterpret_cast<const float4*>(z + o);
+                          return zz;
+                      });
+}
+
+// z drawn in the kernel, keyed as in p_sample_tail_rng_kernel with the MODEL timestep tau[k] as the step, so a
+// strided chain and the full chain draw the same z at the same noise level.
+__global__ __launch_bounds__(256) void sampler_step_rng_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
+    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
+    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
+    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
+    int Cout, int HW, int maxV, int weighting) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
+    sampler_step_body(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW, maxV,
+                      weighting, [seed, id, step](int i, size_t) {
+                          float n[4];
+                          vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
+                          return make_float4(n[0], n[1], n[2], n[3]);
+                      });
+}
+
 // Training draws of sample b (kind 0): t[b] in [1, T-1] as int64, u[b] in [0, 1) (optional output) and
 // level[b] = (g[t] - g[t-1]) u + g[t-1]  (view_fusion.py:229-237).
 __global__ void draw_train_kernel(unsigned long long seed, const long long* __restrict__ ids,
@@ -469,6 +564,32 @@ int vf_p_sample_tail_rng(const float* unet_out, const int* off, const float* y_t
                        unet_out, off, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
                        posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV, weighting,
                        clip);
+    VF_RETURN_LAST_ERROR();
+}
+
+// ---- few-step samplers: one linear-multistep tail (tables: schedule.sampler_tables) ----
+int vf_sampler_step(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* kidx,
+                    const float* a, const float* b, const float* cy, const float* c0, const float* c1,
+                    const float* sigma, float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW,
+                    int maxV, int weighting, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !y_next) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sampler_step_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       unet_out, off, y_t, z, kidx, a, b, cy, c0, c1, sigma, y0_prev, y_next, weights, Cout, HW, maxV,
+                       weighting);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_sampler_step_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                        const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                        const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                        float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW, int maxV,
+                        int weighting, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !y_next) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sampler_step_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       unet_out, off, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev, y_next, weights,
+                       Cout, HW, maxV, weighting);
     VF_RETURN_LAST_ERROR();
 }
 

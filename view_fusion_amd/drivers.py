@@ -37,12 +37,15 @@ def _eval_mode(model):
 # Each driver reaches the sampler through model(..., generate=True), like the reference's (DDP wraps forward), and
 # takes the optional injected randomness of ViewFusion.forward (y_t = the start noise, z_seq[i] = the noise of
 # reverse step i) so that its output can be compared with the CPU oracle.  seed= (and sample_ids=) reach generate() the
-# same way: the draws then come from the counter-based generator of csrc/rng.h, keyed per sample.
+# same way: the draws then come from the counter-based generator of csrc/rng.h, keyed per sample.  So do sample_steps= /
+# solver= / eta= (few-step sampling: K steps over a sub-sequence of the trained schedule instead of all T).
 @torch.no_grad()
 def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None, **inject):
     """Generate with MORE views than the model was trained on (view_count ~ U[max_views+1, 24)),
     experiment.py:472-488.
-    cond (B,23,3,H,W), angle (B,1) -> (generated_batch (B,1+k,3,H,W), logit_arr, weight_arr, view_count)."""
+    cond (B,23,3,H,W), angle (B,1) -> (generated_batch (B,1+k,3,H,W), logit_arr, weight_arr, view_count).
+    **inject reaches generate(): y_t, z_seq, seed, sample_ids, use_graph, and sample_steps / solver / eta for a
+    few-step chain (ViewFusion.generate)."""
     B = cond.shape[0]
     if view_count is None:
         view_count = torch.randint(max_views + 1, 24, (B,), generator=generator)
@@ -53,12 +56,14 @@ def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None
 
 
 @torch.no_grad()
-def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, seed=None, sample_ids=None):
+def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, seed=None, sample_ids=None,
+                           sample_steps=None, solver="ddim", eta=0.0):
     """Start from ONE view and synthesise the orbit view by view, feeding every sample back as an
     extra conditioning view (count = 1 .. steps; angle = 2*pi/24 * count), experiment.py:516-544.
     first_view (B,3,H,W) -> samples (B,steps,3,H,W).  y_t / z_seq: per-count lists of injected randomness.
     seed: the draws of rollout step `count` of object b use the id sample_ids[b] * steps + count - 1 (sample_ids
-    defaults to arange(B)), so every step of every object has noise of its own, independent of the batch."""
+    defaults to arange(B)), so every step of every object has noise of its own, independent of the batch.
+    sample_steps / solver / eta: the few-step sampler of every generate() call (`steps` is the rollout length)."""
     cond = first_view[:, None].contiguous()
     B = cond.shape[0]
     out = []
@@ -73,6 +78,8 @@ def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, se
                           z_seq=None if z_seq is None else z_seq[count - 1])
             if seed is not None:
                 inject.update(seed=seed, sample_ids=base + (count - 1))
+            if sample_steps is not None:
+                inject.update(sample_steps=sample_steps, solver=solver, eta=eta)
             *_, sample = model(y_cond=cond, view_count=view_count, angle=angle, generate=True, **inject)
             cond = torch.cat((cond, sample[:, None]), dim=1)
             out.append(sample)
@@ -85,7 +92,8 @@ def orbit_frames(model, all_views, n=24, **inject):
     of the n target angles 2*pi/n*i is generated from the same 6 conditioning views (every 4th view), i.e. one
     generate() call at B = n, N = 6.
     -> (generated_batch (n,1+k,3,H,W) clamped to [0,1], logit_arr, weight_arr, cond_views (n,6,3,H,W), angles (n,1));
-    the frame i of the animation shows weight_arr[i] next to cond_views[i] and generated_batch[i]."""
+    the frame i of the animation shows weight_arr[i] next to cond_views[i] and generated_batch[i].
+    **inject reaches generate() (sample_steps / solver / eta among it: 24 frames in K instead of T steps)."""
     assert all_views.shape[0] == 24 and n % 24 == 0
     dev = all_views.device
     angles = torch.tensor([2 * math.pi / n * i for i in range(n)], dtype=torch.float32, device=dev).unsqueeze(1)
@@ -253,7 +261,9 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ss
     seed (default None: torch's device generator, as before): the sampler's noise comes from the counter-based generator
     keyed by batch["ids"] (B,) -- dataset indices -- so an image's sample, and with it the metrics, do not depend on how
     the validation set is batched or sharded over ranks.  Without "ids" a running index over this rank's images is
-    used: independent of the batch size, but NOT of the sharding."""
+    used: independent of the batch size, but NOT of the sharding.
+    sample_steps / solver / eta (through **inject): evaluate with a K-step sampler (ViewFusion.generate); which K is
+    good enough for a checkpoint is what this function measures."""
     gen, gt = [], []
     seen = 0
     with _eval_mode(model):                        # Experiment.eval: self.model.eval() (experiment.py:316)

@@ -219,6 +219,40 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
     return y_next, mean, wts
 
 
+def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_prev=None, want_weights=True,
+                 inplace=False, seed=None, ids=None):
+    """One step of a few-step sampler (strided DDIM / DPM-Solver++ 2M), fused like p_sample_tail:
+    compose -> y0 = clamp(a[k] y - b[k] eps) -> y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z, k = kidx[b].
+    tables: the fp32 device tables a, b, cy, c0, c1, sigma (K,) and tau (K,) int64 (ViewFusion._sampler_plan).
+    y0_prev (like y, optional): the multistep history, updated in place; it is not read where c1[k] == 0.
+    Returns (y_next, weights | None).  seed= (with z=None): z is drawn inside the kernel from
+    (seed, ids[b], tau[k], element); where sigma[k] == 0 no z is loaded or drawn at all."""
+    _check(unet_out, y, z, y0_prev, *(tables[n] for n in ("a", "b", "cy", "c0", "c1", "sigma")))
+    if seed is not None and z is not None:
+        raise ValueError("sampler_step takes either z or seed=, not both")
+    S, Cout, H, W = unet_out.shape
+    kidx = _c(kidx.to(torch.int64))
+    y_next = y if inplace else torch.empty_like(y)         # elementwise: safe to overwrite y
+    wts = None
+    if weighting and want_weights:
+        wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)
+    tabs = [_ptr(tables[n]) for n in ("a", "b", "cy", "c0", "c1", "sigma")]
+    tail = (_ptr(y0_prev), _ptr(y_next), _ptr(wts), B, Cout, H * W, max_views, int(weighting), _stream())
+    if seed is not None:
+        ids = sample_ids(y.device, B, ids)
+        _check_ids(ids, B)
+        tau = tables["tau"]
+        if not tau.is_cuda or tau.dtype != torch.int64 or not tau.is_contiguous():
+            raise _lib.VFHipError("tables['tau'] must be a contiguous device int64 tensor")
+        _call("vf_sampler_step_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _seed(seed),
+              ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(kidx.data_ptr()), ctypes.c_void_p(tau.data_ptr()),
+              *tabs, *tail)
+        return y_next, wts
+    _call("vf_sampler_step", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _ptr(z),
+          ctypes.c_void_p(kidx.data_ptr()), *tabs, *tail)
+    return y_next, wts
+
+
 def psnr(generated, target):
     """Per-image PSNR (B,) of (B,C,H,W) tensors in [0,1]."""
     generated, target = _c(generated), _c(target)

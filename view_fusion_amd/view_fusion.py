@@ -38,6 +38,8 @@ class ViewFusion(nn.Module):
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
         betas = _schedule.make_beta_schedule(**self.beta_schedule[phase])
         self.num_timesteps = int(betas.shape[0])
+        self.betas64 = betas                   # float64, for the few-step sampler tables; not a buffer (state_dict)
+        self._plan = None
         for name, val in _schedule.schedule_tensors(betas, device).items():
             if name in self._buffers:
                 self._buffers[name] = val
@@ -46,6 +48,22 @@ class ViewFusion(nn.Module):
 
     def _sched(self):
         return {k: getattr(self, k) for k in _schedule.BUFFER_NAMES}
+
+    def _sampler_plan(self, tau, solver, eta, device):
+        """The device side of a few-step chain: the fp32 tables of schedule.sampler_tables, `tau` as int64 and
+        `level` = the fp32 `gammas` buffer gathered at tau (the network sees the very levels of the full chain).
+        `noisy[k]`: sigma[k] != 0, on the host.  The last plan is kept (evaluate() asks for the same one per batch)."""
+        key = (tuple(int(v) for v in tau), solver, float(eta), device)
+        if self._plan is None or self._plan[0] != key:
+            tab = _schedule.sampler_tables(self.betas64, tau, solver, eta)
+            host = {k: torch.tensor(v, dtype=torch.float32) for k, v in tab.items()}
+            plan = {k: v.to(device) for k, v in host.items()}
+            plan["tau"] = torch.tensor(tau, dtype=torch.int64, device=device)
+            plan["level"] = self.gammas[plan["tau"]].contiguous()
+            plan["noisy"] = (host["sigma"] != 0).tolist()
+            plan["multistep"] = bool((host["c1"] != 0).any())
+            self._plan = (key, plan)
+        return self._plan[1]
 
     @staticmethod
     def _at(table, t, ndim=4):
@@ -65,9 +83,9 @@ class ViewFusion(nn.Module):
         return sample_gammas.sqrt() * y_0 + (1 - sample_gammas).sqrt() * noise
 
     # -- reverse process ---------------------------------------------------------------------
-    def _denoise(self, y_t, y_cond, angle, t, off, S, x=None, copy_cond=True):
+    def _denoise(self, y_t, y_cond, angle, t, off, S, x=None, copy_cond=True, levels=None):
         from . import ops
-        level = ops.gather_level(self.gammas, t)
+        level = ops.gather_level(self.gammas if levels is None else levels, t)
         x, level_s, angle_s = ops.stack_views(y_cond, y_t, None, level, angle, off, S, x=x, copy_cond=copy_cond)
         return x, self.denoise_fn(x, angle_s, level_s)
 
@@ -97,7 +115,7 @@ class ViewFusion(nn.Module):
 
     @torch.no_grad()
     def generate(self, y_cond, view_count, angle, y_t=None, sample_num=8, z_seq=None, use_graph=None, seed=None,
-                 sample_ids=None):
+                 sample_ids=None, sample_steps=None, solver="ddim", eta=0.0):
         """Reverse diffusion over all T steps (reference view_fusion.py:179-214).
 
         use_graph (default: on for GPU tensors with S <= 16 stacked views): one reverse step -- level gather, re-stack of
@@ -108,11 +126,22 @@ class ViewFusion(nn.Module):
         seed (default None: torch's device generator): y_T and every step's z come from the counter-based generator
         (csrc/rng.h), keyed by `sample_ids` (default arange(B)); z is computed inside the tail kernel, so the host
         only refreshes the step index.  An injected y_t / z_seq still wins, each on its own.
+
+        sample_steps (default None: the ancestral chain above, untouched): K, or an explicit increasing sequence of
+        timesteps ending at T-1 -- a K-step chain over the sub-sequence schedule.sample_timesteps(T, K) of the trained
+        levels with solver "ddim" (eta in [0, 1]; 0 deterministic, 1 ancestral) or "dpmpp2m" (DPM-Solver++ 2M, eta 0).
+        The loop is the same one, with the table-driven tail (ops.sampler_step) and the step index k in place of t;
+        z_seq stays (T, ...) and is read at the model timestep, z_seq[tau[k]]; snapshots where k % (K // sample_num) == 0.
         """
         from . import ops
+        plan = tau = None
+        if sample_steps is not None:                      # argument errors first: nothing has been launched yet
+            _schedule.check_sampler(solver, eta)
+            tau = _schedule.sample_timesteps(self.num_timesteps, sample_steps).tolist()
         b = y_cond.shape[0]
         assert self.num_timesteps > sample_num, "num_timesteps must greater than sample_num"
-        every = self.num_timesteps // sample_num
+        n_steps = self.num_timesteps if tau is None else len(tau)
+        every = max(1, n_steps // sample_num)
         ids = None if seed is None else ops.sample_ids(y_cond.device, b, sample_ids)
         if y_t is None and seed is not None:
             y_t = ops.randn_ids(seed, ids, ops.diffusion.RNG_START_NOISE, 0, (3,) + tuple(y_cond.shape[-2:]))
@@ -125,16 +154,27 @@ class ViewFusion(nn.Module):
         sched = self._sched()
         if use_graph is None:                             # measured: replay wins while the step is launch-bound
             use_graph = y.is_cuda and S <= 16   # (at S = 12 replay and eager tie, but replay is immune to host jitter)
-        t = torch.full((b,), self.num_timesteps - 1, device=dev, dtype=torch.long)
+        t = torch.full((b,), n_steps - 1, device=dev, dtype=torch.long)     # the step index: t, or k of a few-step chain
         z_seed = seed if z_seq is None else None          # the tail draws z itself: no noise buffer
         z = None if z_seed is not None else torch.zeros_like(y)
+        levels, hist = self.gammas, None
+        if tau is not None:
+            plan = self._sampler_plan(tau, solver, eta, dev)
+            levels = plan["level"]
+            hist = torch.empty_like(y) if plan["multistep"] else None      # y0 of the step before; never read first
+            if not any(plan["noisy"]):                    # eta = 0: no z anywhere -- no buffer, no draw
+                z_seed = z = None
         y_cond = y_cond.contiguous()
         angle = angle.contiguous()
         # the conditioning half of the stacked input never changes: copy it once
-        x, _, _ = ops.stack_views(y_cond, y, None, ops.gather_level(self.gammas, t), angle, off, S)
+        x, _, _ = ops.stack_views(y_cond, y, None, ops.gather_level(levels, t), angle, off, S)
 
         def step():
-            _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False)
+            _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False, levels=levels)
+            if plan is not None:
+                _, weights = ops.sampler_step(out, off, y, z, t, plan, b, max_v, w_on, y0_prev=hist, inplace=True,
+                                              seed=z_seed, ids=ids)
+                return out, weights
             _, _, weights = ops.p_sample_tail(out, off, y, z, t, sched, b, max_v, w_on, inplace=True, seed=z_seed,
                                               ids=ids)
             return out, weights
@@ -154,14 +194,14 @@ class ViewFusion(nn.Module):
             y.copy_(y0)                                    # capture does not execute, but be explicit
 
         ret, logit_arr, weight_arr = [y_t], [], []
-        for i in reversed(range(self.num_timesteps)):
+        for i in reversed(range(n_steps)):
             t.fill_(i)
             if z is None:                                  # seeded: the tail kernel draws z (0 at step 0) itself
                 pass
-            elif i == 0:
+            elif (i == 0) if plan is None else (not plan["noisy"][i]):
                 z.zero_()
             elif z_seq is not None:
-                z.copy_(z_seq[i])
+                z.copy_(z_seq[i if tau is None else tau[i]])          # z_seq is indexed by the model timestep
             else:
                 z.normal_()
             if graph is not None:
@@ -183,10 +223,10 @@ class ViewFusion(nn.Module):
 
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
-                z_seq=None, use_graph=None, seed=None, sample_ids=None):
+                z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
             return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
-                                 sample_ids=sample_ids)
+                                 sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta)
         from . import ops
         b = y_0.shape[0]
         dev = y_0.device
