@@ -381,6 +381,13 @@ int vf_adam_set_scalars_ex(float* scalars, float lr, float bc1, float bc2, float
 /* exchange p <-> ema in place for every row (desc: only p, numel, first_block are read) */
 int vf_swap_multi(const void* desc, const void* ema_tab, int ntensors, long total_blocks, void* stream);
 
+/* ---- opt-in gradient accumulation over micro-batches (optim.FusedAdam.accumulate, train.Trainer(accum_steps=)) ----
+ * acc = beta * acc + w * g per element: both products and the sum rounded to float, no fma (csrc/adam_update.h).  desc rows
+ * as vf_adam_multi with p = the accumulator, g = the gradient to add (exp_avg / exp_avg_sq unused); scalars: DEVICE
+ * float[2] {beta, w} read when the kernel runs (vf_adam_set_scalars writes them), so a captured launch serves every
+ * micro-batch; beta == 0 never reads the accumulator (it may hold NaN).  No atomics: bit-reproducible */
+int vf_grad_accum_multi(const void* desc, int ntensors, long total_blocks, const float* scalars, void* stream);
+
 /* ---- gradient exchange next to the path: replaces DistributedDataParallel's bucketed NCCL
  *      all-reduce + optimizer.step(), experiment.py:104-107, 118-120, 292-293 -- a one-shot all-reduce over IPC-mapped
  *      peer gradient arenas fused with the Adam update (csrc/xgmi.hip; host side reducer.XgmiArena, VF_REDUCER=xgmi).

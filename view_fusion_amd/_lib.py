@@ -106,6 +106,7 @@ SIGNATURES = {
     "vf_adam_multi_ex_dev": [_P, _P, _I, _L, _P, _F, _F, _F, _P, _P, _P],
     "vf_adam_set_scalars_ex": [_P, _F, _F, _F, _P, _F, _F, _F, _P],
     "vf_swap_multi": [_P, _P, _I, _L, _P],
+    "vf_grad_accum_multi": [_P, _I, _L, _P, _P],
     "vf_xgmi_alloc": [ctypes.POINTER(_P), _L],
     "vf_xgmi_free": [_P],
     "vf_xgmi_export": [_P, _P],

@@ -181,6 +181,42 @@ __global__ __launch_bounds__(256) void swap_multi_kernel(const AdamDesc* __restr
     }
 }
 
+// Gradient accumulation: acc = beta acc + w g for every row (row.p = the accumulator, row.g = this micro-batch's gradient;
+// m, v unused), scal = DEVICE {beta, w}: one captured launch serves every micro-batch position.  beta == 0 (the first
+// micro-batch; uniform over the launch) never READS the accumulator, which may hold NaN or a stale step's sum.
+// Elementwise, no atomics: bit-reproducible.  12 B per parameter (8 on the first micro-batch).
+__global__ __launch_bounds__(256) void grad_accum_multi_kernel(const AdamDesc* __restrict__ desc, int ntensors,
+                                                               const float* __restrict__ scal) {
+    const float beta = scal[0], w = scal[1];
+    int lo = 0, hi = ntensors;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (desc[mid].first_block <= (long long)blockIdx.x) lo = mid; else hi = mid;
+    }
+    const AdamDesc d = desc[lo];
+    const long long base = ((long long)blockIdx.x - d.first_block) * ADAM_PER_BLOCK + 4 * threadIdx.x;
+    if (base >= d.numel) return;
+    if (beta == 0.0f) {
+        if (base + 4 <= d.numel) {
+            const float4 g = *reinterpret_cast<const float4*>(d.g + base);
+            *reinterpret_cast<float4*>(d.p + base) = make_float4(vf_grad_accum_first(g.x, w), vf_grad_accum_first(g.y, w),
+                                                                 vf_grad_accum_first(g.z, w), vf_grad_accum_first(g.w, w));
+        } else {
+            for (long long i = base; i < d.numel; ++i) d.p[i] = vf_grad_accum_first(d.g[i], w);
+        }
+        return;
+    }
+    if (base + 4 <= d.numel) {
+        const float4 g = *reinterpret_cast<const float4*>(d.g + base);
+        float4 a = *reinterpret_cast<float4*>(d.p + base);
+        a.x = vf_grad_accum(a.x, g.x, beta, w); a.y = vf_grad_accum(a.y, g.y, beta, w);
+        a.z = vf_grad_accum(a.z, g.z, beta, w); a.w = vf_grad_accum(a.w, g.w, beta, w);
+        *reinterpret_cast<float4*>(d.p + base) = a;
+    } else {
+        for (long long i = base; i < d.numel; ++i) d.p[i] = vf_grad_accum(d.p[i], d.g[i], beta, w);
+    }
+}
+
 __global__ void adam_set_scalars_ex_kernel(float* dst, float a, float b, float c, float* xs, float d, float omd,
                                            float max_norm) {
     if (dst) { dst[0] = a; dst[1] = b; dst[2] = c; }
@@ -282,6 +318,18 @@ int vf_swap_multi(const void* desc, const void* ema_tab, int ntensors, long tota
     if (!ema_tab) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(swap_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
                        (const AdamDesc*)desc, (float* const*)ema_tab, ntensors);
+    VF_RETURN_LAST_ERROR();
+}
+
+// ---- opt-in gradient accumulation (optim.FusedAdam.accumulate, train.Trainer(accum_steps=)) ----
+// acc = scalars[0] * acc + scalars[1] * g per element (csrc/adam_update.h states the rounding); desc rows as vf_adam_multi
+// with p = the accumulator and g = the gradient to add (m, v unused); scalars: DEVICE float[2] {beta, w}, written with
+// vf_adam_set_scalars; beta == 0 does not read the accumulator
+int vf_grad_accum_multi(const void* desc, int ntensors, long total_blocks, const float* scalars, void* stream) {
+    if (ntensors <= 0 || total_blocks <= 0) return 0;
+    if (!scalars) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(grad_accum_multi_kernel, dim3((unsigned)total_blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const AdamDesc*)desc, ntensors, scalars);
     VF_RETURN_LAST_ERROR();
 }
 

@@ -24,3 +24,21 @@ __device__ __forceinline__ void vf_ema_update(float& ema, float p_new, float d, 
 #pragma clang fp contract(off)
     ema = __builtin_fmaf(d, ema, omd * p_new);
 }
+
+// Gradient accumulation over micro-batches (optim.FusedAdam.accumulate), ONE element:  acc = beta acc + w g  with three
+// roundings -- the two products, then their sum: __fadd_rn(__fmul_rn(beta, acc), __fmul_rn(w, g)) -- and no contraction
+// into an fma, so that numpy float32 restates it bit for bit (tests/accum_ref.py).  Written with plain operators under
+// contract(off), as the update above: hipcc's __fmul_rn / __fadd_rn are inline `x * y` / `x + y` that carry their header's
+// contraction mode into the caller (the float4 path came out as v_pk_fma_f32 with them).  beta is 0 or 1 in practice
+// (1 * acc is exact); the beta == 0 case is the caller's branch.
+__device__ __forceinline__ float vf_grad_accum(float acc, float g, float beta, float w) {
+#pragma clang fp contract(off)
+    const float keep = beta * acc, add = w * g;
+    return keep + add;
+}
+
+// The first micro-batch (beta == 0): acc = w g; the accumulator is not an input
+__device__ __forceinline__ float vf_grad_accum_first(float g, float w) {
+#pragma clang fp contract(off)
+    return w * g;
+}

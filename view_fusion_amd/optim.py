@@ -23,6 +23,13 @@ Two opt-in extras ride the same launch (both off by default: the step is then ex
     parameter's first step; with `ema_warmup` the decay of the update number t (0 for the first) is
     min(ema_decay, (1 + t) / (10 + t)).  `ema_state_dict()` / `load_ema_state_dict()` keep them OUTSIDE `state_dict()`,
     which stays torch's.  `swap_ema()` exchanges parameters and EMA in place (see train.Trainer.ema_weights).
+
+Gradient accumulation (opt-in, for a step whose batch runs as several micro-batches; train.Trainer(accum_steps=)):
+`accumulate(weight, first)` after each micro-batch's backward adds weight * p.grad into one accumulator per parameter in
+ONE launch (acc = w g on the first micro-batch, which never reads the accumulator, acc + w g afterwards; csrc/adam_update.h
+states the rounding; no atomics); the next `step()` takes the accumulators as its gradients -- for the norm pass, the
+update and `grad_norm` alike -- and leaves them in `p.grad`.  A `step()` without an `accumulate()` before it is the step
+described above, launch for launch.  One accumulator set per optimizer, the size of the parameters.
 """
 import ctypes
 
@@ -51,6 +58,10 @@ class FusedAdam(torch.optim.Optimizer):
         self._xs = None           # device float[8]: {d, 1 - d, max_norm, norm, scale, -, -, -}
         self._partials = None     # device double[blocks]: the norm pass' per-block sums
         self._swap = None         # swap_ema()'s descriptor table
+        self._acc = {}            # parameter -> its gradient accumulator (accumulate())
+        self._acc_plan = None     # accumulate()'s descriptor table {acc, grad, -, -, numel, first_block}
+        self._acc_scal = None     # device float[4]: {beta, w, -, -} of the coming accumulate launch
+        self._acc_live = False    # accumulate() ran since the last step(): step() reads the accumulators
 
     # -- the opt-in extras: weight EMA, global-norm clipping ------------------------------------------------------------
     @property
@@ -332,6 +343,92 @@ class FusedAdam(torch.optim.Optimizer):
                       1.0 - b2 ** b["t"], ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
         torch.autograd.graph.increment_version(b["params"])
 
+    # -- gradient accumulation over micro-batches ------------------------------------------------------------------
+    def _accum_plan(self, first):
+        """Descriptor table of accumulate(): rows {accumulator, gradient, -, -, numel, first_block} over every parameter
+        that has a gradient; the accumulators are made once per parameter and never move."""
+        params = [p for group in self.param_groups for p in group["params"] if p.grad is not None]
+        key = tuple(id(p) for p in params)
+        a = self._acc_plan
+        if a is not None and a["key"] == key:
+            return a
+        if not first:
+            raise _lib.VFHipError("FusedAdam.accumulate: the set of parameters with a gradient changed between the "
+                                  "micro-batches of one step")
+        if not params:
+            raise _lib.VFHipError("FusedAdam.accumulate: no parameter has a gradient")
+        rows, first_block = [], 0
+        for p in params:
+            if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
+                raise _lib.VFHipError("FusedAdam needs contiguous float32 GPU parameters")
+            if p not in self._acc:                     # (never read before the first accumulate has written it)
+                self._acc[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
+            rows.append([self._acc[p].data_ptr(), 0, 0, 0, p.numel(), first_block])
+            first_block += (p.numel() + 1023) // 1024
+        dev = params[0].device
+        if self._acc_scal is None or self._acc_scal.device != dev:
+            self._acc_scal = torch.zeros(4, device=dev, dtype=torch.float32)
+        a = self._acc_plan = dict(key=key, params=params, blocks=first_block, numel=sum(p.numel() for p in params),
+                                  host=[torch.tensor(rows, dtype=torch.int64).pin_memory() for _ in range(2)],
+                                  dev=[torch.empty(len(rows), 6, dtype=torch.int64, device=dev) for _ in range(2)],
+                                  ptrs=[None, None], done=[None, None], flip=0)
+        return a
+
+    def _accum_scalars(self, weight, first, raw):
+        ops._launch("adam", 0.0, "vf_adam_set_scalars", ctypes.c_void_p(self._acc_scal.data_ptr()),
+                    0.0 if first else 1.0, float(weight), 0.0, raw)
+
+    @torch.no_grad()
+    def accumulate(self, weight, first):
+        """After a micro-batch's backward: acc = (0 if first else acc) + weight * p.grad for every parameter with a
+        gradient, one launch (plus the one-thread launch that hands it {beta, weight}); the next step() uses the
+        accumulators as its gradients.  `first` starts a new sum: the accumulators are overwritten, never read."""
+        stream = torch.cuda.current_stream()
+        raw = ctypes.c_void_p(stream.cuda_stream)
+        a = self._accum_plan(first)
+        grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in a["params"]]
+        f = self._table_with(a, [g.data_ptr() for g in grads], stream)
+        self._accum_scalars(weight, first, raw)
+        ops._launch("adam", 0.0, "vf_grad_accum_multi", ctypes.c_void_p(a["dev"][f].data_ptr()), len(grads), a["blocks"],
+                    ctypes.c_void_p(self._acc_scal.data_ptr()), raw, nbytes=(8.0 if first else 12.0) * a["numel"])
+        self._acc_live = True
+
+    # the capturable form (train.Trainer: forward + backward + the accumulate launch as one graph per micro-batch
+    # geometry): the launch reads {beta, weight} from device memory that `accum_tick` refreshes before every replay
+    def accum_begin(self):
+        """Handle for capturing `accumulate_captured`, or None before the first eager accumulate() (no accumulators
+        yet) or when it did not cover every parameter."""
+        a = self._acc_plan
+        if a is None or len(a["params"]) != sum(len(g["params"]) for g in self.param_groups):
+            return None
+        rows = a["host"][0].clone()
+        return dict(plan=a, rows=rows, dev=torch.empty(rows.shape, dtype=torch.int64, device=a["params"][0].device))
+
+    @torch.no_grad()
+    def accumulate_captured(self, h):
+        """Inside the capture, after backward(): the accumulate launch on the gradients this capture allocated (their
+        addresses reach the table in `accum_end`, once the capture has ended)."""
+        a = h["plan"]
+        _lib.call("vf_grad_accum_multi", ctypes.c_void_p(h["dev"].data_ptr()), len(a["params"]), a["blocks"],
+                  ctypes.c_void_p(self._acc_scal.data_ptr()), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+    def accum_end(self, h):
+        grads = [p.grad for p in h["plan"]["params"]]
+        if any(g is None or not g.is_contiguous() for g in grads):
+            raise _lib.VFHipError("captured micro-batch: a parameter received no (or a strided) gradient")
+        h["rows"][:, 1] = torch.tensor([g.data_ptr() for g in grads], dtype=torch.int64)
+        h["dev"].copy_(h["rows"])
+        h["grads"] = grads                             # the graph writes these allocations on every replay
+        return h
+
+    def accum_tick(self, h, weight, first):
+        """Before a replay: this micro-batch's {beta, weight}."""
+        if h["plan"] is not self._acc_plan:
+            raise _lib.VFHipError("FusedAdam.accum_tick: the accumulators changed since this micro-batch was captured")
+        _lib.call("vf_adam_set_scalars", ctypes.c_void_p(self._acc_scal.data_ptr()), 0.0 if first else 1.0, float(weight),
+                  0.0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        self._acc_live = True
+
     # -- the step ------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def step(self, closure=None):
@@ -341,6 +438,10 @@ class FusedAdam(torch.optim.Optimizer):
                 loss = closure()
         stream = torch.cuda.current_stream()
         raw = ctypes.c_void_p(stream.cuda_stream)
+        if self._acc_live:                             # the accumulated gradient is this step's gradient, and what
+            for p in self._acc_plan["params"]:         # p.grad shows after it (stable addresses: the tables below are
+                p.grad = self._acc[p]                  # uploaded once)
+            self._acc_live = False
         if self._extras:
             self._step_extras(stream, raw)
             return loss
@@ -364,7 +465,11 @@ class FusedAdam(torch.optim.Optimizer):
         """Bucket b's descriptor table with this step's gradient addresses -> (which of its two copies, the gradient
         tensors the table points at: the caller keeps them until every launch that reads the table is enqueued)."""
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in b["params"]]
-        ptrs = [g.data_ptr() for g in grads]
+        return self._table_with(b, [g.data_ptr() for g in grads], stream), grads
+
+    @staticmethod
+    def _table_with(b, ptrs, stream):
+        """Which of table b's two device copies holds the gradient addresses `ptrs` (uploaded if neither does)."""
         f = b["flip"]
         if b["ptrs"][f] != ptrs:               # gradient arena / stable allocations: the table is reused as is
             f = b["flip"] = f ^ 1
@@ -379,7 +484,7 @@ class FusedAdam(torch.optim.Optimizer):
                 ev = torch.cuda.Event()
                 ev.record(stream)
                 b["done"][f], b["ptrs"][f] = ev, ptrs
-        return f, grads
+        return f
 
     def _step_extras(self, stream, raw):
         """step() with max_grad_norm and / or ema_decay: the norm over ALL gradients of the step first (every group and

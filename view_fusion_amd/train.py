@@ -108,12 +108,34 @@ def step_sample_ids(it, B, rank=0, world=1, global_batch=None):
     return it * global_batch + rank * B
 
 
+def split_batch(batch, extra, accum_steps):
+    """The per-step batch as `accum_steps` contiguous micro-batches along the batch dimension -> [(batch_m, extra_m)].
+    Every per-sample input is cut -- tensors (views, no copies) and lists whose leading length is the batch size B:
+    y_0, y_cond, angle, view_count (list, CPU or device tensor) and injected t / u / noise / sample_ids -- and anything
+    else (the seed, None) is handed to every micro-batch as it is.  Micro-batch m holds samples m B/A ... (m+1) B/A - 1,
+    so with the ids of step_sample_ids() it draws exactly what those samples draw in the undivided batch."""
+    A, B = int(accum_steps), batch["y_0"].shape[0]
+    if A < 1 or B % A:
+        raise ValueError(f"accum_steps={accum_steps} does not divide the batch of {B} samples")
+    n = B // A
+
+    def cut(v, m):
+        if torch.is_tensor(v):
+            return v[m * n:(m + 1) * n] if v.dim() >= 1 and v.shape[0] == B else v
+        if isinstance(v, (list, tuple)) and len(v) == B:
+            return v[m * n:(m + 1) * n]
+        return v
+
+    return [({k: cut(v, m) for k, v in batch.items()}, {k: cut(v, m) for k, v in extra.items()}) for m in range(A)]
+
+
 class _StepGraph:
-    """One captured training iteration (forward, backward, Adam) for one batch geometry."""
-    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads")
+    """One captured training iteration (forward, backward, Adam) for one batch geometry -- or, with accum_steps > 1, one
+    captured micro-batch (forward, backward, the accumulate launch)."""
+    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum")
 
     def __init__(self):
-        self.graph, self.seen = None, 0
+        self.graph, self.seen, self.accum = None, 0, None
 
 
 class Trainer:
@@ -147,14 +169,38 @@ class Trainer:
     update, in every launch mode (in a multi-rank run the norm is taken after the exchange, on the averaged gradients,
     so the replicas stay identical).  `grad_norm` is the last step's pre-clip norm as a 0-d device tensor (no sync);
     `with trainer.ema_weights(): drivers.evaluate(model, ...)` samples from the EMA.  The xgmi reducer applies Adam
-    inside its own all-reduce kernel and has neither: VF_REDUCER=xgmi with either option raises ValueError."""
+    inside its own all-reduce kernel and has neither: VF_REDUCER=xgmi with either option raises ValueError.
+
+    accum_steps = A (default 1: nothing above changes, launch for launch): step(batch) still takes the whole batch and
+    performs ONE optimizer step, but runs the batch as A contiguous micro-batches (split_batch; B % A == 0) -- forward and
+    backward on micro-batch m, then one launch that adds its gradient, weighted B_m / B, into FusedAdam's accumulators --
+    and then the norm pass (max_grad_norm) and the Adam (+ EMA) launch on the accumulated gradient, which is also what
+    p.grad shows afterwards.  Peak activation memory is one micro-batch's; the price is one more parameter-sized buffer.
+    LR schedule, `it`, Adam's step count and the EMA advance once per step(); the returned loss is sum_m (B_m / B) loss_m,
+    the full batch's loss, a device tensor.  With seed= micro-batch m draws for the ids the undivided batch gives its
+    samples, so the accumulated gradient is the big batch's up to summation order.  In graph mode the geometry key is a
+    MICRO-batch's geometry and a graph holds forward + backward + the accumulate launch ({beta, weight} read from device
+    memory: the same graph serves every m and every later step); the norm and Adam launches follow the last replay
+    eagerly, as in "split" mode.  GRAPH_AFTER / GRAPH_MAX count micro-batch sightings and `graph_steps` micro-batch
+    replays.  The weight packs at the head of a micro-batch graph are repeated for m > 0 (profiles/grad_accum.md prices
+    them).  Single process, GPU model only: world > 1 or a CPU model with accum_steps > 1 raises ValueError (the gradient
+    arena averages in place as segments complete)."""
     GRAPH_AFTER = 2
     GRAPH_MAX = 96
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
     inject_capture_failure = None   # set by tests (class or instance attribute), never read from the environment
 
     def __init__(self, model, world=1, local_rank=0, lr_warmup=2500, decay_it=4000000, bucket_cap_mb=32, graph=None,
-                 seed=None, global_batch=None, ema_decay=None, ema_warmup=False, max_grad_norm=None):
+                 seed=None, global_batch=None, ema_decay=None, ema_warmup=False, max_grad_norm=None, accum_steps=1):
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+            raise ValueError(f"accum_steps must be a positive integer, got {accum_steps!r}")
+        if accum_steps > 1 and world > 1:
+            raise ValueError("accum_steps > 1 is single-process only: the gradient exchange of a multi-rank run (every "
+                             "reducer) averages each micro-batch's gradients as they complete, and holding the "
+                             "collectives back until the last micro-batch is not built")
+        if accum_steps > 1 and not next(model.parameters()).is_cuda:
+            raise ValueError("accum_steps > 1 accumulates inside the fused HIP optimizer: the model must be on the GPU")
+        self.accum_steps = accum_steps
         self.module = model
         # seed: the training draws come from the counter-based generator (csrc/rng.h) keyed by a global sample index
         # (step_sample_ids), not from torch's device generator; None (default): as before
@@ -216,7 +262,7 @@ class Trainer:
         self._scal = None           # device {lr, 1-b1^t, 1-b2^t}
         self._last_graph = None
         self._graph_epoch = None    # FusedAdam.graph_epoch the kept graphs were captured under (None: none captured)
-        self.graph_steps = 0        # iterations that ran as a replay (diagnostics / tests)
+        self.graph_steps = 0        # iterations (accum_steps > 1: micro-batches) that ran as a replay (diagnostics / tests)
         self.world = world
         self._check_base = self.GRAPH_AFTER     # multi-rank agreement: flag read at _check_base + 1, 4, 16, then every AGREE_EVERY
         self.demotions = 0
@@ -332,7 +378,7 @@ class Trainer:
         anchors = (g.data_ptr() if torch.is_tensor(g) else 0, self._params[0].data_ptr(), self._params[-1].data_ptr())
         return tuple((k, tuple(t.shape), t.dtype) for k, t in ts) + (anchors + (seed,), sum(vc)), vc
 
-    def _capture(self, e, key, vc, batch, extra):
+    def _capture(self, e, key, vc, batch, extra, accum=False):
         from . import ops
         dev = batch["y_0"].device
         arena = self.arena
@@ -341,9 +387,14 @@ class Trainer:
             raise RuntimeError("injected capture failure (Trainer.inject_capture_failure)")
         # With a host-driven transport (gloo) the graph ends with the backward pass; the exchange and the Adam launch
         # follow each replay eagerly.  On RCCL the segment all-reduces and Adam are part of the graph.
-        split = arena is not None and not arena.capturable
+        # A micro-batch of an accumulated step (accum): the graph ends with the accumulate launch instead; the norm
+        # and Adam launches follow the last micro-batch's replay eagerly.
+        split = accum or (arena is not None and not arena.capturable)
         adam = None if split else self.opt.graph_begin()
         if adam is None and not split:
+            return False
+        acc = self.opt.accum_begin() if accum else None
+        if accum and acc is None:
             return False
         if self._scal is None:
             self._scal = torch.zeros(3, device=dev, dtype=torch.float32)
@@ -378,7 +429,9 @@ class Trainer:
                         grads = arena.capture_finish(grads)
                     for (_, p), gr in zip(self._named, grads):
                         p.grad = gr
-                    if not split:
+                    if acc is not None:
+                        self.opt.accumulate_captured(acc)
+                    elif not split:
                         self.opt.step_captured(adam, self._scal)
                 except Exception as err:      # noqa: BLE001
                     failed = err
@@ -391,6 +444,7 @@ class Trainer:
         if self._pool is None:
             self._pool = g.pool()
         e.adam = None if split else self.opt.graph_end(adam)
+        e.accum = None if acc is None else self.opt.accum_end(acc)
         self._graph_epoch = self.opt.graph_epoch if split else adam["epoch"]
         e.loss, e.graph = loss.detach(), g
         e.grads = list(grads)
@@ -398,7 +452,7 @@ class Trainer:
         e.keep = (fix, tables, offs, getattr(self.module, "gammas", None))
         return True
 
-    def _graph_step(self, e, vc, batch, extra):
+    def _graph_step(self, e, vc, batch, extra, accum=None):
         if vc != e.vc:
             off = [0]
             for v in vc:
@@ -408,6 +462,11 @@ class Trainer:
         for k, dst in e.inputs.items():
             src = extra[k] if k in extra else batch[k]
             dst.copy_(src.reshape(dst.shape), non_blocking=True)
+        if accum is not None:                          # a micro-batch: its gradient goes into the accumulators, which
+            self.opt.accum_tick(e.accum, *accum)       # the optimizer step after the last one reads and leaves in .grad
+            e.graph.replay()
+            self.graph_steps += 1
+            return e.loss.clone()
         if self._last_graph is not e:                  # .grad shows the gradients of the graph that ran last
             for p, gr in zip(self._params, e.grads):
                 p.grad = gr
@@ -449,8 +508,21 @@ class Trainer:
         if not self.model.training or any(not m.training for m in self._mode_modules):
             self.model.train()
         self._agree()
+        if self.accum_steps == 1:
+            return self._run(batch, extra)
+        w, total = 1.0 / self.accum_steps, None
+        for m, (bm, em) in enumerate(split_batch(batch, extra, self.accum_steps)):
+            part = self._run(bm, em, accum=(w, m == 0)) * w
+            total = part if total is None else total + part
+        self.opt.step()                                # the norm pass and Adam (+ EMA) on the accumulated gradient
+        return total
+
+    def _run(self, batch, extra, accum=None):
+        """Forward, backward and the optimizer step on `batch` as a replay or launch by launch; accum = (weight, first):
+        `batch` is a micro-batch, and in place of the optimizer step its gradient is added into the accumulators."""
         key, vc = self._graph_key(batch, extra) or (None, None)
-        if key is not None and self._graph_epoch is not None and self.opt.graph_epoch != self._graph_epoch:
+        if key is not None and accum is None and self._graph_epoch is not None and \
+                self.opt.graph_epoch != self._graph_epoch:      # (a micro-batch graph addresses no Adam state)
             # the optimizer state was replaced (load_state_dict, a changed parameter set): the captured steps still
             # address the old moment tensors -- drop them; every geometry is captured again after its eager sightings
             self._drop_graphs()
@@ -461,7 +533,7 @@ class Trainer:
             if e is not None:
                 if e.graph is None and e.seen >= self.GRAPH_AFTER:
                     try:
-                        if not self._capture(e, key, vc, batch, extra):
+                        if not self._capture(e, key, vc, batch, extra, accum=accum is not None):
                             self.use_graph = False
                             if self.arena is not None:     # this rank stays eager: tell the others (as a failure does)
                                 self.arena.flag_value = 1.0
@@ -475,7 +547,7 @@ class Trainer:
                             self.arena.flag_value = 1.0    # the next agreement point (_agree)
                         self.opt.zero_grad()
                 if e.graph is not None:
-                    return self._graph_step(e, vc, batch, extra)
+                    return self._graph_step(e, vc, batch, extra, accum)
                 e.seen += 1
         self._last_graph = None
         self.opt.zero_grad()
@@ -487,7 +559,9 @@ class Trainer:
         loss.backward()
         if self.arena is not None:
             self.arena.finish()
-        if not fused:
+        if accum is not None:
+            self.opt.accumulate(*accum)
+        elif not fused:
             self.opt.step()
         # detached: a caller that keeps the returned loss should not keep this iteration's autograd graph (its saved
         # activations: several GB at B=16) alive with it
