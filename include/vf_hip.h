@@ -318,6 +318,24 @@ int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, 
                        int B, int n);
 int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int T, long long* t, float* u, int B);
 
+/* ---- batch assembly from a device-resident view store (csrc/batch.hip; data.ViewStore): the reference loader's
+ *      process_sample + collate + H2D, data/nmr_dataset.py:10-52, as one launch.  store: planar uint8 [N][24][3][H][W],
+ *      H * W % 4 == 0.  The views of sample b are a function of (seed, ids[b]) alone: the data draws of csrc/rng.h (kind 4)
+ *      through csrc/batch_plan.h.  objects (DEVICE int64 [B] | NULL): the object of every sample, else drawn from
+ *      [0, N); an object outside [0, N) fills that sample's outputs with NaN and reads nothing.
+ *      y_0 [B][3][H][W], y_cond [B][23][3 (relative: 6)][H][W], angle [B] (relative: the relative angle), objects_out
+ *      (|NULL) [B] the objects used.  all != 0: the identity plan -- y_cond [B][24][3][H][W] = the 24 views of
+ *      objects[b] (required) as floats; seed, ids, y_0, angle unused.  Grid (24, B), no atomics, no workspace. ---- */
+int vf_batch_assemble(const unsigned char* store, long N, int H, int W, unsigned long long seed, const long long* ids,
+                      const long long* objects, int B, int train, int relative, int all, float* y_0, float* y_cond,
+                      float* angle, long long* objects_out, void* stream);
+/* Host mirror (HOST pointers, no stream, no GPU): per sample src [B][24] (cond[k] = views[src[k + 1]]), target [B]
+ * (the target view p[0]), q01 [B][2] (q[0], q[1] of the relative angle), second [B], view_count [B] in [lo, hi]
+ * (1 <= lo <= hi <= 23) and the object [B] (objects[b] when given, checked against N) */
+int vf_batch_host_plan(unsigned long long seed, const long long* ids, int B, int train, int lo, int hi, long N,
+                       const long long* objects, int* src, int* target, int* q01, int* second, long long* view_count,
+                       long long* object);
+
 /* eval metric next to the path: utils/metrics.py:6-8; out[b] = PSNR of image b (n floats each) */
 int vf_psnr(const float* generated, const float* target, float* out /*[B]*/, int B, int n, void* stream);
 /* ... and utils/metrics.py:11-12 (csrc/ssim.hip): out[b] = SSIM of image b, [B][C][H][W] inputs, any H, W >= 11 and

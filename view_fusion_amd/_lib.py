@@ -139,6 +139,8 @@ SIGNATURES = {
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],
+    "vf_batch_assemble": [_P, _L, _I, _I, _U64, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "vf_batch_host_plan": [_U64, _P, _I, _I, _I, _I, _L, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPE = {"vf_conv1x1_bf16x3_pack_dwords": _L, "vf_conv_wgrad_ws_floats": _L, "vf_time_affine_ws_floats": _L, "vf_wino_conv_ws_floats": _L, "vf_wino44_conv_ws_floats": _L, "vf_wino_wgrad_ws_floats": _L, "vf_conv_fwd_ws_floats": _L,
             "vf_conv_small_pack_floats": _L, "vf_ssim_workspace_floats": _L, "vf_lpips_workspace_floats": _L}

@@ -15,6 +15,7 @@
 //   kind 1  training noise, step 0
 //   kind 2  sampler start noise y_T, step 0
 //   kind 3  reverse-step noise z, step = the timestep index t[b]
+//   kind 4  batch assembly (the view store, batch_plan.h / batch.hip), step 0: see "Data draws" below
 //
 // One Philox call gives four 32-bit words w0..w3.
 //   t = 1 + mulhi32(w0, T - 1)          in [1, T - 1] = the reference's randint(1, T); exact integer arithmetic
@@ -28,6 +29,34 @@
 //   device libraries then agree to their last-place errors (the tests bound device - float64 by 4 x the float32
 //   restatement's own error).
 //
+// Data draws (kind 4, step 0): which views of a 24-view object become the target and the conditioning views of a
+// training / eval sample, how many of them the model sees, and which object it is -- the reference loader's
+// process_sample (data/nmr_dataset.py:10-52) and the training loop's view_count (experiment.py:277-279), keyed like every
+// other draw by (seed, sample id) alone.  A sample's data draws are the 52 words w[0..51] of blocks 0..12,
+// w[4 * block + lane] the word `lane` of that block; mulhi32(w, n) = (w * n) >> 32 in [0, n), exact integer arithmetic
+// whose bias against a uniform draw is at most 2^-32 per draw.
+//   w[0..22]   the first Fisher-Yates shuffle of p = 0..23: for i = 23 ... 1, with word w[23 - i]:
+//              r = mulhi32(w, i + 1); swap p[i], p[r]
+//   w[23]      second = train && (w >> 8) < 1677722: u < 0.1 for u = (w >> 8) * 2^-24 (1677722 = ceil(0.1 * 2^24)), as an
+//              integer compare, so no float rounding takes part
+//   w[24..46]  the same shuffle (word w[24 + 23 - i]) applied to a copy q of p: the reference shuffling images_idx a
+//              second time in place.  The words are always consumed; q is used only when `second`, otherwise q = p
+//   w[47]      view_count = lo + mulhi32(w, hi - lo + 1); [lo, hi] = [1, max_views] by default, [max_views + 1, 23]
+//              for the extrapolation call shape
+//   w[48]      object = mulhi32(w, N), N = the store's object count; used only when the caller names no objects:
+//              sampling with replacement, as the reference's resampled=True
+//   w[49..51]  unused
+// What a sample is made of -- the reference's index algebra, quirks included (parity is the contract):
+//   src            = second ? p[q[.]] : p
+//   target         = views[p[0]]: the first shuffle's p, even when `second` (the target may then be among the
+//                    conditioning views, which is the point of the second shuffle)
+//   angle          = float32(2 pi / 24 * p[0]), the product taken in double
+//   cond[k]        = views[src[k + 1]], k = 0..22
+//   relative_angle = float32(2 pi / 24 * (q[1] - q[0])): the VALUES of q -- after a second shuffle these are not the
+//                    views src[1], src[0] that relative_cond shows.  The reference does this; it is kept, not "fixed"
+//   relative_cond[k] = cat(views[src[1]], views[src[k + 1]]) on the channel axis (6 channels)
+//   pixel          = float32(byte) / float32(255), correctly rounded
+//
 // Plain C++: no inline assembly, every value leaves a kernel through an ordinary vector store.
 #pragma once
 #include <math.h>
@@ -39,7 +68,7 @@
 #define VF_RNG_HD inline
 #endif
 
-enum { VF_RNG_TRAIN_SCALARS = 0, VF_RNG_TRAIN_NOISE = 1, VF_RNG_START_NOISE = 2, VF_RNG_STEP_NOISE = 3 };
+enum { VF_RNG_TRAIN_SCALARS = 0, VF_RNG_TRAIN_NOISE = 1, VF_RNG_START_NOISE = 2, VF_RNG_STEP_NOISE = 3, VF_RNG_DATA = 4 };
 
 VF_RNG_HD void vf_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
     uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];

@@ -492,6 +492,25 @@ class Trainer:
         torch.add(ent[0], step_sample_ids(self.it, B, rank, self.world, self.global_batch), out=ent[1])
         return ent[1]
 
+    def draw_batch(self, store, B, max_views=6, relative=False):
+        """The batch of the step about to run, assembled from a data.ViewStore in one launch: its sample ids are
+        step_sample_ids(self.it + 1, B, rank, world, global_batch) + b -- the very ids that step's t / u / noise draws
+        use -- so `trainer.step(trainer.draw_batch(store, 16))` is the whole training loop body, and a sample's views,
+        view_count and object are functions of (seed, id) like its noise: unchanged by accum_steps, by the launch mode
+        and by how the global batch is split over ranks (every rank holds the store; the ids are disjoint by
+        construction).  Needs Trainer(seed=...).  No host sync."""
+        if self.seed is None:
+            raise ValueError("draw_batch draws from the seeded generator: construct the Trainer with seed=...")
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        first = step_sample_ids(self.it + 1, B, rank, self.world, self.global_batch)
+        ent = self._ids.get(("draw", B))
+        if ent is None:
+            ent = self._ids[("draw", B)] = (torch.arange(B, dtype=torch.int64, device=store.device),
+                                            torch.empty(B, dtype=torch.int64, device=store.device))
+        torch.add(ent[0], first, out=ent[1])
+        return store.batch(self.seed, torch.arange(first, first + B, dtype=torch.int64), mode="train",
+                           max_views=max_views, relative=relative, ids_device=ent[1])
+
     def step(self, batch, **extra):
         """One reference iteration; returns the (device) loss tensor, no host sync."""
         self.it += 1
