@@ -267,6 +267,22 @@ int vf_compose_fwd(const float* unet_out, const int* off, const float* target /*
                    int Cout, int HW, int maxV, int weighting, void* stream);
 int vf_compose_mse_bwd(const float* unet_out, const int* off, const float* target, const float* noise_hat,
                        const float* gloss, float* dout, int B, int Cout, int HW, int weighting, void* stream);
+/* Loss options (csrc/loss_weight.h holds the specification): the two calls above with a target, generalised.
+ * penalty 0 mse | 1 l1 | 2 huber(delta > 0) of d = noise_hat - target;  weight_kind 0 none | 1 min_snr(a) | 2 p2(k = a,
+ * p = b) of level[b] (DEVICE float [B], the sample's gamma).  Writes noise_hat, sample_loss[b] = mean_i rho(d_bi),
+ * sample_w[b] and loss = sum_b w_b s_b / B; bin_sum (float [K]) / bin_cnt (int [K]) (both or neither): persistent
+ * accumulators, bin min(K-1, (int)(level K)) += the UNWEIGHTED s_b / 1.  Two launches, no atomics. */
+int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* target, const float* level,
+                        float* noise_hat, float* loss_part /*[B*64]*/, float* sample_loss /*[B]*/,
+                        float* sample_w /*[B]*/, float* loss, float* bin_sum /*[K]|NULL*/, int* bin_cnt /*[K]|NULL*/,
+                        int B, int Cout, int HW, int weighting, int penalty, float delta, int weight_kind, float a,
+                        float b, int K, void* stream);
+/* d unet_out for gloss * loss: g = gloss w_b rho'(d) / (3 HW B) through the softmax / mean; one launch */
+int vf_compose_loss_bwd(const float* unet_out, const int* off, const float* target, const float* noise_hat,
+                        const float* gloss, const float* sample_w, float* dout, int B, int Cout, int HW, int weighting,
+                        int penalty, float delta, void* stream);
+/* Host mirror of the weight function: HOST pointers, no stream, no GPU needed. */
+int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, float* out /*[B]*/);
 int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,
                      const long long* t, const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
                      const float* posterior_log_variance, const float* posterior_mean_coef1,

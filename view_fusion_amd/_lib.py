@@ -129,6 +129,9 @@ SIGNATURES = {
     "vf_stack_views": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vf_compose_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vf_compose_mse_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vf_compose_loss_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _F, _I, _P],
+    "vf_compose_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "vf_loss_weights_host": [_P, _I, _I, _F, _F, _P],
     "vf_p_sample_tail": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "vf_draw_train": [_U64, _P, _P, _I, _P, _P, _P, _I, _P],
     "vf_randn_ids": [_U64, _P, _I, _I, _P, _I, _I, _P],

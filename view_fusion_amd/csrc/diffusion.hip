@@ -11,7 +11,13 @@
 //
 // Few-step sampling: sampler_step(_rng)_kernel is the same tail with a table-driven linear-multistep update
 // (strided DDIM / DPM-Solver++ 2M) instead of the one-step DDPM posterior; the p_sample_tail kernels stay as they are.
+//
+// Loss options (loss_weight.h holds the specification): compose_loss_fwd / _finish / _bwd are siblings of the MSE
+// kernels with a penalty template (mse / l1 / huber), a per-sample noise-level weight (min-SNR, P2), the per-sample
+// loss handed back and an optional loss-by-level histogram -- same launch count, no atomics.  Opt-in; the MSE kernels
+// and their entry points are untouched.
 #include "common.h"
+#include "loss_weight.h"
 #include "rng.h"
 
 namespace {
@@ -446,6 +452,124 @@ __global__ __launch_bounds__(256) void psnr_kernel(const float* __restrict__ a, 
     if (threadIdx.x == 0) out[blockIdx.x] = 20.0f * log10f(1.0f / sqrtf(s / (float)n));
 }
 
+// ---- loss options: penalty x noise-level weight, per-sample loss, loss-by-level histogram (loss_weight.h) ----
+// compose_fwd_kernel's sibling: the same noise_hat and the same (b, chunk) partial sums, of rho(noise_hat - target).
+template <int PEN>
+__global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __restrict__ out,
+                                                               const int* __restrict__ off,
+                                                               const float* __restrict__ target,
+                                                               float* __restrict__ noise_hat,
+                                                               float* __restrict__ loss_part, int Cout, int HW,
+                                                               int weighting, float delta) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    float acc = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        *reinterpret_cast<float4*>(noise_hat + o) = nh;
+        const float4 t = *reinterpret_cast<const float4*>(target + o);
+        acc += (vf_loss_rho<PEN>(nh.x - t.x, delta) + vf_loss_rho<PEN>(nh.y - t.y, delta)) +
+               (vf_loss_rho<PEN>(nh.z - t.z, delta) + vf_loss_rho<PEN>(nh.w - t.w, delta));
+    }
+    acc = block_sum<256>(acc, red);
+    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// One workgroup.  Per sample (one thread each): s_b = its `ch` partials in index order / n, w_b = the weight of its
+// level; then loss = sum_b w_b s_b / B in index order (one thread); then, with a histogram attached, one thread per bin
+// walks the samples in index order and adds the UNWEIGHTED s_b of its own bin into the persistent accumulators.  Every
+// address is written by exactly one thread: no atomics, the same bits on every run.
+__global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __restrict__ part,
+                                                                 const float* __restrict__ level,
+                                                                 float* __restrict__ sample_loss,
+                                                                 float* __restrict__ sample_w, float* __restrict__ loss,
+                                                                 float* __restrict__ bin_sum, int* __restrict__ bin_cnt,
+                                                                 int B, int ch, int K, float inv_n, int kind, float a,
+                                                                 float b) {
+    for (int s = threadIdx.x; s < B; s += 64) {
+        float acc = 0.f;
+        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
+        sample_loss[s] = acc * inv_n;
+        sample_w[s] = vf_loss_weight(kind, a, b, level[s]);
+    }
+    __syncthreads();                        // (also makes the workgroup's global stores above visible to it)
+    if (threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
+        *loss = acc / (float)B;
+    }
+    if (bin_sum == nullptr) return;
+    for (int k = threadIdx.x; k < K; k += 64) {
+        float sum = 0.f;
+        int cnt = 0;
+        for (int s = 0; s < B; ++s) {
+            int bin = (int)(level[s] * (float)K);
+            bin = bin > K - 1 ? K - 1 : bin;
+            if (bin == k) {
+                sum += sample_loss[s];
+                ++cnt;
+            }
+        }
+        bin_sum[k] += sum;
+        bin_cnt[k] += cnt;
+    }
+}
+
+// compose_mse_bwd_kernel's sibling: g = gloss w_b rho'(noise_hat - target) / (n B), then the same softmax / mean
+// chain rule (d eps_v = w_v g;  d logit_v = w_v (eps_v - nh) g;  mean ablation: d eps_v = g / count, logits zero).
+template <int PEN>
+__global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __restrict__ out,
+                                                               const int* __restrict__ off,
+                                                               const float* __restrict__ target,
+                                                               const float* __restrict__ noise_hat,
+                                                               const float* __restrict__ gloss,
+                                                               const float* __restrict__ sample_w,
+                                                               float* __restrict__ dout, int Cout, int HW,
+                                                               int weighting, float inv_nb, float delta) {
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const float gs = gloss[0] * sample_w[b] * inv_nb;
+    const size_t vs = (size_t)Cout * HW;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
+        const float4 t = *reinterpret_cast<const float4*>(target + o);
+        const float4 g = make_float4(gs * vf_loss_drho<PEN>(nh.x - t.x, delta), gs * vf_loss_drho<PEN>(nh.y - t.y, delta),
+                                     gs * vf_loss_drho<PEN>(nh.z - t.z, delta), gs * vf_loss_drho<PEN>(nh.w - t.w, delta));
+        if (!weighting) {
+            const float inv = 1.0f / (float)(v1 - v0);
+            const float4 d = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
+            for (int v = v0; v < v1; ++v) {
+                *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)c * HW + p) = d;
+                if (Cout > 3)
+                    *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)(3 + c) * HW + p) =
+                        make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            continue;
+        }
+        float4 mx, inv;
+        (void)compose4(out, Cout, HW, v0, v1, c, p, 1, &mx, &inv);
+        for (int v = v0; v < v1; ++v) {
+            const float* ep = out + (size_t)v * vs + (size_t)c * HW + p;
+            const float4 e = *reinterpret_cast<const float4*>(ep);
+            const float4 l = *reinterpret_cast<const float4*>(ep + (size_t)3 * HW);
+            const float4 w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
+                                         expf(l.w - mx.w) * inv.w);
+            float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
+            *reinterpret_cast<float4*>(dp) = make_float4(w.x * g.x, w.y * g.y, w.z * g.z, w.w * g.w);
+            *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
+                make_float4(w.x * (e.x - nh.x) * g.x, w.y * (e.y - nh.y) * g.y, w.z * (e.z - nh.z) * g.z,
+                            w.w * (e.w - nh.w) * g.w);
+        }
+    }
+}
+
 inline int chunks_for(int n4) {
     int c = (n4 + 255) / 256;
     return c < 1 ? 1 : (c > 64 ? 64 : c);
@@ -506,6 +630,68 @@ int vf_compose_mse_bwd(const float* unet_out, const int* off, const float* targe
                        unet_out, off, target, noise_hat, gloss, dout, Cout, HW, weighting,
                        1.0f / ((float)B * 3.0f * (float)HW));
     VF_RETURN_LAST_ERROR();
+}
+
+// ---- loss options (loss_weight.h): vf_compose_fwd with a target / vf_compose_mse_bwd with a penalty, a per-sample
+// weight of `level`, the per-sample loss and an optional histogram.  Two launches forward, one backward, as those. ----
+static inline bool loss_args_ok(int B, int Cout, int HW, int weighting, int penalty, float delta) {
+    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6)) return false;
+    if (penalty < VF_LOSS_MSE || penalty > VF_LOSS_HUBER) return false;
+    return penalty != VF_LOSS_HUBER || delta > 0.0f;
+}
+
+int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* target, const float* level,
+                        float* noise_hat, float* loss_part, float* sample_loss, float* sample_w, float* loss,
+                        float* bin_sum, int* bin_cnt, int B, int Cout, int HW, int weighting, int penalty, float delta,
+                        int weight_kind, float a, float b, int K, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
+    if (!target || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = chunks_for(3 * HW / 4);
+    const dim3 grid(ch, B), block(256);
+    if (penalty == VF_LOSS_L1)
+        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_L1>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           loss_part, Cout, HW, weighting, delta);
+    else if (penalty == VF_LOSS_HUBER)
+        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_HUBER>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           loss_part, Cout, HW, weighting, delta);
+    else
+        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           loss_part, Cout, HW, weighting, delta);
+    hipLaunchKernelGGL(compose_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_part, level, sample_loss, sample_w,
+                       loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_compose_loss_bwd(const float* unet_out, const int* off, const float* target, const float* noise_hat,
+                        const float* gloss, const float* sample_w, float* dout, int B, int Cout, int HW, int weighting,
+                        int penalty, float delta, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta) || !sample_w) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(chunks_for(3 * HW / 4), B), block(256);
+    const float inv_nb = 1.0f / ((float)B * 3.0f * (float)HW);
+    if (penalty == VF_LOSS_L1)
+        hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_L1>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
+    else if (penalty == VF_LOSS_HUBER)
+        hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_HUBER>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
+    else
+        hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirror: vf_loss_weight itself on the CPU.  HOST pointers, no stream.
+int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, float* out) {
+    if (B < 0 || kind < VF_LOSS_W_NONE || kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    for (int s = 0; s < B; ++s) out[s] = vf_loss_weight(kind, a, b, level[s]);
+    return 0;
 }
 
 int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* t,

@@ -47,7 +47,7 @@ from .attention import (  # noqa: F401
     _AttentionFn, _AttentionStreamFn, _ConcatFn, attention, attention_route, attention_streaming, concat_channels
 )
 from .diffusion import (  # noqa: F401
-    _ComposeLossFn, compose, compose_mse_loss, draw_train, gather_level, p_sample_tail, philox_ids, psnr, randn_ids,
+    _ComposeLossFn, _ComposeLossOptFn, compose, compose_loss, compose_mse_loss, draw_train, gather_level, p_sample_tail, philox_ids, psnr, randn_ids,
     sample_ids, sampler_step, ssim, stack_views, view_offsets
 )
 from .lpips import (  # noqa: F401

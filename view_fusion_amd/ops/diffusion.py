@@ -174,6 +174,66 @@ def compose_mse_loss(unet_out, target_noise, off, B, weighting):
     return _ComposeLossFn.apply(unet_out, _c(target_noise), off, B, weighting)
 
 
+# ---- loss options (csrc/loss_weight.h): penalty x noise-level weight, per-sample loss, loss-by-level histogram ----
+PENALTIES = {"mse": 0, "l1": 1, "huber": 2}
+WEIGHT_KINDS = {None: 0, "none": 0, "min_snr": 1, "p2": 2}
+
+
+class _ComposeLossOptFn(torch.autograd.Function):
+    """_ComposeLossFn with a penalty, a per-sample weight of the noise level and the per-sample loss as a second
+    (non-differentiable) output: the same two launches forward and one backward."""
+
+    @staticmethod
+    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt):
+        _check(out, target, level, bin_sum)
+        S, Cout, H, W = out.shape
+        if level.numel() != B:
+            raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
+        K = 0
+        if bin_sum is not None:
+            K = bin_sum.numel()
+            if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
+                raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
+        nh = torch.empty(B, 3, H, W, device=out.device, dtype=torch.float32)
+        buf = torch.empty(B * 66 + 1, device=out.device, dtype=torch.float32)   # partials | sample_loss | sample_w | loss
+        sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * 66:]
+        _call("vf_compose_loss_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(level), _ptr(nh),
+              _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
+              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
+              delta, kind, a, b, K, _stream())
+        ctx.save_for_backward(out, target, nh, off, sample_w)
+        ctx.B, ctx.weighting, ctx.penalty, ctx.delta = B, int(weighting), penalty, delta
+        ctx.mark_non_differentiable(sample_loss)
+        return loss.reshape(()), sample_loss
+
+    @staticmethod
+    def backward(ctx, gloss, _gsample):
+        out, target, nh, off, sample_w = ctx.saved_tensors
+        S, Cout, H, W = out.shape
+        gloss = _c(gloss.reshape(1).float())
+        dout = torch.empty_like(out)
+        _call("vf_compose_loss_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(nh), _ptr(gloss),
+              _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, _stream())
+        return (dout,) + (None,) * 12
+
+
+def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delta=1.0, weight_kind=None, a=0.0, b=0.0,
+                 hist=None):
+    """compose_mse_loss with options: -> (loss, sample_loss).  d = compose(unet_out) - target;
+    penalty "mse" d^2 | "l1" |d| | "huber" (F.huber_loss with `delta`);  sample_loss[b] = mean_i rho(d_bi) (B,), detached;
+    weight_kind None | "min_snr" (w = min(1, a (1 - g) / g)) | "p2" (w = (a + g / (1 - g))^-b) of g = level[b], the
+    sample's gamma (device float32 (B,));  loss = sum_b w_b sample_loss[b] / B, differentiable in unet_out.
+    hist = (bin_sum float32 [K], bin_cnt int32 [K]) device accumulators: bin min(K - 1, int(g K)) receives the
+    UNWEIGHTED sample_loss[b] and a count; they persist across calls (the caller zeroes them)."""
+    if penalty not in PENALTIES:
+        raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
+    if weight_kind not in WEIGHT_KINDS:
+        raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2'")
+    bin_sum, bin_cnt = hist if hist is not None else (None, None)
+    return _ComposeLossOptFn.apply(unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty],
+                                   float(delta), WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt)
+
+
 def compose(unet_out, off, B, max_views, weighting, want_weights=True):
     """Inference compose: -> noise (B,3,H,W), weights (B,maxV,3,H,W) | None."""
     _check(unet_out)

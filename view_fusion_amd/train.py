@@ -132,7 +132,7 @@ def split_batch(batch, extra, accum_steps):
 class _StepGraph:
     """One captured training iteration (forward, backward, Adam) for one batch geometry -- or, with accum_steps > 1, one
     captured micro-batch (forward, backward, the accumulate launch)."""
-    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum")
+    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum", "sample")
 
     def __init__(self):
         self.graph, self.seen, self.accum = None, 0, None
@@ -184,14 +184,24 @@ class Trainer:
     eagerly, as in "split" mode.  GRAPH_AFTER / GRAPH_MAX count micro-batch sightings and `graph_steps` micro-batch
     replays.  The weight packs at the head of a micro-batch graph are repeated for m > 0 (profiles/grad_accum.md prices
     them).  Single process, GPU model only: world > 1 or a CPU model with accum_steps > 1 raises ValueError (the gradient
-    arena averages in place as segments complete)."""
+    arena averages in place as segments complete).
+
+    loss_bins = K (default None: nothing above changes): the trainer owns a K-bin histogram of the per-sample loss by noise
+    level -- two K-element device accumulators that the loss kernels add into (ViewFusion.loss_hist; csrc/loss_weight.h) --
+    read with loss_by_level().  With it the loss-option kernels run even for the default objective (the same launch count).
+    The objective itself is the model's: `model.set_loss(...)`; a set_loss() call between steps takes effect on the next
+    step -- the captured steps are dropped and every geometry is captured again after its eager sightings -- never a
+    replay of the old objective.  In graph mode the accumulators, `model.last_sample_loss` and
+    `model.last_level` are static buffers of the captured step; with accum_steps > 1 every micro-batch adds its samples
+    (B counts per step) and the two `last_*` tensors show the last micro-batch.  GPU model only."""
     GRAPH_AFTER = 2
     GRAPH_MAX = 96
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
     inject_capture_failure = None   # set by tests (class or instance attribute), never read from the environment
 
     def __init__(self, model, world=1, local_rank=0, lr_warmup=2500, decay_it=4000000, bucket_cap_mb=32, graph=None,
-                 seed=None, global_batch=None, ema_decay=None, ema_warmup=False, max_grad_norm=None, accum_steps=1):
+                 seed=None, global_batch=None, ema_decay=None, ema_warmup=False, max_grad_norm=None, accum_steps=1,
+                 loss_bins=None):
         if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
             raise ValueError(f"accum_steps must be a positive integer, got {accum_steps!r}")
         if accum_steps > 1 and world > 1:
@@ -201,6 +211,17 @@ class Trainer:
         if accum_steps > 1 and not next(model.parameters()).is_cuda:
             raise ValueError("accum_steps > 1 accumulates inside the fused HIP optimizer: the model must be on the GPU")
         self.accum_steps = accum_steps
+        if loss_bins is not None:
+            if isinstance(loss_bins, bool) or not isinstance(loss_bins, int) or loss_bins < 1:
+                raise ValueError(f"loss_bins must be a positive integer or None, got {loss_bins!r}")
+            if not next(model.parameters()).is_cuda:
+                raise ValueError("loss_bins is filled by the fused HIP loss kernels: the model must be on the GPU")
+            if not hasattr(model, "set_loss"):
+                raise ValueError("loss_bins needs a ViewFusion model (its forward feeds the histogram)")
+            dev = next(model.parameters()).device
+            model.loss_hist = (torch.zeros(loss_bins, device=dev, dtype=torch.float32),
+                               torch.zeros(loss_bins, device=dev, dtype=torch.int32))
+        self.loss_bins = loss_bins
         self.module = model
         # seed: the training draws come from the counter-based generator (csrc/rng.h) keyed by a global sample index
         # (step_sample_ids), not from torch's device generator; None (default): as before
@@ -261,6 +282,7 @@ class Trainer:
         self._pool = None           # the graphs' shared private memory pool
         self._scal = None           # device {lr, 1-b1^t, 1-b2^t}
         self._last_graph = None
+        self._loss_key = None       # ViewFusion.loss_key() the kept graphs were captured under
         self._graph_epoch = None    # FusedAdam.graph_epoch the kept graphs were captured under (None: none captured)
         self.graph_steps = 0        # iterations (accum_steps > 1: micro-batches) that ran as a replay (diagnostics / tests)
         self.world = world
@@ -281,6 +303,23 @@ class Trainer:
         """Global L2 norm of the last step's (averaged) gradients before clipping: a 0-d device tensor that every
         step rewrites, never a sync.  None without max_grad_norm."""
         return getattr(self.opt, "grad_norm", None)
+
+    def loss_by_level(self, reset=False):
+        """-> (mean_loss (K,), count (K,) int32): the per-sample training loss by noise level since the last reset -- bin k
+        holds the samples with min(K - 1, int(gamma K)) == k, gamma the sample's continuous level, so bin 0 is the noisiest.
+        The loss is the UNWEIGHTED per-sample mean of the penalty (what `model.last_sample_loss` shows), so curves
+        compare across weightings; a bin without samples gives NaN.  Device tensors, computed without a host sync:
+        reading them is the caller's sync.  reset=True zeroes the accumulators afterwards (the sums are fp32: reset at
+        every logging interval of a long run).  Rank-local under every reducer: each rank bins the samples it ran itself,
+        and nothing is exchanged -- reduce the sums and counts across ranks yourself if you need the global curve."""
+        if self.loss_bins is None:
+            raise ValueError("loss_by_level needs Trainer(loss_bins=K)")
+        bin_sum, bin_cnt = self.module.loss_hist
+        mean, count = bin_sum / bin_cnt.to(torch.float32), bin_cnt.clone()
+        if reset:
+            bin_sum.zero_()
+            bin_cnt.zero_()
+        return mean, count
 
     def ema_state_dict(self):
         return self.opt.ema_state_dict()
@@ -447,6 +486,10 @@ class Trainer:
         e.accum = None if acc is None else self.opt.accum_end(acc)
         self._graph_epoch = self.opt.graph_epoch if split else adam["epoch"]
         e.loss, e.graph = loss.detach(), g
+        # the loss-option kernels' per-sample outputs are static buffers of this graph (None on the default path)
+        e.sample = None
+        if getattr(self.module, "_loss", None) is not None or getattr(self.module, "loss_hist", None) is not None:
+            e.sample = (self.module.last_sample_loss, self.module.last_level)
         e.grads = list(grads)
         # what the captured launches address besides the graph's own pool
         e.keep = (fix, tables, offs, getattr(self.module, "gammas", None))
@@ -462,6 +505,8 @@ class Trainer:
         for k, dst in e.inputs.items():
             src = extra[k] if k in extra else batch[k]
             dst.copy_(src.reshape(dst.shape), non_blocking=True)
+        if e.sample is not None:
+            self.module.last_sample_loss, self.module.last_level = e.sample
         if accum is not None:                          # a micro-batch: its gradient goes into the accumulators, which
             self.opt.accum_tick(e.accum, *accum)       # the optimizer step after the last one reads and leaves in .grad
             e.graph.replay()
@@ -539,6 +584,15 @@ class Trainer:
     def _run(self, batch, extra, accum=None):
         """Forward, backward and the optimizer step on `batch` as a replay or launch by launch; accum = (weight, first):
         `batch` is a micro-batch, and in place of the optimizer step its gradient is added into the accumulators."""
+        loss_key = getattr(self.module, "loss_key", None)
+        loss_key = None if loss_key is None else loss_key()
+        if loss_key != self._loss_key:
+            # the objective (model.set_loss) or the histogram changed: both are constants of the captured launches, so
+            # the captured steps are dropped (and their memory freed); every geometry is captured again after its eager
+            # sightings.  A replay never keeps the old objective.
+            if self._graphs:
+                self._drop_graphs()
+            self._loss_key = loss_key
         key, vc = self._graph_key(batch, extra) or (None, None)
         if key is not None and accum is None and self._graph_epoch is not None and \
                 self.opt.graph_epoch != self._graph_epoch:      # (a micro-batch graph addresses no Adam state)

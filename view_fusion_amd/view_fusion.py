@@ -19,6 +19,9 @@ do -- can be compared against the CPU oracle; `sample()` is an alias of `generat
 injected from the counter-based generator of csrc/rng.h instead of torch's device generator: a draw is then a function
 of (seed, sample id, purpose, step, element) alone -- the same for a sample whatever its row, its batch or its rank --
 and tests/rng_ref.py can restate it on the CPU.
+
+`set_loss(...)` (default: the reference's unweighted MSE, untouched) selects the training objective's penalty (mse / l1 /
+huber) and a per-sample weight of the noise level (min-SNR, P2); see csrc/loss_weight.h.
 """
 import torch
 from torch import nn
@@ -33,6 +36,48 @@ class ViewFusion(nn.Module):
         self.beta_schedule = beta_schedule
         self.weighting_train = weighting_train
         self.weighting_inference = weighting_inference
+        # the training objective (set_loss) and what the optional loss kernels hand back: plain attributes, no buffers
+        self._loss = None                 # None: the reference's unweighted MSE through compose_mse_loss
+        self.loss_hist = None             # (bin_sum, bin_cnt) device accumulators, attached by train.Trainer(loss_bins=)
+        self.last_sample_loss = self.last_level = None
+
+    # -- training objective -------------------------------------------------------------------
+    def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
+        """The training objective of forward(): loss = mean_b w_b mean_i rho(noise_hat - noise)  (csrc/loss_weight.h).
+
+        penalty: "mse" (d^2), "l1" (|d|) or "huber" (F.huber_loss with `delta`).
+        weighting: None (w = 1), "min_snr" (w = min(SNR, snr_gamma) / SNR, Hang et al.) or "p2" (w = (p2_k + SNR)^-p2_gamma,
+        Choi et al.), with SNR = gamma / (1 - gamma) of the sample's own continuous level.  No renormalisation by sum w.
+        The defaults ARE the reference's loss, and with them forward() runs exactly the launches it ran before.  Anything
+        else runs the loss-option kernels (the same launch count) and forward() then also leaves `last_sample_loss`
+        (B,), the unweighted per-sample loss, and `last_level` (B,): detached device tensors, valid until the next
+        forward.  Stores no parameter or buffer.  A Trainer drops its captured steps when these settings change."""
+        from .ops.diffusion import PENALTIES, WEIGHT_KINDS
+        if penalty not in PENALTIES:
+            raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
+        if weighting not in WEIGHT_KINDS:
+            raise ValueError(f"unknown loss weighting {weighting!r}: one of None, 'min_snr', 'p2'")
+        delta, snr_gamma, p2_k, p2_gamma = float(delta), float(snr_gamma), float(p2_k), float(p2_gamma)
+        if not delta > 0:
+            raise ValueError(f"delta must be positive, got {delta}")
+        if not snr_gamma > 0:
+            raise ValueError(f"snr_gamma must be positive, got {snr_gamma}")
+        if not p2_k >= 0:
+            raise ValueError(f"p2_k must be non-negative, got {p2_k}")
+        if p2_gamma != p2_gamma:
+            raise ValueError("p2_gamma must be a number")
+        kind = None if weighting in (None, "none") else weighting
+        a, b = (snr_gamma, 0.0) if kind == "min_snr" else ((p2_k, p2_gamma) if kind == "p2" else (0.0, 0.0))
+        if penalty == "mse" and kind is None:
+            self._loss = None
+        else:
+            self._loss = dict(penalty=penalty, delta=delta if penalty == "huber" else 1.0, weight_kind=kind, a=a, b=b)
+
+    def loss_key(self):
+        """What a captured training step depends on besides its inputs: the objective and the attached histogram."""
+        h = self.loss_hist
+        return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
+                None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()))
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -255,4 +300,9 @@ class ViewFusion(nn.Module):
         off, S, _ = ops.view_offsets(view_count, dev)
         x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S)
         out = self.denoise_fn(x, angle_s, level_s)
-        return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
+        if self._loss is None and self.loss_hist is None:
+            return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
+        loss, sample_loss = ops.compose_loss(out, noise, off, b, bool(self.weighting_train), level,
+                                             **(self._loss or {}), hist=self.loss_hist)
+        self.last_sample_loss, self.last_level = sample_loss.detach(), level.detach()
+        return loss
