@@ -224,6 +224,9 @@ int vf_bgemm(const float* A, const float* B, float* C, const float* bias /*[N]|N
  * P [S][L][L] (softmax probabilities, saved for backward).  L in {64,256}, C % 32 == 0.  Other L <= 4096 run
  * vf_bgemm + vf_softmax_fwd / _bwd on materialised S x L x L scores (cols <= 4096); L > 4096 vf_attn_stream_*. */
 int vf_attention_fwd(const float* qkv, float* out, float* P /*|NULL*/, int S, int C, int L, void* stream);
+/* the forward kernel vf_attention_fwd launches at this shape (the launcher switches on it): 1 16-query, 2 32-query,
+ * 3 key-split, 4 128-query; 0 where the shape is refused */
+int vf_attention_fwd_kernel(int S, int C, int L);
 /* attention backward (autograd of unet.py:267-274), L = 256, C % 32 == 0, first of three launches:
  * dS = P o (dP - rowsum(P o dP)) with dP = dO^T V computed in the kernel, and dQ = K dS^T / sqrt(C) -> q third of dqkv;
  * qkv, dqkv [S][3C][L], dO [S][C][L], P, dS [S][L][L] (dS must not alias P).  dV and dK stay vf_bgemm calls. */
@@ -233,12 +236,12 @@ int vf_attention_dscore(const float* qkv, const float* dO, const float* P, float
 int vf_attention_dvdk(const float* qkv, const float* dO, const float* P, const float* dS, float* dqkv, int S, int C, int L,
                       void* stream);
 /* streaming attention (unet.py:248-277 core, csrc/attention_stream.hip), any L >= 1, 1 <= C <= 512, no L x L buffer:
- * online softmax over key blocks.  qkv [S][3C][L] -> out [S][C][L]; lse [S][L] = per-query log-sum-exp of the scaled
- * scores (training) or NULL.  ops.attention takes this route for L > 4096. */
-int vf_attn_stream_fwd(const float* qkv, float* out, float* lse /*|NULL*/, int S, int C, int L, void* stream);
-/* ... its backward (FlashAttention-2, deterministic, no float atomics): the probabilities recomputed from lse;
+ * online softmax over key blocks.  qkv [S][3C][L] -> out [S][C][L]; rowstat [S][2][L] = per-query softmax statistics
+ * (log2 e / sqrt(C) x the largest score, 1 / sum; training) or NULL.  ops.attention takes this route for L > 4096. */
+int vf_attn_stream_fwd(const float* qkv, float* out, float* rowstat /*|NULL*/, int S, int C, int L, void* stream);
+/* ... its backward (FlashAttention-2, deterministic, no float atomics): the probabilities recomputed from rowstat;
  * delta [S][L] workspace (rowsum(dO o out)); writes all of dqkv [S][3C][L].  Three launches: delta, dK + dV, dQ. */
-int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* lse, float* delta,
+int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* rowstat, float* delta,
                        float* dqkv, int S, int C, int L, void* stream);
 int vf_softmax_fwd(const float* x, float* y, int rows, int cols, void* stream);
 int vf_softmax_bwd(const float* y, const float* dy, float* dx, int rows, int cols, void* stream);

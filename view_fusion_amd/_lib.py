@@ -79,6 +79,7 @@ SIGNATURES = {
     "vf_time_affine_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vf_bgemm": [_P, _P, _P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _L, _L, _F, _F, _P],
     "vf_attention_fwd": [_P, _P, _P, _I, _I, _I, _P],
+    "vf_attention_fwd_kernel": [_I, _I, _I],
     "vf_attention_dscore": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vf_attention_dvdk": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vf_attn_stream_fwd": [_P, _P, _P, _I, _I, _I, _P],

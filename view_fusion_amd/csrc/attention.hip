@@ -898,13 +898,10 @@ __global__ __launch_bounds__(256, 5) void attn_bwd_dvdk_kernel(const float* __re
 
 extern "C" {
 
-// qkv [S][3C][L] (q | k | v channel thirds), out [S][C][L], P [S][L][L] or NULL.
-// L in {64, 256, 1024(no)}: spatial 8x8 or 16x16; C multiple of 32.
-int vf_attention_fwd(const float* qkv, float* out, float* P, int S, int C, int L, void* stream) {
-    if (S <= 0) return 0;
-    if (C % 32 != 0) return (int)hipErrorInvalidValue;
-    const float alpha = 1.0f / sqrtf((float)C);
-    hipStream_t st = (hipStream_t)stream;
+// The forward kernel vf_attention_fwd launches at this shape: 1 the 16-query kernel, 2 the 32-query kernel, 3 the
+// key-split kernel, 4 the 128-query kernel; 0 where it refuses the shape.  The launcher itself switches on this.
+int vf_attention_fwd_kernel(int S, int C, int L) {
+    if (S <= 0 || C <= 0 || C % 32 != 0) return 0;
     // L = 256 (round 5; profiles/r05_attention_q32.md has the sweep):
     //   S <= 16 (the sampler)          16-query kernel: 16 S workgroups
     //   otherwise                      32-query kernel (8 S workgroups of four waves, three per compute unit) or the
@@ -916,17 +913,32 @@ int vf_attention_fwd(const float* qkv, float* out, float* P, int S, int C, int L
     static const bool q16 = !(getenv("VF_ATTN_Q16") && getenv("VF_ATTN_Q16")[0] == '0');
     static const bool q32 = !(getenv("VF_ATTN_Q32") && getenv("VF_ATTN_Q32")[0] == '0');
     const bool q32_wins = 177 * ((S + 31) / 32) + 30 < 660 * ((S + 127) / 128);
-    if (L == 256 && S <= 16 && C % 64 == 0 && q16)
+    if ((L == 256 || L == 64) && S <= 16 && C % 64 == 0 && q16) return 1;
+    if (L == 256 && q32 && q32_wins) return 2;
+    if (L == 256 && S <= 52 && !q32) return 3;
+    if (L == 256) return 4;
+    return L == 64 ? 3 : 0;
+}
+
+// qkv [S][3C][L] (q | k | v channel thirds), out [S][C][L], P [S][L][L] or NULL.
+// L in {64, 256, 1024(no)}: spatial 8x8 or 16x16; C multiple of 32.
+int vf_attention_fwd(const float* qkv, float* out, float* P, int S, int C, int L, void* stream) {
+    if (S <= 0) return 0;
+    if (C % 32 != 0) return (int)hipErrorInvalidValue;
+    const float alpha = 1.0f / sqrtf((float)C);
+    hipStream_t st = (hipStream_t)stream;
+    const int kernel = vf_attention_fwd_kernel(S, C, L);
+    if (kernel == 1 && L == 256)
         hipLaunchKernelGGL(attn_fwd_q16_kernel<256>, dim3(16, S), dim3(512), 0, st, qkv, out, P, C, alpha);
-    else if (L == 64 && S <= 16 && C % 64 == 0 && q16)
+    else if (kernel == 1)
         hipLaunchKernelGGL(attn_fwd_q16_kernel<64>, dim3(4, S), dim3(128), 0, st, qkv, out, P, C, alpha);
-    else if (L == 256 && q32 && q32_wins)
+    else if (kernel == 2)
         hipLaunchKernelGGL(attn_fwd_q32_kernel<false>, dim3(8 * S), dim3(256), 0, st, qkv, out, P, C, alpha, S, nullptr, nullptr);
-    else if (L == 256 && S <= 52 && !q32)
+    else if (kernel == 3 && L == 256)
         hipLaunchKernelGGL(attn_fwd_split_kernel<256>, dim3(8, S), dim3(512), 0, st, qkv, out, P, C, alpha);
-    else if (L == 256)
+    else if (kernel == 4)
         hipLaunchKernelGGL(attn_fwd_kh_kernel, dim3(2, S), dim3(512), 0, st, qkv, out, P, C, alpha);
-    else if (L == 64)
+    else if (kernel == 3)
         hipLaunchKernelGGL(attn_fwd_split_kernel<64>, dim3(2, S), dim3(128), 0, st, qkv, out, P, C, alpha);
     else
         return (int)hipErrorInvalidValue;

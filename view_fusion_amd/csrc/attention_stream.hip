@@ -1,8 +1,15 @@
 // Streaming single-head spatial self-attention, any L (reference model/unet.py:248-277, the einsum + softmax core):
 //   O[c][i] = sum_j V[c][j] * softmax_j(alpha * sum_c' Q[c'][i] K[c'][j]),  alpha = 1/sqrt(C),  qkv [S][3C][L]
 // The L x L score matrix is never written: keys and values are streamed in blocks with an online softmax, and the
-// backward recomputes the probabilities from the forward's per-query log-sum-exp (FlashAttention-2).  Memory is O(L)
-// per view (lse and delta, S x L floats each); the materialised path (attention.py, L <= 4096) needs S x L x L twice.
+// backward recomputes the probabilities from the forward's per-query softmax statistics (FlashAttention-2).  Memory is
+// O(L) per view (rowstat 2 x S x L floats, delta S x L); the materialised path (attention.py, L <= 4096) needs
+// S x L x L twice.
+//
+// The statistics are kept as the pair (c2 max, 1 / sum), c2 = alpha log2 e, not as one log-sum-exp: the backward then
+// forms p = exp2(c2 s - c2 max) / sum from the same score s (same MFMA order, accumulator 0) and the same two numbers
+// as the forward.  A single lse = alpha max + ln sum carried as the initial accumulator of S rounds every partial sum at
+// the magnitude of the largest score: with scores of +-350 (C = 64: raw 2800, ulp 2.4e-4) over C / 2 MFMA steps that
+// is about 5e-5 in p, which missed the stated d(qkv) tolerance on peaked inputs.
 //
 // Orientation (all kernels), v_mfma_f32_32x32x2_f32, accumulator register r of lane (li = lane & 31, lh = lane >> 5)
 // = row (r & 3) + 8 (r >> 2) + 4 lh, column li:
@@ -10,8 +17,7 @@
 //                 (running max and sum, the rescale of the O accumulator) is per lane; O = V P^T takes P in the
 //                 registers' row order with V fetched in that order (one 4-key run per four MFMAs), as attention.hip.
 //   dK / dV       S = Q^T K: the key is on the lane ("key on the lane"), the queries sit in the registers; the
-//                 row constants -lse/alpha and -delta are the initial accumulators of S and dP, so p = exp2(c2 s')
-//                 and dS = p o dP' need no subtraction.
+//                 row constant -delta is the initial accumulator of dP, so dS = p o dP' needs no subtraction.
 //
 // Tiling: a workgroup is 4 waves.  Forward and dQ: one view x 32 queries, streaming 128 keys per iteration, one 32-key
 // sub-block per wave for the score product (sum over all C); the probabilities (dS for dQ) go through LDS, and the
@@ -31,7 +37,7 @@
 // ordered hand-off of dQ tiles between the key-block workgroups of a view, needs all of a view's L / 32 workgroups
 // resident together (512 at L = 16384, more than the chip holds with S > 1) and bounded spins; the recompute needs
 // neither, has no float atomics, and replays bit-equal.
-//   attn_stream_fwd_kernel<NT>    O (and lse = alpha max + ln sum when lse != NULL)
+//   attn_stream_fwd_kernel<NT>    O (and rowstat = (c2 max, 1 / sum) when rowstat != NULL)
 //   attn_stream_delta_kernel      delta[i] = sum_c dO[c][i] O[c][i]
 //   attn_stream_dkv_kernel<NT>    dK, dV -> the k and v thirds of dqkv
 //   attn_stream_dq_kernel<NT>     dQ -> the q third of dqkv
@@ -140,8 +146,8 @@ __device__ __forceinline__ void block_ids(int& blk, int& b) {
 
 template <int NT>
 __global__ __launch_bounds__(256) void attn_stream_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ out,
-                                                              float* __restrict__ lse, int C, int L, float alpha,
-                                                              int vec) {
+                                                              float* __restrict__ rowstat, int C, int L,
+                                                              float alpha, int vec) {
     __shared__ __attribute__((aligned(16))) float pl[2][4][SQ][SPAD];   // P [buf][key sub-block][query][key]
     __shared__ float stat[2][2][4][SQ];                                  // [buf][max | sum][key sub-block][query]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 31, lh = lane >> 5;
@@ -217,7 +223,10 @@ __global__ __launch_bounds__(256) void attn_stream_fwd_kernel(const float* __res
             if (c < C) out[((size_t)b * C + c) * L + qi] = o[t][r] * inv;
         }
     }
-    if (lse && w == 0 && lh == 0) lse[(size_t)b * L + qi] = alpha * m + logf(l);
+    if (rowstat && w == 0 && lh == 0) {
+        rowstat[(size_t)(2 * b) * L + qi] = m * c2;
+        rowstat[(size_t)(2 * b + 1) * L + qi] = inv;
+    }
 }
 
 __global__ __launch_bounds__(256) void attn_stream_delta_kernel(const float* __restrict__ out,
@@ -234,7 +243,7 @@ __global__ __launch_bounds__(256) void attn_stream_delta_kernel(const float* __r
 template <int NT>
 __global__ __launch_bounds__(256) void attn_stream_dkv_kernel(const float* __restrict__ qkv,
                                                               const float* __restrict__ dO,
-                                                              const float* __restrict__ lse,
+                                                              const float* __restrict__ rowstat,
                                                               const float* __restrict__ delta,
                                                               float* __restrict__ dqkv, int C, int L, float alpha,
                                                               int vec) {
@@ -247,11 +256,12 @@ __global__ __launch_bounds__(256) void attn_stream_dkv_kernel(const float* __res
     const float* kp = qp + CL;
     const float* vp = kp + CL;
     const float* gp = dO + (size_t)b * CL;
-    const float* lp = lse + (size_t)b * L;
+    const float* mp = rowstat + (size_t)(2 * b) * L;     // c2 max
+    const float* ip = mp + L;                            // 1 / sum
     const float* dp = delta + (size_t)b * L;
     const int kj = kblk * SQ + li;
     const bool kok = kj < L;
-    const float c2 = alpha * 1.44269504088896341f, ia = 1.0f / alpha;
+    const float c2 = alpha * 1.44269504088896341f;
     const float one[4] = {1.f, 1.f, 1.f, 1.f};
 
     f32x16 dk[NT], dv[NT];
@@ -263,18 +273,17 @@ __global__ __launch_bounds__(256) void attn_stream_dkv_kernel(const float* __res
         const int qa = q0 + li;                          // its A-operand row
         f32x16 s, dp_;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {                   // row constants of query q0 + crow(r)
+        for (int r = 0; r < 16; ++r) {                   // row constant of query q0 + crow(r)
             const int q = q0 + crow(r, lh);
-            const bool ok = q < L;
-            const int qc = ok ? q : L - 1;
-            s[r] = ok ? -lp[qc] * ia : -INFINITY;
-            dp_[r] = ok ? -dp[qc] : 0.f;
+            dp_[r] = q < L ? -dp[q < L ? q : L - 1] : 0.f;
         }
-        s = chan_mfma(qp + (qa < L ? qa : 0), qa < L, kp + (kok ? kj : 0), kok, C, L, lh, s);
+        s = chan_mfma(qp + (qa < L ? qa : 0), qa < L, kp + (kok ? kj : 0), kok, C, L, lh, (f32x16){0});
         dp_ = chan_mfma(gp + (qa < L ? qa : 0), qa < L, vp + (kok ? kj : 0), kok, C, L, lh, dp_);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float p = kok ? __builtin_amdgcn_exp2f(s[r] * c2) : 0.f;
+            const int q = q0 + crow(r, lh);
+            const int qc = q < L ? q : L - 1;
+            const float p = kok && q < L ? __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mp[qc])) * ip[qc] : 0.f;
             s[r] = p;
             dp_[r] *= p;                                 // dS = P o (dP - delta)
         }
@@ -304,7 +313,7 @@ __global__ __launch_bounds__(256) void attn_stream_dkv_kernel(const float* __res
 template <int NT>
 __global__ __launch_bounds__(256) void attn_stream_dq_kernel(const float* __restrict__ qkv,
                                                              const float* __restrict__ dO,
-                                                             const float* __restrict__ lse,
+                                                             const float* __restrict__ rowstat,
                                                              const float* __restrict__ delta,
                                                              float* __restrict__ dqkv, int C, int L, float alpha,
                                                              int vec) {
@@ -321,7 +330,8 @@ __global__ __launch_bounds__(256) void attn_stream_dq_kernel(const float* __rest
     const bool qok = qi < L;
     const int qc = qok ? qi : 0;
     const float c2 = alpha * 1.44269504088896341f;
-    const float s0 = qok ? -lse[(size_t)b * L + qc] / alpha : 0.f;
+    const float mc = qok ? rowstat[(size_t)(2 * b) * L + qc] : 0.f;          // c2 max
+    const float il = qok ? rowstat[(size_t)(2 * b + 1) * L + qc] : 0.f;      // 1 / sum
     const float d0 = qok ? -delta[(size_t)b * L + qc] : 0.f;
     const float one[4] = {1.f, 1.f, 1.f, 1.f};
 
@@ -334,15 +344,12 @@ __global__ __launch_bounds__(256) void attn_stream_dq_kernel(const float* __rest
         const int kj = k0 + li;
         f32x16 s, dp_;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            s[r] = s0;
-            dp_[r] = d0;
-        }
-        s = chan_mfma(kp + (kj < L ? kj : 0), kj < L, qp + qc, qok, C, L, lh, s);
+        for (int r = 0; r < 16; ++r) dp_[r] = d0;
+        s = chan_mfma(kp + (kj < L ? kj : 0), kj < L, qp + qc, qok, C, L, lh, (f32x16){0});
         dp_ = chan_mfma(vp + (kj < L ? kj : 0), kj < L, gp + qc, qok, C, L, lh, dp_);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float p = qok && k0 + crow(r, lh) < L ? __builtin_amdgcn_exp2f(s[r] * c2) : 0.f;
+            const float p = qok && k0 + crow(r, lh) < L ? __builtin_amdgcn_exp2f(fmaf(s[r], c2, -mc)) * il : 0.f;
             dp_[r] *= p;
         }
         put_tile(pl[buf][w], dp_, li, lh);
@@ -371,8 +378,8 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" {
 
-// qkv [S][3C][L] -> out [S][C][L]; lse [S][L] (training) or NULL.  Any L >= 1, 1 <= C <= 512.
-int vf_attn_stream_fwd(const float* qkv, float* out, float* lse, int S, int C, int L, void* stream) {
+// qkv [S][3C][L] -> out [S][C][L]; rowstat [S][2][L] (training) or NULL.  Any L >= 1, 1 <= C <= 512.
+int vf_attn_stream_fwd(const float* qkv, float* out, float* rowstat, int S, int C, int L, void* stream) {
     if (S <= 0 || L <= 0) return 0;
     if (C <= 0 || C > 512) return (int)hipErrorInvalidValue;
     const float alpha = 1.0f / sqrtf((float)C);
@@ -380,17 +387,18 @@ int vf_attn_stream_fwd(const float* qkv, float* out, float* lse, int S, int C, i
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((L + SQ - 1) / SQ, S);
     switch (tiles_per_wave(C)) {
-        case 1: hipLaunchKernelGGL(attn_stream_fwd_kernel<1>, grid, dim3(256), 0, st, qkv, out, lse, C, L, alpha, vec); break;
-        case 2: hipLaunchKernelGGL(attn_stream_fwd_kernel<2>, grid, dim3(256), 0, st, qkv, out, lse, C, L, alpha, vec); break;
-        case 3: hipLaunchKernelGGL(attn_stream_fwd_kernel<3>, grid, dim3(256), 0, st, qkv, out, lse, C, L, alpha, vec); break;
-        default: hipLaunchKernelGGL(attn_stream_fwd_kernel<4>, grid, dim3(256), 0, st, qkv, out, lse, C, L, alpha, vec); break;
+        case 1: hipLaunchKernelGGL(attn_stream_fwd_kernel<1>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
+        case 2: hipLaunchKernelGGL(attn_stream_fwd_kernel<2>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
+        case 3: hipLaunchKernelGGL(attn_stream_fwd_kernel<3>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
+        default: hipLaunchKernelGGL(attn_stream_fwd_kernel<4>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
     }
     VF_RETURN_LAST_ERROR();
 }
 
-// qkv, dqkv [S][3C][L]; out, dO [S][C][L]; lse [S][L] from vf_attn_stream_fwd; delta [S][L] workspace.  Three launches:
+// qkv, dqkv [S][3C][L]; out, dO [S][C][L]; rowstat [S][2][L] from vf_attn_stream_fwd; delta [S][L] workspace.  Three
+// launches:
 // delta, dK + dV, dQ.  Every element of dqkv is written.
-int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* lse, float* delta,
+int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* rowstat, float* delta,
                        float* dqkv, int S, int C, int L, void* stream) {
     if (S <= 0 || L <= 0) return 0;
     if (C <= 0 || C > 512) return (int)hipErrorInvalidValue;
@@ -400,8 +408,8 @@ int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, cons
     hipLaunchKernelGGL(attn_stream_delta_kernel, dim3((L + 255) / 256, S), dim3(256), 0, st, out, dO, delta, C, L);
     const dim3 grid((L + SQ - 1) / SQ, S);
 #define VF_AS_BWD(NT_)                                                                                                \
-    hipLaunchKernelGGL(attn_stream_dkv_kernel<NT_>, grid, dim3(256), 0, st, qkv, dO, lse, delta, dqkv, C, L, alpha, vec); \
-    hipLaunchKernelGGL(attn_stream_dq_kernel<NT_>, grid, dim3(256), 0, st, qkv, dO, lse, delta, dqkv, C, L, alpha, vec);
+    hipLaunchKernelGGL(attn_stream_dkv_kernel<NT_>, grid, dim3(256), 0, st, qkv, dO, rowstat, delta, dqkv, C, L, alpha, vec); \
+    hipLaunchKernelGGL(attn_stream_dq_kernel<NT_>, grid, dim3(256), 0, st, qkv, dO, rowstat, delta, dqkv, C, L, alpha, vec);
     switch (tiles_per_wave(C)) {
         case 1: VF_AS_BWD(1) break;
         case 2: VF_AS_BWD(2) break;

@@ -48,7 +48,8 @@ struct SmallArgs {
     const float* ig;                   // gamma, beta of the input GroupNorm
     const float* ib;
     int icpg, isilu;                   // channels per group
-    float iinv, ieps;                  // 1 / (2^24 * icpg * H * W)
+    double iinv;                       // 1 / (2^24 * icpg * H * W)
+    float ieps;
     int up;                            // 3x3 only: x is stored at half size, nearest-x2-upsampled on read (Upsample conv, unet.py:185-190)
     const float* wp;                   // 3x3 only: the weights in the packed order of vf_conv_small_pack, or null (unpacked OIHW)
 };
@@ -56,16 +57,19 @@ struct SmallArgs {
 constexpr float SM_FIX = 16777216.f;   // 2^24: fixed-point unit of the statistics
 
 // mean, rstd * gamma, beta of channel c of view s from the producer's integer sums (biased variance, eps inside the
-// square root, like nn.GroupNorm; E[x^2] - mean^2 in fp32 on exactly accumulated sums)
+// square root, like nn.GroupNorm).  E[x^2] - mean^2 is formed in DOUBLE on the exactly accumulated sums: behind a
+// residual add the group mean is ~100 standard deviations, where the fp32 difference (and the fp32 1 / n, which scales
+// the two terms differently when n is no power of two) loses 6e-4 of the variance; in double the cancellation costs
+// 1e-4 * 2^-53 / 2^-24 of it.
 __device__ __forceinline__ void small_gn_coef(const SmallArgs& a, int s, int c, float& mean, float& scale, float& beta) {
     const int g0 = (c / a.icpg) * a.icpg;
     const unsigned long long* p = a.ist + ((size_t)s * a.Cin + g0) * 2;
     long long s1 = 0, s2 = 0;
     for (int i = 0; i < a.icpg; ++i) { s1 += (long long)p[2 * i]; s2 += (long long)p[2 * i + 1]; }
-    mean = (float)((double)s1 * (double)a.iinv);
-    const float ex2 = (float)((double)s2 * (double)a.iinv);
-    const float var = fmaxf(ex2 - mean * mean, 0.f);
-    scale = a.ig[c] / sqrtf(var + a.ieps);
+    const double m = (double)s1 * a.iinv;
+    const double var = fmax((double)s2 * a.iinv - m * m, 0.0);
+    mean = (float)m;
+    scale = a.ig[c] / sqrtf((float)var + a.ieps);
     beta = a.ib[c];
 }
 __device__ __forceinline__ float small_gn_apply(float x, float mean, float scale, float beta, int silu) {
@@ -125,13 +129,16 @@ __device__ __forceinline__ void small_epilogue(const SmallArgs& a, float* red, c
     }
     if (a.ost && tid < TCO * SM_PX) {              // (whole waves: TCO * 16 is a multiple of 64)
         // sums of this tile's 16 pixels per channel (16 consecutive lanes), then two integer atomics per channel
-        float s1 = v, s2 = v * v;
+        // (in double: v * v is exact and so, to 2^-53, are the 16-term sums -- the only rounding is the one to the 2^-24
+        //  unit.  Summed in fp32 the squares of a tile lose 2^-24 of THEIR size, which at mean / std = 100 is 6e-4 of the
+        //  variance the consumer forms from them)
+        double s1 = (double)v, s2 = (double)v * (double)v;
 #pragma unroll
         for (int o = 1; o < 16; o <<= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
         if ((tid & 15) == 0 && ep.o != ~(size_t)0) {
             unsigned long long* d = a.ost + (ep.o >> (2 * a.logW)) * 2;      // ep.o / HW = s * Cout + co
-            atomicAdd(d, (unsigned long long)__float2ll_rn(s1 * SM_FIX));
-            atomicAdd(d + 1, (unsigned long long)__float2ll_rn(s2 * SM_FIX));
+            atomicAdd(d, (unsigned long long)__double2ll_rn(s1 * (double)SM_FIX));
+            atomicAdd(d + 1, (unsigned long long)__double2ll_rn(s2 * (double)SM_FIX));
         }
     }
 }
@@ -494,7 +501,7 @@ static int conv_small_launch(const float* x, const float* x2, int C1, const floa
     a.rn = rx ? ((((rC + 7) / 8) + 15) & ~15) : 0;
     a.ost = gn.ost; a.ist = gn.ist; a.ig = gn.ig; a.ib = gn.ib;
     a.icpg = gn.ist ? Cin / gn.groups : 1; a.isilu = gn.silu; a.ieps = gn.eps;
-    a.iinv = gn.ist ? (float)(1.0 / (16777216.0 * (double)a.icpg * (double)H * (double)W)) : 0.f;
+    a.iinv = gn.ist ? 1.0 / (16777216.0 * (double)a.icpg * (double)H * (double)W) : 0.0;
     a.up = mode == 2 ? 1 : 0;
     a.wp = KS == 3 ? gn.wp : nullptr;
     hipStream_t st = (hipStream_t)stream;

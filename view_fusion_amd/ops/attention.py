@@ -90,23 +90,24 @@ def attention_route(C, L):
 
 class _AttentionStreamFn(torch.autograd.Function):
     """The same attention without any L x L buffer (csrc/attention_stream.hip): online softmax over key blocks, the
-    backward recomputes the probabilities from the saved per-query log-sum-exp.  Training saves (qkv, out, lse)."""
+    backward recomputes the probabilities from the saved per-query (scaled maximum, 1 / sum).  Training saves (qkv, out,
+    rowstat)."""
 
     @staticmethod
-    def forward(ctx, qkv, need_lse):
+    def forward(ctx, qkv, need_stat):
         _check(qkv)
         S, C3, H, W = qkv.shape
         C, L = C3 // 3, H * W
         out = torch.empty(S, C, H, W, device=qkv.device, dtype=torch.float32)
-        lse = torch.empty(S, L, device=qkv.device, dtype=torch.float32) if need_lse else None
-        _launch("attn_fwd", 4.0 * S * L * L * C, "vf_attn_stream_fwd", _ptr(qkv), _ptr(out), _ptr(lse), S, C, L,
-                _stream(), nbytes=4.0 * (qkv.numel() + out.numel() + (S * L if need_lse else 0)))
-        ctx.save_for_backward(qkv, out, lse)
+        rowstat = torch.empty(S, 2, L, device=qkv.device, dtype=torch.float32) if need_stat else None
+        _launch("attn_fwd", 4.0 * S * L * L * C, "vf_attn_stream_fwd", _ptr(qkv), _ptr(out), _ptr(rowstat), S, C, L,
+                _stream(), nbytes=4.0 * (qkv.numel() + out.numel() + (2 * S * L if need_stat else 0)))
+        ctx.save_for_backward(qkv, out, rowstat)
         return out
 
     @staticmethod
     def backward(ctx, dO):
-        qkv, out, lse = ctx.saved_tensors
+        qkv, out, rowstat = ctx.saved_tensors
         dO = _c(dO)
         S, C3, H, W = qkv.shape
         C, L = C3 // 3, H * W
@@ -114,9 +115,9 @@ class _AttentionStreamFn(torch.autograd.Function):
         delta = torch.empty(S, L, device=qkv.device, dtype=torch.float32)
         # executed FLOPs: 8 L^2 C per view in the dK / dV kernel (S, dP, dV, dK) + 6 L^2 C in the dQ kernel (S and dP
         # recomputed, dQ)
-        _launch("attn_bwd", 14.0 * S * L * L * C, "vf_attn_stream_bwd", _ptr(qkv), _ptr(out), _ptr(dO), _ptr(lse),
+        _launch("attn_bwd", 14.0 * S * L * L * C, "vf_attn_stream_bwd", _ptr(qkv), _ptr(out), _ptr(dO), _ptr(rowstat),
                 _ptr(delta), _ptr(dqkv), S, C, L, _stream(),
-                nbytes=4.0 * (2 * qkv.numel() + 2 * out.numel() + 2 * S * L))
+                nbytes=4.0 * (2 * qkv.numel() + 2 * out.numel() + 3 * S * L))
         return dqkv, None
 
 
