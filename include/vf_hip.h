@@ -331,11 +331,51 @@ int vf_sampler_step_rng(const float* unet_out, const int* off, const float* y_t,
                         const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
                         float* y0_prev /*|NULL*/, float* y_next, float* weights /*|NULL*/, int B, int Cout, int HW,
                         int maxV, int weighting, void* stream);
+/* ---- classifier-free guidance (csrc/diffusion.hip holds the definition): conditioning dropout in training, an
+ *      unconditional ("null") row per sample and a guided noise eps = g eps_c + (1 - g) eps_u in sampling. ---- */
+/* vf_stack_views with drop (DEVICE uint8 [B] | NULL: the conditioning half of every row of a sample with drop[b] != 0
+ * is zeros, y_cond is not read for it) and null_rows (!= 0: S + B rows are written; row S + b = [ 0 | y_t[b] ] with
+ * level[b], angle[b]).  x [S (+ B)][Cc+3][HW], level_s / angle_s [S (+ B)].  copy_cond == 0 touches no conditioning half.
+ * With null_rows every sample must have a real row (S >= B, else hipErrorInvalidValue); without, any S as above. */
+int vf_stack_views_cfg(const float* y_cond, const float* y_t, const float* noise /*|NULL*/, const float* level,
+                       const float* angle, const int* off /*[B+1]*/, const unsigned char* drop /*[B]|NULL*/, float* x,
+                       float* level_s, float* angle_s, int B, int Nmax, int Cc, int HW, int S, int copy_cond,
+                       int null_rows, void* stream);
+/* drop[b] = (w2 >> 8) < thr: word 2 of the training-scalar call (kind 0) of sample ids[b]; thr = ceil(p 2^24) <= 2^24 */
+int vf_draw_cond_drop(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* drop /*[B]*/, int B,
+                      void* stream);
+/* The guided reverse-step tails: the sibling's arguments plus g (DEVICE fp32 [B], the guidance scales); unet_out is
+ * [S + B][Cout][HW] with S = off[B], row S + b the null row of sample b.  weights stay the conditional ones. */
+int vf_p_sample_tail_cfg(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,
+                         const long long* t, const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                         const float* posterior_log_variance, const float* posterior_mean_coef1,
+                         const float* posterior_mean_coef2, float* y_next /*|NULL*/, float* mean_out /*|NULL*/,
+                         float* weights /*|NULL*/, int B, int Cout, int HW, int maxV, int weighting, int clip,
+                         const float* g /*[B]*/, void* stream);
+int vf_p_sample_tail_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                             const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                             const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                             const float* posterior_mean_coef1, const float* posterior_mean_coef2,
+                             float* y_next /*|NULL*/, float* mean_out /*|NULL*/, float* weights /*|NULL*/, int B,
+                             int Cout, int HW, int maxV, int weighting, int clip, const float* g /*[B]*/,
+                             void* stream);
+int vf_sampler_step_cfg(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,
+                        const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                        const float* c1, const float* sigma, float* y0_prev /*[B][3][HW]|NULL*/, float* y_next,
+                        float* weights /*|NULL*/, int B, int Cout, int HW, int maxV, int weighting,
+                        const float* g /*[B]*/, void* stream);
+int vf_sampler_step_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                            const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                            const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                            float* y0_prev /*|NULL*/, float* y_next, float* weights /*|NULL*/, int B, int Cout, int HW,
+                            int maxV, int weighting, const float* g /*[B]*/, void* stream);
 /* Host mirrors: the same inline functions run on the CPU.  HOST pointers, no stream, no GPU needed. */
 int vf_rng_host_philox(const unsigned* counter /*[4]*/, const unsigned* key /*[2]*/, unsigned* out /*[4]*/);
 int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, int step, float* out /*[B][n]*/,
                        int B, int n);
 int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int T, long long* t, float* u, int B);
+/* vf_draw_cond_drop on the CPU */
+int vf_cond_drop_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* drop /*[B]*/, int B);
 
 /* ---- batch assembly from a device-resident view store (csrc/batch.hip; data.ViewStore): the reference loader's
  *      process_sample + collate + H2D, data/nmr_dataset.py:10-52, as one launch.  store: planar uint8 [N][24][3][H][W],

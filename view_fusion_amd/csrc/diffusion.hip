@@ -16,6 +16,24 @@
 // kernels with a penalty template (mse / l1 / huber), a per-sample noise-level weight (min-SNR, P2), the per-sample
 // loss handed back and an optional loss-by-level histogram -- same launch count, no atomics.  Opt-in; the MSE kernels
 // and their entry points are untouched.
+//
+// Classifier-free guidance (Ho & Salimans, "Classifier-Free Diffusion Guidance").  This comment is the ONE written
+// definition; tests/guidance_ref.py restates it.  Opt-in: siblings of the kernels above, which are untouched.
+//   Null conditioning.  The unconditional input of sample b is its own noisy target next to an all-zero conditioning half
+//     (all Cc channels, 3 or 6); its own level and angle (the relative angle in the `relative` configs) are kept.
+//   Guided noise.  eps = g_b * eps_c + (1 - g_b) * eps_u, in this order with 1 - g_b formed first, so that g = 1 gives
+//     eps_c and g = 0 gives eps_u exactly, contracted to a multiply-add or not.  eps_c: the composition over the sample's
+//     real views (softmax-weighted, or the mean) as above; eps_u: noise channels 0..2 of the sample's null row (that
+//     row's logit channels are ignored); g_b: a per-sample fp32 scale read from device memory (g > 1 extrapolates).
+//     The weights handed back stay the conditional softmax weights.
+//   Rows of a guided step.  The stacked batch has S + B rows: rows 0..S-1 are the unguided step's, under the same `off`
+//     table, and row S + b (S = off[B]) is sample b's null row.  Nothing that reads `off` changes meaning.
+//   Training drop (seeded; rng.h).  Sample `id` is dropped iff (w2 >> 8) < thr, w2 = word 2 of the kind-0, step-0, block-0
+//     call that already gives t (word 0) and u (word 1), thr = ceil(p * 2^24) computed on the host: an integer compare.
+//     p = 1 drops every sample; p = 0 is "off" and launches nothing.
+//   A dropped sample keeps its view_count: ALL its rows get the zero conditioning half, so S, `off` and every shape stay
+//     static for a captured step.  Its rows are then identical, so the composition (a convex combination) returns that one
+//     prediction -- the prediction of the single null row that sampling uses.
 #include "common.h"
 #include "loss_weight.h"
 #include "rng.h"
@@ -67,6 +85,67 @@ __global__ void stack_views_kernel(const float4* __restrict__ y_cond, const floa
         }
         o[nc4 + i] = y;
     }
+}
+
+// stack_views_kernel with conditioning dropout and null rows (classifier-free guidance, see the head of this file).
+// drop (uint8[B] | null): the conditioning half of every row of a sample with drop[b] != 0 is zeros; y_cond is not read
+// for it.  grid (chunks, rows): rows = S, or S + B with null rows -- row S + b is [ 0 | y_t[b] ] with level[b], angle[b].
+// The target half is stack_views_kernel's expression, so equal inputs give equal bits.
+__global__ void stack_views_cfg_kernel(const float4* __restrict__ y_cond, const float4* __restrict__ y_t,
+                                       const float4* __restrict__ noise, const float* __restrict__ level,
+                                       const float* __restrict__ angle, const int* __restrict__ off,
+                                       const unsigned char* __restrict__ drop, float4* __restrict__ x,
+                                       float* __restrict__ level_s, float* __restrict__ angle_s, int B, int Nmax, int nc4,
+                                       int n4, int copy_cond, int S) {
+    const int v = blockIdx.y;
+    const bool null_row = v >= S;
+    const int b = null_row ? v - S : sample_of_view(off, B, v);
+    const int j = null_row ? 0 : v - off[b];
+    const bool zero = null_row || (drop != nullptr && drop[b] != 0);
+    const float lv = level[b];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        level_s[v] = lv;
+        angle_s[v] = angle[b];
+    }
+    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    const float4* c = y_cond + ((size_t)b * Nmax + j) * nc4;
+    const float4* t = y_t + (size_t)b * n4;
+    const float4* z = noise ? noise + (size_t)b * n4 : nullptr;
+    float4* o = x + (size_t)v * (nc4 + n4);
+    if (copy_cond) {
+        if (zero)
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x)
+                o[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x) o[i] = c[i];
+    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+        float4 y = t[i];
+        if (z) {
+            const float4 e = z[i];
+            y.x = sa * y.x + sb * e.x;
+            y.y = sa * y.y + sb * e.y;
+            y.z = sa * y.z + sb * e.z;
+            y.w = sa * y.w + sb * e.w;
+        }
+        o[nc4 + i] = y;
+    }
+}
+
+// drop[b] = the training drop draw of sample ids[b] (rng.h: word 2 of the training-scalar call against thr)
+__global__ void draw_cond_drop_kernel(unsigned long long seed, const long long* __restrict__ ids, unsigned thr,
+                                      unsigned char* __restrict__ drop, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t w[4];
+    vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+    drop[b] = (unsigned char)vf_rng_cond_drop(w[2], thr);
+}
+
+// The guided combination of one float4: g eps_c + (1 - g) eps_u, gm = 1 - g formed by the caller.
+__device__ __forceinline__ float4 guide4(float4 ec, const float* __restrict__ eu, float g, float gm) {
+    const float4 u = *reinterpret_cast<const float4*>(eu);
+    return make_float4(g * ec.x + gm * u.x, g * ec.y + gm * u.y, g * ec.z + gm * u.z, g * ec.w + gm * u.w);
 }
 
 // Composed noise for one float4 of (b, c, pixels): softmax over the sample's views of the
@@ -206,23 +285,33 @@ __global__ __launch_bounds__(256) void compose_mse_bwd_kernel(const float* __res
 // One reverse step after the UNet: compose -> y0_hat = a_t y_t - b_t eps -> clamp ->
 // mean = c1 y0_hat + c2 y_t -> y_{t-1} = mean + z * exp(0.5 logvar).
 // `noise(i, o)` gives z for float4 i of the sample (o = its float offset in [B][3][HW]): a load, or a Philox draw.
-template <class Noise>
+// CFG: `out` has off[B] + B rows and the composed eps is guided by the sample's null row with the scale gscale[b].
+template <bool CFG, class Noise>
 __device__ __forceinline__ void p_sample_tail_body(
     const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
     const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
     const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
     const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip, Noise noise) {
+    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip, const float* __restrict__ gscale,
+    Noise noise) {
     const int b = blockIdx.y;
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
+    float g = 1.0f, gm = 0.0f;
+    const float* eu = nullptr;
+    if constexpr (CFG) {
+        g = gscale[b];
+        gm = 1.0f - g;
+        eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
+    }
     const long long tb = t[b];
     const float a_t = sqrt_recip[tb], b_t = sqrt_recipm1[tb], c1 = coef1[tb], c2 = coef2[tb];
     const float sd = expf(0.5f * logvar[tb]);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         float4 mx, inv;
-        const float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        if constexpr (CFG) eps = guide4(eps, eu + (size_t)c * HW + p, g, gm);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
         const float4 y = *reinterpret_cast<const float4*>(y_t + o);
         float y0[4] = {a_t * y.x - b_t * eps.x, a_t * y.y - b_t * eps.y, a_t * y.z - b_t * eps.z,
@@ -261,8 +350,24 @@ __global__ __launch_bounds__(256) void p_sample_tail_kernel(
     const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
     const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
     float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
-    p_sample_tail_body(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out, weights, Cout,
-                       HW, maxV, weighting, clip, [z](int, size_t o) {
+    p_sample_tail_body<false>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
+                       weights, Cout, HW, maxV, weighting, clip, nullptr, [z](int, size_t o) {
+                           float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+                           if (z) zz = *reinterpret_cast<const float4*>(z + o);
+                           return zz;
+                       });
+}
+
+// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
+__global__ __launch_bounds__(256) void p_sample_tail_cfg_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
+    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
+    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
+    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip,
+    const float* __restrict__ g) {
+    p_sample_tail_body<true>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
+                       weights, Cout, HW, maxV, weighting, clip, g, [z](int, size_t o) {
                            float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
                            if (z) zz = *reinterpret_cast<const float4*>(z + o);
                            return zz;
@@ -279,8 +384,26 @@ __global__ __launch_bounds__(256) void p_sample_tail_rng_kernel(
     float* __restrict__ mean_out, float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
     const unsigned long long id = (unsigned long long)ids[blockIdx.y];
     const long long tb = t[blockIdx.y];
-    p_sample_tail_body(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out, weights, Cout,
-                       HW, maxV, weighting, clip, [seed, id, tb](int i, size_t) {
+    p_sample_tail_body<false>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
+                       weights, Cout, HW, maxV, weighting, clip, nullptr, [seed, id, tb](int i, size_t) {
+                           float n[4] = {0.f, 0.f, 0.f, 0.f};
+                           if (tb != 0) vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
+                           return make_float4(n[0], n[1], n[2], n[3]);
+                       });
+}
+
+// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
+__global__ __launch_bounds__(256) void p_sample_tail_cfg_rng_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
+    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
+    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
+    float* __restrict__ mean_out, float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip,
+    const float* __restrict__ g) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    const long long tb = t[blockIdx.y];
+    p_sample_tail_body<true>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
+                       weights, Cout, HW, maxV, weighting, clip, g, [seed, id, tb](int i, size_t) {
                            float n[4] = {0.f, 0.f, 0.f, 0.f};
                            if (tb != 0) vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
                            return make_float4(n[0], n[1], n[2], n[3]);
@@ -291,24 +414,32 @@ __global__ __launch_bounds__(256) void p_sample_tail_rng_kernel(
 //   y0 = clamp(a[k] y - b[k] eps, -1, 1);  y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z;  y0_prev <- y0
 // with k = kidx[b] read from device memory.  sigma[k] == 0: `noise` is never called (no load, no draw);
 // c1[k] == 0 or no history buffer: y0_prev is not read (it may hold anything before the first multistep step).
-// Elementwise: y_next may be y, and y0_prev is read and written by the same thread.
-template <class Noise>
+// Elementwise: y_next may be y, and y0_prev is read and written by the same thread.  CFG: as in p_sample_tail_body.
+template <bool CFG, class Noise>
 __device__ __forceinline__ void sampler_step_body(
     const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
     const long long* __restrict__ kidx, const float* __restrict__ ta, const float* __restrict__ tb,
     const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
     const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
-    int Cout, int HW, int maxV, int weighting, Noise noise) {
+    int Cout, int HW, int maxV, int weighting, const float* __restrict__ gscale, Noise noise) {
     const int b = blockIdx.y;
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
+    float g = 1.0f, gm = 0.0f;
+    const float* eu = nullptr;
+    if constexpr (CFG) {
+        g = gscale[b];
+        gm = 1.0f - g;
+        eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
+    }
     const long long k = kidx[b];
     const float a_k = ta[k], b_k = tb[k], cy = tcy[k], c0 = tc0[k], c1 = tc1[k], sg = tsigma[k];
     const bool hist = y0_prev != nullptr && c1 != 0.0f, noisy = sg != 0.0f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         float4 mx, inv;
-        const float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        if constexpr (CFG) eps = guide4(eps, eu + (size_t)c * HW + p, g, gm);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
         const float4 y = *reinterpret_cast<const float4*>(y_t + o);
         const float ys[4] = {y.x, y.y, y.z, y.w};
@@ -352,8 +483,24 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(
     const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
     const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next,
     float* __restrict__ weights, int Cout, int HW, int maxV, int weighting) {
-    sampler_step_body(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW, maxV,
-                      weighting, [z](int, size_t o) {
+    sampler_step_body<false>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
+                      maxV, weighting, nullptr, [z](int, size_t o) {
+                          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+                          if (z) zz = *reinterpret_cast<const float4*>(z + o);
+                          return zz;
+                      });
+}
+
+// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
+__global__ __launch_bounds__(256) void sampler_step_cfg_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    const float* __restrict__ z, const long long* __restrict__ kidx, const float* __restrict__ ta,
+    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
+    const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next,
+    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting,
+    const float* __restrict__ g) {
+    sampler_step_body<true>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
+                      maxV, weighting, g, [z](int, size_t o) {
                           float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
                           if (z) zz = *reinterpret_cast<const float4*>(z + o);
                           return zz;
@@ -371,8 +518,27 @@ __global__ __launch_bounds__(256) void sampler_step_rng_kernel(
     int Cout, int HW, int maxV, int weighting) {
     const unsigned long long id = (unsigned long long)ids[blockIdx.y];
     const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
-    sampler_step_body(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW, maxV,
-                      weighting, [seed, id, step](int i, size_t) {
+    sampler_step_body<false>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
+                      maxV, weighting, nullptr, [seed, id, step](int i, size_t) {
+                          float n[4];
+                          vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
+                          return make_float4(n[0], n[1], n[2], n[3]);
+                      });
+}
+
+// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
+__global__ __launch_bounds__(256) void sampler_step_cfg_rng_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
+    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
+    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
+    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
+    int Cout, int HW, int maxV, int weighting,
+    const float* __restrict__ g) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
+    sampler_step_body<true>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
+                      maxV, weighting, g, [seed, id, step](int i, size_t) {
                           float n[4];
                           vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
                           return make_float4(n[0], n[1], n[2], n[3]);
@@ -779,6 +945,93 @@ int vf_sampler_step_rng(const float* unet_out, const int* off, const float* y_t,
     VF_RETURN_LAST_ERROR();
 }
 
+// ---- classifier-free guidance (the head of this file): conditioning dropout, null rows, guided tails ----
+// vf_stack_views with drop (DEVICE uint8 [B] | NULL) and null_rows: x [S (+ B)][Cc+3][HW], level_s / angle_s [S (+ B)].
+int vf_stack_views_cfg(const float* y_cond, const float* y_t, const float* noise, const float* level,
+                       const float* angle, const int* off, const unsigned char* drop, float* x, float* level_s,
+                       float* angle_s, int B, int Nmax, int Cc, int HW, int S, int copy_cond, int null_rows,
+                       void* stream) {
+    if (S <= 0 || B <= 0) return 0;
+    // a null row stands next to a sample's real rows: with null_rows every sample has at least one (S >= B); a
+    // drop-only call takes any S, like vf_stack_views
+    if ((HW & 3) || Cc < 1 || (null_rows && S < B)) return (int)hipErrorInvalidValue;
+    const int rows = null_rows ? S + B : S;
+    if (rows > 65535) return (int)hipErrorInvalidValue;
+    const int n4 = 3 * HW / 4, nc4 = Cc * HW / 4;
+    hipLaunchKernelGGL(stack_views_cfg_kernel, dim3(chunks_for(nc4 > n4 ? nc4 : n4), rows), dim3(256), 0,
+                       (hipStream_t)stream, (const float4*)y_cond, (const float4*)y_t, (const float4*)noise, level, angle,
+                       off, drop, (float4*)x, level_s, angle_s, B, Nmax, nc4, n4, copy_cond, S);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_draw_cond_drop(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* drop, int B,
+                      void* stream) {
+    if (B <= 0) return 0;
+    if (thr > (1u << 24)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(draw_cond_drop_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, seed, ids, thr,
+                       drop, B);
+    VF_RETURN_LAST_ERROR();
+}
+
+static inline bool tail_args_ok(int Cout, int HW, int weighting, const float* g) {
+    return !((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !g);
+}
+
+// The four guided tails: the sibling's arguments + g [B]; unet_out is [off[B] + B][Cout][HW].
+int vf_p_sample_tail_cfg(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* t,
+                         const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                         const float* posterior_log_variance, const float* posterior_mean_coef1,
+                         const float* posterior_mean_coef2, float* y_next, float* mean_out, float* weights, int B,
+                         int Cout, int HW, int maxV, int weighting, int clip, const float* g, void* stream) {
+    if (B <= 0) return 0;
+    if (!tail_args_ok(Cout, HW, weighting, g)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(p_sample_tail_cfg_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       unet_out, off, y_t, z, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
+                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV,
+                       weighting, clip, g);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_p_sample_tail_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                             const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                             const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                             const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
+                             float* mean_out, float* weights, int B, int Cout, int HW, int maxV, int weighting,
+                             int clip, const float* g, void* stream) {
+    if (B <= 0) return 0;
+    if (!tail_args_ok(Cout, HW, weighting, g)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(p_sample_tail_cfg_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas,
+                       posterior_log_variance, posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights,
+                       Cout, HW, maxV, weighting, clip, g);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_sampler_step_cfg(const float* unet_out, const int* off, const float* y_t, const float* z,
+                        const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                        const float* c1, const float* sigma, float* y0_prev, float* y_next, float* weights, int B,
+                        int Cout, int HW, int maxV, int weighting, const float* g, void* stream) {
+    if (B <= 0) return 0;
+    if (!tail_args_ok(Cout, HW, weighting, g) || !y_next) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sampler_step_cfg_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       unet_out, off, y_t, z, kidx, a, b, cy, c0, c1, sigma, y0_prev, y_next, weights, Cout, HW, maxV,
+                       weighting, g);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_sampler_step_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                            const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                            const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                            float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW, int maxV,
+                            int weighting, const float* g, void* stream) {
+    if (B <= 0) return 0;
+    if (!tail_args_ok(Cout, HW, weighting, g) || !y_next) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sampler_step_cfg_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev,
+                       y_next, weights, Cout, HW, maxV, weighting, g);
+    VF_RETURN_LAST_ERROR();
+}
+
 // Host mirrors: the same inline functions on the CPU, HOST pointers, no stream (the CPU suite's side of the parity).
 int vf_rng_host_philox(const unsigned* counter, const unsigned* key, unsigned* out) {
     vf_philox4x32_10(counter, key, out);
@@ -801,6 +1054,17 @@ int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int
         vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
         t[b] = vf_rng_timestep(w[0], T);
         u[b] = vf_rng_uniform24(w[1]);
+    }
+    return 0;
+}
+
+// the training drop draw on the CPU: drop[b] = (word 2 >> 8) < thr for the ids (HOST int64 [B])
+int vf_cond_drop_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* drop, int B) {
+    if (B < 0 || thr > (1u << 24)) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b) {
+        uint32_t w[4];
+        vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+        drop[b] = (unsigned char)vf_rng_cond_drop(w[2], thr);
     }
     return 0;
 }

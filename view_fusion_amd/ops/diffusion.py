@@ -1,6 +1,7 @@
 """The ViewFusion ops around the UNet: view stacking + q_sample, compose / weighted-noise loss, the sampler tail, PSNR
 and SSIM (reference model/view_fusion.py:70-177, 229-300; utils/metrics.py:6-12)."""
 import ctypes
+import math
 
 import torch
 
@@ -124,23 +125,98 @@ def philox_ids(seed, ids, kind, step, n):
     return out
 
 
-def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True):
+def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True, drop=None, null_rows=False):
     """Ragged stacking (+ optional q_sample): -> x (S,Cc+3,H,W), level_s (S,1), angle_s (S,1); Cc = y_cond's
-    channel count (3, or 6 for the `relative` configs)."""
+    channel count (3, or 6 for the `relative` configs).
+    Classifier-free guidance (csrc/diffusion.hip), through a sibling kernel taken only when one of the two is used:
+    drop (device bool / uint8 (B,)): the conditioning half of every row of a sample with drop[b] != 0 is zeros;
+    null_rows=True: S + B rows come back, row S + b = [ 0 | y_t[b] ] with the sample's own level and angle."""
     y_cond, y_t = _c(y_cond), _c(y_t)
     angle = _c(angle.reshape(-1).float())
     _check(y_cond, y_t, noise, level, angle)
     B, Nmax, Cc, H, W = y_cond.shape
     if y_t.shape[1] != 3:
         raise ValueError(f"the noisy target must have 3 channels, got {tuple(y_t.shape)}")
+    rows = S + B if null_rows else S
     if x is None:
-        x = torch.empty(S, Cc + 3, H, W, device=y_cond.device, dtype=torch.float32)
-    ls = torch.empty(S, 1, device=y_cond.device, dtype=torch.float32)
-    as_ = torch.empty(S, 1, device=y_cond.device, dtype=torch.float32)
-    _call("vf_stack_views", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
+        x = torch.empty(rows, Cc + 3, H, W, device=y_cond.device, dtype=torch.float32)
+    elif x.shape[0] != rows:
+        raise ValueError(f"stack_views writes {rows} rows, x has {x.shape[0]}")
+    ls = torch.empty(rows, 1, device=y_cond.device, dtype=torch.float32)
+    as_ = torch.empty(rows, 1, device=y_cond.device, dtype=torch.float32)
+    if drop is None and not null_rows:
+        _call("vf_stack_views", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
               ctypes.c_void_p(off.data_ptr()), _ptr(x), _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond),
               _stream())
+        return x, ls, as_
+    if drop is not None:
+        drop = _drop_mask(drop, B, y_cond.device)
+    _call("vf_stack_views_cfg", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
+          ctypes.c_void_p(off.data_ptr()), None if drop is None else ctypes.c_void_p(drop.data_ptr()), _ptr(x),
+          _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond), int(bool(null_rows)), _stream())
     return x, ls, as_
+
+
+# ---- classifier-free guidance (csrc/diffusion.hip holds the definition) ----
+def _drop_mask(drop, B, device):
+    """A conditioning-dropout mask as the contiguous device uint8 (B,) the kernels read (bool is reinterpreted)."""
+    if not torch.is_tensor(drop) or drop.dtype not in (torch.bool, torch.uint8) or drop.numel() != B:
+        raise ValueError(f"a conditioning-dropout mask is a bool / uint8 tensor of {B} elements")
+    if drop.device != device:
+        raise _lib.VFHipError("the conditioning-dropout mask must live on the batch's device")
+    drop = _c(drop.reshape(-1))
+    return drop.view(torch.uint8) if drop.dtype == torch.bool else drop
+
+
+def cond_drop_threshold(p):
+    """thr = ceil(p * 2^24) of the seeded drop draw, p in [0, 1] (p * 2^24 is exact in double precision)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:                      # (also refuses NaN)
+        raise ValueError(f"the conditioning-dropout probability must be in [0, 1], got {p}")
+    return int(math.ceil(p * 2.0 ** 24))
+
+
+def draw_cond_drop(seed, ids, p):
+    """The seeded conditioning-dropout mask of samples `ids`: device uint8 (B,), 1 = dropped.  A function of
+    (seed, id) alone: word 2 of the call that gives the sample's t and u, against ceil(p * 2^24).  One launch."""
+    thr = cond_drop_threshold(p)
+    B = ids.numel()
+    _check_ids(ids, B)
+    drop = torch.empty(B, device=ids.device, dtype=torch.uint8)
+    _call("vf_draw_cond_drop", _seed(seed), ctypes.c_void_p(ids.data_ptr()), thr, ctypes.c_void_p(drop.data_ptr()), B,
+          _stream())
+    return drop
+
+
+def guidance_scales(device, B, guidance):
+    """A guidance scale -- a number, or one per sample as a (B,) tensor / sequence -- as the contiguous fp32 (B,) tensor
+    on `device` that the guided tails read.  Finite and >= 0, else ValueError (checked on the host: a device tensor is
+    read back once, so hand the result, not the raw tensor, to anything that is called per step)."""
+    if torch.is_tensor(guidance) or isinstance(guidance, (list, tuple)):
+        g = torch.as_tensor(guidance).detach().reshape(-1).to(torch.float32)
+        if g.numel() != B:
+            raise ValueError(f"guidance needs one scale per sample: {g.numel()} scales for a batch of {B}")
+        host = g.cpu()
+        if not bool(torch.isfinite(host).all()) or bool((host < 0).any()):
+            raise ValueError("guidance scales must be finite and >= 0")
+        return _c(g.to(device))
+    g = float(guidance)
+    if not math.isfinite(g) or g < 0:
+        raise ValueError(f"a guidance scale must be finite and >= 0, got {g}")
+    return torch.full((B,), g, dtype=torch.float32, device=device)
+
+
+def _check_guidance(guidance, unet_out, B, S):
+    """The kernel reads row off[B] + b of unet_out and cannot see its row count: S = off[B] comes from the host
+    (view_offsets), and unet_out must have exactly S + B rows."""
+    _check(guidance)
+    if guidance.numel() != B:
+        raise ValueError(f"guidance needs one scale per sample (ops.guidance_scales): {guidance.numel()} for {B}")
+    if S is None:
+        raise ValueError("a guided tail needs S= (view_offsets): the null rows are rows S .. S + B - 1 of unet_out")
+    if unet_out.shape[0] != int(S) + B:
+        raise ValueError(f"a guided tail reads S + B rows (the null rows last): unet_out has {unet_out.shape[0]} rows "
+                         f"for S = {int(S)} views of {B} samples")
 
 
 class _ComposeLossFn(torch.autograd.Function):
@@ -248,14 +324,21 @@ def compose(unet_out, off, B, max_views, weighting, want_weights=True):
 
 
 def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip=True, want_weights=True,
-                  want_mean=False, inplace=False, seed=None, ids=None):
+                  want_mean=False, inplace=False, seed=None, ids=None, guidance=None, S=None):
     """Fused compose -> y0_hat -> clamp -> posterior mean -> + z*sigma.
     Returns (y_next, mean | None, weights | None).  seed= (with z=None): z is drawn inside the kernel from
-    (seed, ids[b], t[b], element) and is 0 where t[b] == 0; ids defaults to arange(B)."""
+    (seed, ids[b], t[b], element) and is 0 where t[b] == 0; ids defaults to arange(B).
+    guidance (device fp32 (B,), ops.guidance_scales) with S= (view_offsets' S = off[B], checked against unet_out's row
+    count): unet_out has S + B rows, the null rows last, and the composed noise is g eps_c + (1 - g) eps_u
+    (classifier-free guidance); the weights stay the conditional ones."""
     _check(unet_out, y_t, z)
+    if guidance is not None:
+        _check_guidance(guidance, unet_out, B, S)
+    cfg = "" if guidance is None else "_cfg"
+    gargs = () if guidance is None else (_ptr(guidance),)
     if seed is not None and z is not None:
         raise ValueError("p_sample_tail takes either z or seed=, not both")
-    S, Cout, H, W = unet_out.shape
+    _, Cout, H, W = unet_out.shape
     t = _c(t.to(torch.int64))
     y_next = y_t if inplace else torch.empty_like(y_t)     # elementwise: safe to overwrite y_t
     mean = torch.empty_like(y_t) if want_mean else None
@@ -265,50 +348,55 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
     if seed is not None:
         ids = sample_ids(y_t.device, B, ids)
         _check_ids(ids, B)
-        _call("vf_p_sample_tail_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _seed(seed),
+        _call(f"vf_p_sample_tail{cfg}_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _seed(seed),
               ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(t.data_ptr()), _ptr(sched["sqrt_recip_gammas"]),
               _ptr(sched["sqrt_recipm1_gammas"]), _ptr(sched["posterior_log_variance_clipped"]),
               _ptr(sched["posterior_mean_coef1"]), _ptr(sched["posterior_mean_coef2"]), _ptr(y_next), _ptr(mean),
-              _ptr(wts), B, Cout, H * W, max_views, int(weighting), int(clip), _stream())
+              _ptr(wts), B, Cout, H * W, max_views, int(weighting), int(clip), *gargs, _stream())
         return y_next, mean, wts
-    _call("vf_p_sample_tail", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _ptr(z),
+    _call(f"vf_p_sample_tail{cfg}", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _ptr(z),
               ctypes.c_void_p(t.data_ptr()), _ptr(sched["sqrt_recip_gammas"]), _ptr(sched["sqrt_recipm1_gammas"]),
               _ptr(sched["posterior_log_variance_clipped"]), _ptr(sched["posterior_mean_coef1"]),
               _ptr(sched["posterior_mean_coef2"]), _ptr(y_next), _ptr(mean), _ptr(wts), B, Cout, H * W, max_views,
-              int(weighting), int(clip), _stream())
+              int(weighting), int(clip), *gargs, _stream())
     return y_next, mean, wts
 
 
 def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_prev=None, want_weights=True,
-                 inplace=False, seed=None, ids=None):
+                 inplace=False, seed=None, ids=None, guidance=None, S=None):
     """One step of a few-step sampler (strided DDIM / DPM-Solver++ 2M), fused like p_sample_tail:
     compose -> y0 = clamp(a[k] y - b[k] eps) -> y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z, k = kidx[b].
     tables: the fp32 device tables a, b, cy, c0, c1, sigma (K,) and tau (K,) int64 (ViewFusion._sampler_plan).
     y0_prev (like y, optional): the multistep history, updated in place; it is not read where c1[k] == 0.
     Returns (y_next, weights | None).  seed= (with z=None): z is drawn inside the kernel from
-    (seed, ids[b], tau[k], element); where sigma[k] == 0 no z is loaded or drawn at all."""
+    (seed, ids[b], tau[k], element); where sigma[k] == 0 no z is loaded or drawn at all.
+    guidance (device fp32 (B,)) with S=: the guided tail, as in p_sample_tail."""
     _check(unet_out, y, z, y0_prev, *(tables[n] for n in ("a", "b", "cy", "c0", "c1", "sigma")))
+    if guidance is not None:
+        _check_guidance(guidance, unet_out, B, S)
+    cfg = "" if guidance is None else "_cfg"
     if seed is not None and z is not None:
         raise ValueError("sampler_step takes either z or seed=, not both")
-    S, Cout, H, W = unet_out.shape
+    _, Cout, H, W = unet_out.shape
     kidx = _c(kidx.to(torch.int64))
     y_next = y if inplace else torch.empty_like(y)         # elementwise: safe to overwrite y
     wts = None
     if weighting and want_weights:
         wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)
     tabs = [_ptr(tables[n]) for n in ("a", "b", "cy", "c0", "c1", "sigma")]
-    tail = (_ptr(y0_prev), _ptr(y_next), _ptr(wts), B, Cout, H * W, max_views, int(weighting), _stream())
+    tail = (_ptr(y0_prev), _ptr(y_next), _ptr(wts), B, Cout, H * W, max_views, int(weighting),
+            *(() if guidance is None else (_ptr(guidance),)), _stream())
     if seed is not None:
         ids = sample_ids(y.device, B, ids)
         _check_ids(ids, B)
         tau = tables["tau"]
         if not tau.is_cuda or tau.dtype != torch.int64 or not tau.is_contiguous():
             raise _lib.VFHipError("tables['tau'] must be a contiguous device int64 tensor")
-        _call("vf_sampler_step_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _seed(seed),
+        _call(f"vf_sampler_step{cfg}_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _seed(seed),
               ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(kidx.data_ptr()), ctypes.c_void_p(tau.data_ptr()),
               *tabs, *tail)
         return y_next, wts
-    _call("vf_sampler_step", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _ptr(z),
+    _call(f"vf_sampler_step{cfg}", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _ptr(z),
           ctypes.c_void_p(kidx.data_ptr()), *tabs, *tail)
     return y_next, wts
 

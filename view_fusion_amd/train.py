@@ -132,7 +132,7 @@ def split_batch(batch, extra, accum_steps):
 class _StepGraph:
     """One captured training iteration (forward, backward, Adam) for one batch geometry -- or, with accum_steps > 1, one
     captured micro-batch (forward, backward, the accumulate launch)."""
-    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum", "sample")
+    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum", "sample", "drop")
 
     def __init__(self):
         self.graph, self.seen, self.accum = None, 0, None
@@ -193,7 +193,13 @@ class Trainer:
     step -- the captured steps are dropped and every geometry is captured again after its eager sightings -- never a
     replay of the old objective.  In graph mode the accumulators, `model.last_sample_loss` and
     `model.last_level` are static buffers of the captured step; with accum_steps > 1 every micro-batch adds its samples
-    (B counts per step) and the two `last_*` tensors show the last micro-batch.  GPU model only."""
+    (B counts per step) and the two `last_*` tensors show the last micro-batch.  GPU model only.
+
+    Conditioning dropout (`model.set_cond_dropout(p)`, classifier-free guidance; default 0: nothing above changes) is the
+    model's too, and p is part of the same key: a change between steps drops the captured steps.  With seed= a sample's
+    mask is a function of (seed, sample id) -- the same under accum_steps, graph replay and any split over ranks;
+    `model.last_cond_drop` is a static buffer of the captured step (the last micro-batch's with accum_steps > 1).  An
+    injected `cond_drop=` mask runs the step eagerly, like every injected argument that is not a graph input."""
     GRAPH_AFTER = 2
     GRAPH_MAX = 96
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
@@ -490,6 +496,7 @@ class Trainer:
         e.sample = None
         if getattr(self.module, "_loss", None) is not None or getattr(self.module, "loss_hist", None) is not None:
             e.sample = (self.module.last_sample_loss, self.module.last_level)
+        e.drop = getattr(self.module, "last_cond_drop", None)      # conditioning dropout: the step's mask, likewise
         e.grads = list(grads)
         # what the captured launches address besides the graph's own pool
         e.keep = (fix, tables, offs, getattr(self.module, "gammas", None))
@@ -507,6 +514,8 @@ class Trainer:
             dst.copy_(src.reshape(dst.shape), non_blocking=True)
         if e.sample is not None:
             self.module.last_sample_loss, self.module.last_level = e.sample
+        if hasattr(self.module, "last_cond_drop"):
+            self.module.last_cond_drop = e.drop
         if accum is not None:                          # a micro-batch: its gradient goes into the accumulators, which
             self.opt.accum_tick(e.accum, *accum)       # the optimizer step after the last one reads and leaves in .grad
             e.graph.replay()
@@ -587,7 +596,8 @@ class Trainer:
         loss_key = getattr(self.module, "loss_key", None)
         loss_key = None if loss_key is None else loss_key()
         if loss_key != self._loss_key:
-            # the objective (model.set_loss) or the histogram changed: both are constants of the captured launches, so
+            # the objective (model.set_loss), the histogram or the conditioning-dropout probability changed: all are
+            # constants of the captured launches, so
             # the captured steps are dropped (and their memory freed); every geometry is captured again after its eager
             # sightings.  A replay never keeps the old objective.
             if self._graphs:

@@ -22,6 +22,11 @@ and tests/rng_ref.py can restate it on the CPU.
 
 `set_loss(...)` (default: the reference's unweighted MSE, untouched) selects the training objective's penalty (mse / l1 /
 huber) and a per-sample weight of the noise level (min-SNR, P2); see csrc/loss_weight.h.
+
+Classifier-free guidance (csrc/diffusion.hip holds the definition; both halves off by default, and then every path runs
+the launches it ran before): `set_cond_dropout(p)` zeroes the conditioning views of a training sample with probability
+p, and `generate(..., guidance=g)` (also `forward(generate=True)`, `p_sample`, `p_mean_variance`) runs one unconditional
+row per sample next to the conditional ones and extrapolates the noise prediction, g eps_c + (1 - g) eps_u.
 """
 import torch
 from torch import nn
@@ -40,6 +45,9 @@ class ViewFusion(nn.Module):
         self._loss = None                 # None: the reference's unweighted MSE through compose_mse_loss
         self.loss_hist = None             # (bin_sum, bin_cnt) device accumulators, attached by train.Trainer(loss_bins=)
         self.last_sample_loss = self.last_level = None
+        # conditioning dropout (set_cond_dropout) and the mask of the last training forward: plain attributes too
+        self._cond_drop_p = 0.0
+        self.last_cond_drop = None
 
     # -- training objective -------------------------------------------------------------------
     def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
@@ -73,11 +81,25 @@ class ViewFusion(nn.Module):
         else:
             self._loss = dict(penalty=penalty, delta=delta if penalty == "huber" else 1.0, weight_kind=kind, a=a, b=b)
 
+    def set_cond_dropout(self, p=0.0):
+        """Conditioning dropout for classifier-free guidance: in training mode, forward() replaces the conditioning
+        views of a sample by zeros with probability p (the null conditioning that generate(guidance=) samples with).  A
+        dropped sample keeps its view_count -- all its rows get the zero conditioning half -- so no shape changes.
+        With seed= the draw is a function of (seed, sample id) alone (ops.draw_cond_drop); without, torch.rand(B) < p
+        drawn after t, u and the noise.  forward(cond_drop=mask) injects the mask instead.  `last_cond_drop` is the
+        mask of the last training forward (device uint8 (B,), None while the feature is off).  p = 0 (the default): off,
+        the launches of before.  Stores no parameter or buffer; a Trainer drops its captured steps when p changes."""
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"the conditioning-dropout probability must be in [0, 1], got {p}")
+        self._cond_drop_p = p
+
     def loss_key(self):
-        """What a captured training step depends on besides its inputs: the objective and the attached histogram."""
+        """What a captured training step depends on besides its inputs: the objective, the attached histogram and the
+        conditioning-dropout probability."""
         h = self.loss_hist
         return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
-                None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()))
+                None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p)
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -128,39 +150,43 @@ class ViewFusion(nn.Module):
         return sample_gammas.sqrt() * y_0 + (1 - sample_gammas).sqrt() * noise
 
     # -- reverse process ---------------------------------------------------------------------
-    def _denoise(self, y_t, y_cond, angle, t, off, S, x=None, copy_cond=True, levels=None):
+    def _denoise(self, y_t, y_cond, angle, t, off, S, x=None, copy_cond=True, levels=None, null_rows=False):
         from . import ops
         level = ops.gather_level(self.gammas if levels is None else levels, t)
-        x, level_s, angle_s = ops.stack_views(y_cond, y_t, None, level, angle, off, S, x=x, copy_cond=copy_cond)
+        x, level_s, angle_s = ops.stack_views(y_cond, y_t, None, level, angle, off, S, x=x, copy_cond=copy_cond,
+                                              null_rows=null_rows)
         return x, self.denoise_fn(x, angle_s, level_s)
 
-    def p_mean_variance(self, y_t, y_cond, view_count, angle, t, clip_denoised: bool):
+    def p_mean_variance(self, y_t, y_cond, view_count, angle, t, clip_denoised: bool, guidance=None):
+        """guidance (a scale, or one per sample): the mean of the guided step; logits are the S conditional rows'."""
         from . import ops
+        gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
-        _, out = self._denoise(y_t, y_cond, angle, t, off, S)
+        _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None)
         w_on = bool(self.weighting_inference)
         _, mean, weights = ops.p_sample_tail(out, off, y_t, None, t, self._sched(), y_t.shape[0], max_v, w_on,
-                                             clip=clip_denoised, want_mean=True)
-        logits = out[:, 3:, ...] if w_on else None
+                                             clip=clip_denoised, want_mean=True, guidance=gs, S=S)
+        logits = out[:S, 3:, ...] if w_on else None
         return mean, self._at(self.posterior_log_variance_clipped, t), logits, weights
 
     @torch.no_grad()
-    def p_sample(self, y_t, y_cond, view_count, angle, t, clip_denoised=True, z=None):
+    def p_sample(self, y_t, y_cond, view_count, angle, t, clip_denoised=True, z=None, guidance=None):
         from . import ops
+        gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
-        _, out = self._denoise(y_t, y_cond, angle, t, off, S)
+        _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None)
         if z is None:
             z = torch.randn_like(y_t) if bool((t > 0).any()) else None
         elif not bool((t > 0).any()):
             z = None
         w_on = bool(self.weighting_inference)
         y, _, weights = ops.p_sample_tail(out, off, y_t, z, t, self._sched(), y_t.shape[0], max_v, w_on,
-                                          clip=clip_denoised)
-        return y, (out[:, 3:, ...] if w_on else None), weights
+                                          clip=clip_denoised, guidance=gs, S=S)
+        return y, (out[:S, 3:, ...] if w_on else None), weights
 
     @torch.no_grad()
     def generate(self, y_cond, view_count, angle, y_t=None, sample_num=8, z_seq=None, use_graph=None, seed=None,
-                 sample_ids=None, sample_steps=None, solver="ddim", eta=0.0):
+                 sample_ids=None, sample_steps=None, solver="ddim", eta=0.0, guidance=None):
         """Reverse diffusion over all T steps (reference view_fusion.py:179-214).
 
         use_graph (default: on for GPU tensors with S <= 16 stacked views): one reverse step -- level gather, re-stack of
@@ -177,6 +203,13 @@ class ViewFusion(nn.Module):
         levels with solver "ddim" (eta in [0, 1]; 0 deterministic, 1 ancestral) or "dpmpp2m" (DPM-Solver++ 2M, eta 0).
         The loop is the same one, with the table-driven tail (ops.sampler_step) and the step index k in place of t;
         z_seq stays (T, ...) and is read at the model timestep, z_seq[tau[k]]; snapshots where k % (K // sample_num) == 0.
+
+        guidance (default None: everything above, launch for launch): a classifier-free guidance scale g >= 0, or one per
+        sample as a (B,) tensor.  The stacked batch gets one null row per sample after the S real ones -- the sample's
+        noisy target next to an all-zero conditioning half, its own level and angle -- so the UNet sees S + B rows, and
+        every tail (ancestral or few-step, loaded or drawn z) uses eps = g eps_c + (1 - g) eps_u.  g = 1 is the
+        unguided sampler, g = 0 the unconditional model, g > 1 extrapolates.  The returned logits are those of the S
+        real rows and the weights stay the conditional softmax; the use_graph default compares S + B.
         """
         from . import ops
         plan = tau = None
@@ -184,6 +217,8 @@ class ViewFusion(nn.Module):
             _schedule.check_sampler(solver, eta)
             tau = _schedule.sample_timesteps(self.num_timesteps, sample_steps).tolist()
         b = y_cond.shape[0]
+        gs = None if guidance is None else ops.guidance_scales(y_cond.device, b, guidance)
+        guided = gs is not None
         assert self.num_timesteps > sample_num, "num_timesteps must greater than sample_num"
         n_steps = self.num_timesteps if tau is None else len(tau)
         every = max(1, n_steps // sample_num)
@@ -198,7 +233,7 @@ class ViewFusion(nn.Module):
         w_on = bool(self.weighting_inference)
         sched = self._sched()
         if use_graph is None:                             # measured: replay wins while the step is launch-bound
-            use_graph = y.is_cuda and S <= 16   # (at S = 12 replay and eager tie, but replay is immune to host jitter)
+            use_graph = y.is_cuda and S + (b if guided else 0) <= 16   # (at S = 12 replay and eager tie, but replay is immune to host jitter)
         t = torch.full((b,), n_steps - 1, device=dev, dtype=torch.long)     # the step index: t, or k of a few-step chain
         z_seed = seed if z_seq is None else None          # the tail draws z itself: no noise buffer
         z = None if z_seed is not None else torch.zeros_like(y)
@@ -211,17 +246,17 @@ class ViewFusion(nn.Module):
                 z_seed = z = None
         y_cond = y_cond.contiguous()
         angle = angle.contiguous()
-        # the conditioning half of the stacked input never changes: copy it once
-        x, _, _ = ops.stack_views(y_cond, y, None, ops.gather_level(levels, t), angle, off, S)
+        # the conditioning half of the stacked input never changes: copy it once (guided: the null rows' zeros too)
+        x, _, _ = ops.stack_views(y_cond, y, None, ops.gather_level(levels, t), angle, off, S, null_rows=guided)
 
         def step():
-            _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False, levels=levels)
+            _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False, levels=levels, null_rows=guided)
             if plan is not None:
                 _, weights = ops.sampler_step(out, off, y, z, t, plan, b, max_v, w_on, y0_prev=hist, inplace=True,
-                                              seed=z_seed, ids=ids)
+                                              seed=z_seed, ids=ids, guidance=gs, S=S)
                 return out, weights
             _, _, weights = ops.p_sample_tail(out, off, y, z, t, sched, b, max_v, w_on, inplace=True, seed=z_seed,
-                                              ids=ids)
+                                              ids=ids, guidance=gs, S=S)
             return out, weights
 
         graph = None
@@ -255,7 +290,7 @@ class ViewFusion(nn.Module):
                 out, weights = step()
             if i % every == 0:
                 ret.append(y.clone())
-                logit_arr.append(out[:, 3:, ...].clone() if w_on else None)
+                logit_arr.append(out[:S, 3:, ...].clone() if w_on else None)
                 weight_arr.append(weights.clone() if w_on else None)
         ret = torch.stack(ret, dim=1)
         samples = ret[:, -1, ...]
@@ -268,16 +303,23 @@ class ViewFusion(nn.Module):
 
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
-                z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0):
+                z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0,
+                guidance=None, cond_drop=None):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
             return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
-                                 sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta)
+                                 sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta,
+                                 guidance=guidance)
         from . import ops
         b = y_0.shape[0]
         dev = y_0.device
         level = None
+        # conditioning dropout (set_cond_dropout): an injected mask wins; else drawn in training mode when p > 0
+        drop_p = self._cond_drop_p if (cond_drop is None and self.training) else 0.0
+        drop = cond_drop
         if seed is not None:              # whatever was not injected comes from the counter-based generator
             ids = ops.sample_ids(dev, b, sample_ids)
+            if drop_p > 0:                # word 2 of the call that gives the sample's t and u
+                drop = ops.draw_cond_drop(seed, ids, drop_p)
             if t is None or u is None:
                 t_d, level_d, u_d = ops.draw_train(seed, ids, self.gammas, want_u=t is not None)
                 if t is None and u is None:
@@ -295,10 +337,16 @@ class ViewFusion(nn.Module):
             u = torch.rand((b, 1), device=dev)
         if noise is None:
             noise = torch.randn_like(y_0)
+        if drop is None and drop_p > 0:   # after t, u and noise: the reference's draw order for those is unchanged
+            drop = torch.rand(b, device=dev) < drop_p
         if level is None:
             level = ops.gather_level(self.gammas, t, u.reshape(-1).contiguous())
         off, S, _ = ops.view_offsets(view_count, dev)
-        x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S)
+        if drop is not None:
+            drop = ops.diffusion._drop_mask(drop, b, dev)
+        self.last_cond_drop = drop
+        x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S,
+                                              drop=drop)
         out = self.denoise_fn(x, angle_s, level_s)
         if self._loss is None and self.loss_hist is None:
             return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
