@@ -369,6 +369,49 @@ int vf_sampler_step_cfg_rng(const float* unet_out, const int* off, const float* 
                             const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
                             float* y0_prev /*|NULL*/, float* y_next, float* weights /*|NULL*/, int B, int Cout, int HW,
                             int maxV, int weighting, const float* g /*[B]*/, void* stream);
+/* ---- dynamic thresholding and guidance rescaling of the reverse step (csrc/diffusion.hip holds the definition): three
+ *      launches in place of one tail.  eps [B][3][HW] and stat [B][2] = {r_b, s_b} are the caller's scratch. ---- */
+/* The composed (g != NULL: and guided, unet_out [off[B] + B][Cout][HW]) noise into eps, the conditional weights as
+ * vf_compose_fwd writes them, and per-workgroup sums of eps_c, eps_c^2, eps_g, eps_g^2 into part (DEVICE double
+ * [B * 64 * 4]), reduced in a fixed order.  fused: which tail follows, as in vf_sample_stat (the guided combination is
+ * rounded as that tail's composing sibling rounds it). */
+int vf_compose_eps(const float* unet_out, const int* off, const float* g /*[B]|NULL*/, float* eps,
+                   float* weights /*|NULL*/, double* part, int B, int Cout, int HW, int maxV, int weighting, int fused,
+                   void* stream);
+/* One workgroup per sample: r_b = phi sigma(eps_c) / sigma(eps_g) + 1 - phi from `part` (phi <= 0: r_b = 1, part not
+ * read) and s_b = min(max(1, quantile), cmax), the (k, frac) quantile of |ta[idx[b]] y - tb[idx[b]] r_b eps| by exact radix
+ * selection (k < 0: s_b = 1, nothing selected).  k = floor(q (n - 1)), frac = q (n - 1) - k in [0, 1), n = 3 HW; frac != 0
+ * needs k + 1 < n.  cmax >= 1 (+inf: no cap).  fused: how the tail that follows rounds y0_hat -- 1 in front of
+ * vf_p_sample_tail_eps(_rng) (fma(a, y, -(b eps))), 0 in front of vf_sampler_step_eps(_rng) (a y and b eps rounded, then
+ * subtracted) -- so that the selection sees the very values the tail bounds. */
+int vf_sample_stat(const float* eps, const double* part /*|NULL*/, const float* y, const long long* idx, const float* ta,
+                   const float* tb, float* stat, int B, int HW, float phi, int k, float frac, float cmax, int fused,
+                   void* stream);
+/* out[b] = x_s[k] + frac (x_s[k+1] - x_s[k]) with x_s = sort(|x[b][0..n)|): the same selection on a plain [B][n] buffer,
+ * any n >= 1.  x_s[k+1] is not read when frac == 0. */
+int vf_abs_quantile(const float* x, int B, int n, int k, float frac, float* out /*[B]*/, void* stream);
+/* The tails on the eps buffer: eps is multiplied by stat[b][0] when rescale != 0; thr != 0 bounds y0_hat by
+ * clamp(., -s, s) / s with s = stat[b][1], else the static clamp (under `clip` in the ancestral tail).  Everything else
+ * as vf_p_sample_tail(_rng) / vf_sampler_step(_rng); the weights come from vf_compose_eps. */
+int vf_p_sample_tail_eps(const float* eps, const float* stat, const float* y_t, const float* z /*|NULL*/,
+                         const long long* t, const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                         const float* posterior_log_variance, const float* posterior_mean_coef1,
+                         const float* posterior_mean_coef2, float* y_next /*|NULL*/, float* mean_out /*|NULL*/, int B,
+                         int HW, int clip, int rescale, int thr, void* stream);
+int vf_p_sample_tail_eps_rng(const float* eps, const float* stat, const float* y_t, unsigned long long seed,
+                             const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                             const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                             const float* posterior_mean_coef1, const float* posterior_mean_coef2,
+                             float* y_next /*|NULL*/, float* mean_out /*|NULL*/, int B, int HW, int clip, int rescale,
+                             int thr, void* stream);
+int vf_sampler_step_eps(const float* eps, const float* stat, const float* y_t, const float* z /*|NULL*/,
+                        const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                        const float* c1, const float* sigma, float* y0_prev /*[B][3][HW]|NULL*/, float* y_next, int B,
+                        int HW, int rescale, int thr, void* stream);
+int vf_sampler_step_eps_rng(const float* eps, const float* stat, const float* y_t, unsigned long long seed,
+                            const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                            const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                            float* y0_prev /*|NULL*/, float* y_next, int B, int HW, int rescale, int thr, void* stream);
 /* Host mirrors: the same inline functions run on the CPU.  HOST pointers, no stream, no GPU needed. */
 int vf_rng_host_philox(const unsigned* counter /*[4]*/, const unsigned* key /*[2]*/, unsigned* out /*[4]*/);
 int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, int step, float* out /*[B][n]*/,

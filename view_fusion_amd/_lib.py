@@ -147,6 +147,13 @@ SIGNATURES = {
     "vf_p_sample_tail_cfg_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P],
     "vf_sampler_step_cfg": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
     "vf_sampler_step_cfg_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P],
+    "vf_compose_eps": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "vf_sample_stat": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _I, _F, _F, _I, _P],
+    "vf_abs_quantile": [_P, _I, _I, _I, _F, _P, _P],
+    "vf_p_sample_tail_eps": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vf_p_sample_tail_eps_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vf_sampler_step_eps": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vf_sampler_step_eps_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

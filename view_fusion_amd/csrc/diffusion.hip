@@ -34,6 +34,31 @@
 //   A dropped sample keeps its view_count: ALL its rows get the zero conditioning half, so S, `off` and every shape stay
 //     static for a captured step.  Its rows are then identical, so the composition (a convex combination) returns that one
 //     prediction -- the prediction of the single null row that sampling uses.
+//
+// Dynamic thresholding (Saharia et al., Imagen, 2.3) and guidance rescaling (Lin et al., "Common Diffusion Noise
+// Schedules and Sample Steps are Flawed", 3.4) for the reverse step.  This comment is the ONE written definition;
+// tests/threshold_ref.py restates it.  Opt-in: with both off every path runs the kernels above, untouched.
+//   n = 3 H W; every statistic is per sample b, over its n elements.
+//   1. eps_c = the composed noise (softmax over views, or the mean); eps_g = g eps_c + (1 - g) eps_u when guided, else
+//      eps_g = eps_c: compose4 / guide4 as above.
+//   2. Rescale (phi in (0, 1], needs guidance): r_b = phi (sigma(eps_c) / sigma(eps_g)) + (1 - phi), sigma the standard
+//      deviation over the n elements (the same n in both, so n against n - 1 cancels); r_b = 1 where sigma(eps_g) == 0;
+//      eps = r_b eps_g.  Off: eps = eps_g, no multiply.
+//   3. y0_hat = a y - b eps with the step's own table pair (sqrt_recip_gammas[t], sqrt_recipm1_gammas[t]; a[k], b[k]).
+//   4. Threshold (q in (0, 1], optional cap c >= 1): x = sort(|y0_hat|), pos = q (n - 1) in float64 on the host,
+//      k = floor(pos), frac = float32(pos - k); s_q = x[k] + frac (x[k+1] - x[k]) (torch.quantile's linear interpolation;
+//      x[k+1] is not read when frac == 0, which covers q = 1); s_b = max(1, s_q), then min(s_b, c);
+//      y0 = clamp(y0_hat, -s_b, s_b) / s_b.  This replaces the static clamp.  Off: the static clamp stays as it is.
+//   5. The rest of the step is unchanged (posterior mean + z sd, or cy y + c0 y0 + c1 y0_prev + sigma z); y0_prev
+//      receives the thresholded y0.     6. Weights and logits stay the conditional ones.
+//   NaN / Inf inputs: unspecified.
+//   Three launches instead of the one tail: compose_eps_kernel writes eps_g, the weights and per-workgroup partial sums
+//   of eps_c, eps_c^2, eps_g, eps_g^2 (doubles, fixed-order trees, no atomics on global memory); sample_stat_kernel, one
+//   workgroup per sample, adds the partials in index order (double) -> r_b, then finds x[k] and x[k+1] of
+//   |a y - b r_b eps_g| EXACTLY by radix selection on the bit pattern with the sign cleared -- monotone for non-negative
+//   floats, denormals and -0 included -- with LDS histograms of 32-bit integer counts (integer adds commute, so LDS
+//   atomics do not make the result depend on their order), and writes stat[b] = {r_b, s_b}; the *_eps tails read eps_g and
+//   stat.  t / kidx / stat all live in device memory: a captured step replays for every step.
 #include "common.h"
 #include "loss_weight.h"
 #include "rng.h"
@@ -282,20 +307,110 @@ __global__ __launch_bounds__(256) void compose_mse_bwd_kernel(const float* __res
     }
 }
 
+// y0_hat of one element, as the composing tails write it.  How it is rounded there is the compiler's choice per body
+// (held fixed by the instruction-stream comparison of profiles/threshold.md): the ancestral tails round b eps and fuse the
+// rest, fma(a, y, -(b eps)); the few-step tails round both products and subtract.  The tails on the eps buffer and the
+// statistics kernel say explicitly which (FUSED), so that a sample whose threshold is 1 gets the static clamp's bits and
+// the selection sees exactly the values the tail bounds.
+__device__ __forceinline__ float y0_hat(float a, float y, float b, float eps) { return a * y - b * eps; }
+// (Pinned arithmetic: contraction is off inside these functions, so a product or a sum written here is rounded as
+// written, and a fused multiply-add is one only where __builtin_fmaf says so.)
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+template <bool FUSED>
+__device__ __forceinline__ float y0_hat_as(float a, float y, float b, float eps) {
+    if constexpr (FUSED) return __builtin_fmaf(a, y, -mul_rn(b, eps));
+    return add_rn(mul_rn(a, y), -mul_rn(b, eps));
+}
+
+// y0 -> y_next, the one copy of each flavour's update.  PINNED = false is the expression the composing tails have always
+// compiled; PINNED = true (the tails on the eps buffer) writes out, operation by operation, the roundings the compiler
+// gives that expression in ALL of those tails (read off their instruction stream, which the comparison of
+// profiles/threshold.md holds fixed), so that a sample whose threshold is 1 gets the static clamp's bits:
+//   ancestral: mean = fma(c2, y, c1 y0), y_next = fma(z, sd, mean), every element;
+//   few-step:  cy y + c0 y0 is fma(cy, y, c0 y0) in elements 0, 1 of a float4 and both products rounded, then added, in
+//              elements 2, 3 (the packed-math schedule of that body); the history and noise terms are fused onto it.
+template <bool PINNED>
+__device__ __forceinline__ void posterior_update(float c1, float c2, float sd, float y0, float y, float z, float& m,
+                                                 float& r) {
+    if constexpr (PINNED) {
+        m = __builtin_fmaf(c2, y, mul_rn(c1, y0));
+        r = __builtin_fmaf(z, sd, m);
+    } else {
+        m = c1 * y0 + c2 * y;
+        r = m + z * sd;
+    }
+}
+template <bool PINNED>
+__device__ __forceinline__ float multistep_base(float cy, float y, float c0, float y0, int j) {
+    if constexpr (PINNED)
+        return j < 2 ? __builtin_fmaf(cy, y, mul_rn(c0, y0)) : add_rn(mul_rn(cy, y), mul_rn(c0, y0));
+    return cy * y + c0 * y0;
+}
+template <bool PINNED>
+__device__ __forceinline__ float multistep_add(float r, float c, float v) {
+    if constexpr (PINNED) return __builtin_fmaf(c, v, r);
+    return r + c * v;
+}
+
+// What the tails that read the composed-eps buffer know about their sample (the head of this file holds the definition):
+// stat[b] = {r_b, s_b} from sample_stat_kernel.  rescale == 0: eps is the buffer's value, no multiply; thr == 0: the
+// static clamp under `clip`, as in the composing tails.
+struct EpsBound {
+    float r, s;
+    int thr;
+    __device__ __forceinline__ float operator()(float v, int clip) const {
+        if (thr) return fminf(fmaxf(v, -s), s) / s;
+        return clip ? fminf(fmaxf(v, -1.0f), 1.0f) : v;
+    }
+};
+struct EpsBuffer {
+    const float* __restrict__ eps = nullptr;      // eps_g [B][3][HW]
+    const float2* __restrict__ stat = nullptr;    // [B]
+    int rescale = 0, thr = 0;
+    __device__ __forceinline__ EpsBound bound(int b) const {
+        EpsBound l{1.0f, 1.0f, thr};
+        if (stat != nullptr && (rescale || thr)) {
+            const float2 st = stat[b];
+            l.r = st.x;
+            l.s = st.y;
+        }
+        return l;
+    }
+    __device__ __forceinline__ float4 load(size_t o, const EpsBound& l) const {
+        float4 e = *reinterpret_cast<const float4*>(eps + o);
+        if (rescale) e = make_float4(l.r * e.x, l.r * e.y, l.r * e.z, l.r * e.w);
+        return e;
+    }
+};
+
 // One reverse step after the UNet: compose -> y0_hat = a_t y_t - b_t eps -> clamp ->
 // mean = c1 y0_hat + c2 y_t -> y_{t-1} = mean + z * exp(0.5 logvar).
 // `noise(i, o)` gives z for float4 i of the sample (o = its float offset in [B][3][HW]): a load, or a Philox draw.
 // CFG: `out` has off[B] + B rows and the composed eps is guided by the sample's null row with the scale gscale[b].
-template <bool CFG, class Noise>
+// EPS (the source of eps): false -- composed (+ guided) here from `out`, static clamp, weights written; true -- read
+// back from the composed-eps pass through `src` (EpsBuffer below: rescale, dynamic threshold), and `out`, `off`,
+// `weights`, `gscale` and the four ints after `weights` are not touched.  Everything from y0 on is shared.
+template <bool CFG, bool EPS = false, class Noise>
 __device__ __forceinline__ void p_sample_tail_body(
     const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
     const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
     const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
     const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
     float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip, const float* __restrict__ gscale,
-    Noise noise) {
+    Noise noise, EpsBuffer src = EpsBuffer{}) {
     const int b = blockIdx.y;
-    const int v0 = off[b], v1 = off[b + 1];
+    int v0 = 0, v1 = 0;
+    if constexpr (!EPS) {
+        v0 = off[b];
+        v1 = off[b + 1];
+    }
     const int n4 = 3 * HW / 4;
     float g = 1.0f, gm = 0.0f;
     const float* eu = nullptr;
@@ -304,30 +419,40 @@ __device__ __forceinline__ void p_sample_tail_body(
         gm = 1.0f - g;
         eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
     }
+    const EpsBound lim = src.bound(b);
     const long long tb = t[b];
     const float a_t = sqrt_recip[tb], b_t = sqrt_recipm1[tb], c1 = coef1[tb], c2 = coef2[tb];
     const float sd = expf(0.5f * logvar[tb]);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         float4 mx, inv;
-        float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        float4 eps;
+        if constexpr (!EPS) eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
         if constexpr (CFG) eps = guide4(eps, eu + (size_t)c * HW + p, g, gm);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        if constexpr (EPS) eps = src.load(o, lim);
         const float4 y = *reinterpret_cast<const float4*>(y_t + o);
-        float y0[4] = {a_t * y.x - b_t * eps.x, a_t * y.y - b_t * eps.y, a_t * y.z - b_t * eps.z,
-                       a_t * y.w - b_t * eps.w};
+        float y0[4] = {y0_hat(a_t, y.x, b_t, eps.x), y0_hat(a_t, y.y, b_t, eps.y), y0_hat(a_t, y.z, b_t, eps.z),
+                       y0_hat(a_t, y.w, b_t, eps.w)};
+        if constexpr (EPS) {
+            y0[0] = y0_hat_as<true>(a_t, y.x, b_t, eps.x);
+            y0[1] = y0_hat_as<true>(a_t, y.y, b_t, eps.y);
+            y0[2] = y0_hat_as<true>(a_t, y.z, b_t, eps.z);
+            y0[3] = y0_hat_as<true>(a_t, y.w, b_t, eps.w);
+        }
         const float ys[4] = {y.x, y.y, y.z, y.w};
         float m[4], r[4];
         const float4 zz = noise(i, o);
         const float zs[4] = {zz.x, zz.y, zz.z, zz.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if (clip) y0[k] = fminf(fmaxf(y0[k], -1.0f), 1.0f);
-            m[k] = c1 * y0[k] + c2 * ys[k];
-            r[k] = m[k] + zs[k] * sd;
+            if constexpr (EPS) y0[k] = lim(y0[k], clip);
+            else if (clip) y0[k] = fminf(fmaxf(y0[k], -1.0f), 1.0f);
+            posterior_update<EPS>(c1, c2, sd, y0[k], ys[k], zs[k], m[k], r[k]);
         }
         if (y_next) *reinterpret_cast<float4*>(y_next + o) = make_float4(r[0], r[1], r[2], r[3]);
         if (mean_out) *reinterpret_cast<float4*>(mean_out + o) = make_float4(m[0], m[1], m[2], m[3]);
+        if constexpr (EPS) continue;
         if (weights && weighting) {
             const size_t vs = (size_t)Cout * HW;
             for (int j = 0; j < maxV; ++j) {
@@ -415,15 +540,22 @@ __global__ __launch_bounds__(256) void p_sample_tail_cfg_rng_kernel(
 // with k = kidx[b] read from device memory.  sigma[k] == 0: `noise` is never called (no load, no draw);
 // c1[k] == 0 or no history buffer: y0_prev is not read (it may hold anything before the first multistep step).
 // Elementwise: y_next may be y, and y0_prev is read and written by the same thread.  CFG: as in p_sample_tail_body.
-template <bool CFG, class Noise>
+// EPS: the source of eps, as in p_sample_tail_body.
+template <bool CFG, bool EPS = false, class Noise>
 __device__ __forceinline__ void sampler_step_body(
     const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
     const long long* __restrict__ kidx, const float* __restrict__ ta, const float* __restrict__ tb,
     const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
     const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
-    int Cout, int HW, int maxV, int weighting, const float* __restrict__ gscale, Noise noise) {
+    int Cout, int HW, int maxV, int weighting, const float* __restrict__ gscale, Noise noise,
+    EpsBuffer src = EpsBuffer{}) {
     const int b = blockIdx.y;
-    const int v0 = off[b], v1 = off[b + 1];
+    int v0 = 0, v1 = 0;
+    if constexpr (!EPS) {
+        v0 = off[b];
+        v1 = off[b + 1];
+    }
+    const EpsBound lim = src.bound(b);
     const int n4 = 3 * HW / 4;
     float g = 1.0f, gm = 0.0f;
     const float* eu = nullptr;
@@ -438,28 +570,34 @@ __device__ __forceinline__ void sampler_step_body(
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         float4 mx, inv;
-        float4 eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        float4 eps;
+        if constexpr (!EPS) eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
         if constexpr (CFG) eps = guide4(eps, eu + (size_t)c * HW + p, g, gm);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        if constexpr (EPS) eps = src.load(o, lim);
         const float4 y = *reinterpret_cast<const float4*>(y_t + o);
         const float ys[4] = {y.x, y.y, y.z, y.w};
         const float es[4] = {eps.x, eps.y, eps.z, eps.w};
         float y0[4], r[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            y0[j] = fminf(fmaxf(a_k * ys[j] - b_k * es[j], -1.0f), 1.0f);
-            r[j] = cy * ys[j] + c0 * y0[j];
+            if constexpr (EPS) y0[j] = lim(y0_hat_as<false>(a_k, ys[j], b_k, es[j]), 1);
+            else y0[j] = fminf(fmaxf(y0_hat(a_k, ys[j], b_k, es[j]), -1.0f), 1.0f);
+            r[j] = multistep_base<EPS>(cy, ys[j], c0, y0[j], j);
         }
         if (hist) {
             const float4 h = *reinterpret_cast<const float4*>(y0_prev + o);
-            r[0] += c1 * h.x; r[1] += c1 * h.y; r[2] += c1 * h.z; r[3] += c1 * h.w;
+            r[0] = multistep_add<EPS>(r[0], c1, h.x); r[1] = multistep_add<EPS>(r[1], c1, h.y);
+            r[2] = multistep_add<EPS>(r[2], c1, h.z); r[3] = multistep_add<EPS>(r[3], c1, h.w);
         }
         if (noisy) {
             const float4 z = noise(i, o);
-            r[0] += sg * z.x; r[1] += sg * z.y; r[2] += sg * z.z; r[3] += sg * z.w;
+            r[0] = multistep_add<EPS>(r[0], sg, z.x); r[1] = multistep_add<EPS>(r[1], sg, z.y);
+            r[2] = multistep_add<EPS>(r[2], sg, z.z); r[3] = multistep_add<EPS>(r[3], sg, z.w);
         }
         if (y0_prev) *reinterpret_cast<float4*>(y0_prev + o) = make_float4(y0[0], y0[1], y0[2], y0[3]);
         *reinterpret_cast<float4*>(y_next + o) = make_float4(r[0], r[1], r[2], r[3]);
+        if constexpr (EPS) continue;
         if (weights && weighting) {
             const size_t vs = (size_t)Cout * HW;
             for (int j = 0; j < maxV; ++j) {
@@ -734,6 +872,284 @@ __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __re
                             w.w * (e.w - nh.w) * g.w);
         }
     }
+}
+
+// ---- dynamic thresholding / guidance rescaling (the head of this file) ----
+// grid (chunks, B).  eps_g [B][3][HW] (= eps_c when !CFG); the conditional weights as compose_fwd_kernel writes them;
+// part[(b * chunks + chunk) * 4 + {0..3}] = this workgroup's sums of eps_c, eps_c^2, eps_g, eps_g^2.
+// FUSED_TAIL (CFG only): which tail follows, as in y0_hat_as.  The composing guided tails round guide4's expression
+// differently too -- fma(g, eps_c, gm eps_u) in the ancestral bodies, fma(gm, eps_u, g eps_c) in the few-step ones -- and
+// the eps written here is pinned to the tail it stands in for (g = 1 and g = 0 reduce exactly in both forms).
+template <bool CFG, bool FUSED_TAIL>
+__global__ __launch_bounds__(256) void compose_eps_kernel(const float* __restrict__ out, const int* __restrict__ off,
+                                                          const float* __restrict__ gscale, float* __restrict__ eps_out,
+                                                          float* __restrict__ weights, double* __restrict__ part,
+                                                          int Cout, int HW, int maxV, int weighting) {
+    __shared__ double red[4][4];
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    float g = 1.0f, gm = 0.0f;
+    const float* eu = nullptr;
+    if constexpr (CFG) {
+        g = gscale[b];
+        gm = 1.0f - g;
+        eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
+    }
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        float4 mx, inv;
+        const float4 ec = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        float4 eg = ec;
+        if constexpr (CFG) {
+            const float4 u = *reinterpret_cast<const float4*>(eu + (size_t)c * HW + p);
+            if constexpr (FUSED_TAIL)
+                eg = make_float4(__builtin_fmaf(g, ec.x, mul_rn(gm, u.x)), __builtin_fmaf(g, ec.y, mul_rn(gm, u.y)),
+                                 __builtin_fmaf(g, ec.z, mul_rn(gm, u.z)), __builtin_fmaf(g, ec.w, mul_rn(gm, u.w)));
+            else
+                eg = make_float4(__builtin_fmaf(gm, u.x, mul_rn(g, ec.x)), __builtin_fmaf(gm, u.y, mul_rn(g, ec.y)),
+                                 __builtin_fmaf(gm, u.z, mul_rn(g, ec.z)), __builtin_fmaf(gm, u.w, mul_rn(g, ec.w)));
+        }
+        *reinterpret_cast<float4*>(eps_out + (size_t)b * 3 * HW + 4 * (size_t)i) = eg;
+        const double c4[4] = {ec.x, ec.y, ec.z, ec.w}, g4[4] = {eg.x, eg.y, eg.z, eg.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            sum[0] += c4[j];
+            sum[1] += c4[j] * c4[j];
+            sum[2] += g4[j];
+            sum[3] += g4[j] * g4[j];
+        }
+        if (weights && weighting) {
+            const size_t vs = (size_t)Cout * HW;
+            for (int j = 0; j < maxV; ++j) {
+                float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (v0 + j < v1) {
+                    const float4 l = *reinterpret_cast<const float4*>(out + (size_t)(v0 + j) * vs +
+                                                                     (size_t)(3 + c) * HW + p);
+                    w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
+                                    expf(l.w - mx.w) * inv.w);
+                }
+                *reinterpret_cast<float4*>(weights + (((size_t)b * maxV + j) * 3) * HW + 4 * (size_t)i) = w;
+            }
+        }
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                            // a fixed tree per wave, then the four waves in index order
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) sum[q] += __shfl_xor(sum[q], o, VF_WAVE);
+        if (lane == 0) red[wid][q] = sum[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        const int q = threadIdx.x;
+        part[((size_t)b * gridDim.x + blockIdx.x) * 4 + q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+    }
+}
+
+// Exact selection of the order statistics k (and k + 1 when want_next) of n values given as bit patterns with the sign
+// cleared: bits_at(i), i in [0, n).  One workgroup of any multiple of 64 threads; every thread gets the result.
+// Four passes of 8 bits, most significant first: a 256-bin LDS histogram of the values that match the prefix found so
+// far, then the bin that holds the rank.  `below` counts the values smaller than x[k], `eq` those equal to it, so
+// x[k+1] == x[k] iff below + eq > k + 1 (duplicates straddling the two ranks); else x[k+1] is the smallest value above
+// x[k], an integer minimum.  Counts are 32-bit integers (a bin may hold all n values); integer adds and minima
+// commute, so the result does not depend on the order the LDS atomics land in.
+// A wave whose active lanes all hit ONE bin -- the usual case in the exponent pass -- adds its count once.
+template <class Bits>
+__device__ __forceinline__ void abs_select(Bits bits_at, int n, int k, bool want_next, unsigned* hist /*[256]*/,
+                                           unsigned* sh /*[4]*/, unsigned& xk, unsigned& xk1) {
+    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
+    unsigned prefix = 0, mask = 0, below = 0, eq = 0;
+    unsigned rank = (unsigned)k;
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int j = tid; j < 256; j += nt) hist[j] = 0;
+        __syncthreads();
+        for (int base = 0; base < n; base += nt) {           // base is uniform: every lane reaches the ballots
+            const int i = base + tid;
+            bool act = i < n;
+            const unsigned u = act ? bits_at(i) : 0u;
+            act = act && (u & mask) == prefix;
+            const unsigned bin = (u >> shift) & 255u;
+            const unsigned long long m = __ballot(act);
+            if (m != 0ull) {
+                const int lead = __ffsll((long long)m) - 1;
+                const unsigned lb = (unsigned)__shfl((int)bin, lead, VF_WAVE);
+                const unsigned long long same = __ballot(act && bin == lb);
+                if (same == m) {
+                    if (lane == lead) atomicAdd(&hist[lb], (unsigned)__popcll(m));
+                } else if (act) {
+                    atomicAdd(&hist[bin], 1u);
+                }
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            unsigned acc = 0;
+            int j = 0;
+            for (; j < 255; ++j) {
+                const unsigned c = hist[j];
+                if (acc + c > rank) break;
+                acc += c;
+            }
+            sh[0] = (unsigned)j;
+            sh[1] = acc;
+            sh[2] = hist[j];
+        }
+        __syncthreads();
+        prefix |= sh[0] << shift;
+        mask |= 255u << shift;
+        rank -= sh[1];
+        below += sh[1];
+        eq = sh[2];
+    }
+    xk = xk1 = prefix;
+    if (!want_next || below + eq > (unsigned)k + 1u) return;  // (uniform: every thread holds the same counts)
+    if (tid == 0) sh[3] = 0xffffffffu;
+    __syncthreads();
+    unsigned mn = 0xffffffffu;
+    for (int i = tid; i < n; i += nt) {
+        const unsigned u = bits_at(i);
+        if (u > prefix && u < mn) mn = u;
+    }
+    if (mn != 0xffffffffu) atomicMin(&sh[3], mn);
+    __syncthreads();
+    xk1 = sh[3];
+}
+
+// s_q = x[k] + frac (x[k+1] - x[k]); exactly x[k] where frac == 0 or the two are equal
+__device__ __forceinline__ float quantile_lerp(unsigned xk, unsigned xk1, float frac) {
+    const float x0 = __uint_as_float(xk);
+    return frac != 0.0f ? x0 + frac * (__uint_as_float(xk1) - x0) : x0;
+}
+
+// One workgroup per sample: stat[b] = {r_b, s_b} (the head of this file).  phi <= 0: rescale off, r_b = 1 and `part` is
+// not read; k < 0: threshold off, s_b = 1 and nothing is selected.  idx = t or kidx, (ta, tb) the step's table pair;
+// fused: how the tail that follows rounds y0_hat (y0_hat_as: 1 the ancestral tail, 0 the few-step one).
+__global__ __launch_bounds__(1024) void sample_stat_kernel(const float* __restrict__ eps, const double* __restrict__ part,
+                                                           int ch, const float* __restrict__ y,
+                                                           const long long* __restrict__ idx,
+                                                           const float* __restrict__ ta, const float* __restrict__ tb,
+                                                           float2* __restrict__ stat, int n, float phi, int k,
+                                                           float frac, float cmax, int fused) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sh[4];
+    __shared__ float r_sh;
+    const int b = blockIdx.x;
+    const bool rescale = phi > 0.0f;
+    if (threadIdx.x == 0) {
+        float r = 1.0f;
+        if (rescale) {
+            double sm[4] = {0.0, 0.0, 0.0, 0.0};
+            for (int c = 0; c < ch; ++c)
+                for (int q = 0; q < 4; ++q) sm[q] += part[((size_t)b * ch + c) * 4 + q];
+            const double var_c = fmax(sm[1] - sm[0] * sm[0] / (double)n, 0.0);
+            const double var_g = fmax(sm[3] - sm[2] * sm[2] / (double)n, 0.0);
+            if (var_g > 0.0) r = (float)((double)phi * sqrt(var_c / var_g) + (1.0 - (double)phi));
+        }
+        r_sh = r;
+    }
+    __syncthreads();
+    const float r = r_sh;
+    float s = 1.0f;
+    if (k >= 0) {
+        const long long tk = idx[b];
+        const float a = ta[tk], bb = tb[tk];
+        const float* e = eps + (size_t)b * n;
+        const float* yy = y + (size_t)b * n;
+        unsigned xk, xk1;
+        abs_select(
+            [=](int i) {
+                float ev = e[i];
+                if (rescale) ev = r * ev;
+                const float v = fused ? y0_hat_as<true>(a, yy[i], bb, ev) : y0_hat_as<false>(a, yy[i], bb, ev);
+                return __float_as_uint(v) & 0x7fffffffu;
+            },
+            n, k, frac != 0.0f, hist, sh, xk, xk1);
+        s = fminf(fmaxf(1.0f, quantile_lerp(xk, xk1, frac)), cmax);
+    }
+    if (threadIdx.x == 0) stat[b] = make_float2(r, s);
+}
+
+// out[b] = the (k, frac) quantile of |x[b][0..n)|: the same selection on a plain buffer; one workgroup per row
+__global__ __launch_bounds__(1024) void abs_quantile_kernel(const float* __restrict__ x, float* __restrict__ out, int n,
+                                                            int k, float frac) {
+    __shared__ unsigned hist[256];
+    __shared__ unsigned sh[4];
+    const float* row = x + (size_t)blockIdx.x * n;
+    unsigned xk, xk1;
+    abs_select([=](int i) { return __float_as_uint(row[i]) & 0x7fffffffu; }, n, k, frac != 0.0f, hist, sh, xk, xk1);
+    if (threadIdx.x == 0) out[blockIdx.x] = quantile_lerp(xk, xk1, frac);
+}
+
+// The four tails on the composed-eps buffer: grid (chunks, B) as their composing siblings, the same z conventions.
+__global__ __launch_bounds__(256) void p_sample_tail_eps_kernel(
+    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
+    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
+    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
+    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out, int HW, int clip,
+    int rescale, int thr) {
+    p_sample_tail_body<false, true>(nullptr, nullptr, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next,
+                                    mean_out, nullptr, 0, HW, 0, 0, clip, nullptr,
+                                    [z](int, size_t o) {
+                                        float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+                                        if (z) zz = *reinterpret_cast<const float4*>(z + o);
+                                        return zz;
+                                    },
+                                    EpsBuffer{eps, stat, rescale, thr});
+}
+
+__global__ __launch_bounds__(256) void p_sample_tail_eps_rng_kernel(
+    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
+    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
+    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
+    float* __restrict__ mean_out, int HW, int clip, int rescale, int thr) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    const long long tb = t[blockIdx.y];
+    p_sample_tail_body<false, true>(nullptr, nullptr, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next,
+                                    mean_out, nullptr, 0, HW, 0, 0, clip, nullptr,
+                                    [seed, id, tb](int i, size_t) {
+                                        float n[4] = {0.f, 0.f, 0.f, 0.f};
+                                        if (tb != 0)
+                                            vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
+                                        return make_float4(n[0], n[1], n[2], n[3]);
+                                    },
+                                    EpsBuffer{eps, stat, rescale, thr});
+}
+
+__global__ __launch_bounds__(256) void sampler_step_eps_kernel(
+    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
+    const float* __restrict__ z, const long long* __restrict__ kidx, const float* __restrict__ ta,
+    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
+    const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, int HW,
+    int rescale, int thr) {
+    sampler_step_body<false, true>(nullptr, nullptr, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, nullptr,
+                                   0, HW, 0, 0, nullptr,
+                                   [z](int, size_t o) {
+                                       float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+                                       if (z) zz = *reinterpret_cast<const float4*>(z + o);
+                                       return zz;
+                                   },
+                                   EpsBuffer{eps, stat, rescale, thr});
+}
+
+__global__ __launch_bounds__(256) void sampler_step_eps_rng_kernel(
+    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
+    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
+    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
+    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, int HW, int rescale, int thr) {
+    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
+    const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
+    sampler_step_body<false, true>(nullptr, nullptr, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, nullptr,
+                                   0, HW, 0, 0, nullptr,
+                                   [seed, id, step](int i, size_t) {
+                                       float n[4];
+                                       vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
+                                       return make_float4(n[0], n[1], n[2], n[3]);
+                                   },
+                                   EpsBuffer{eps, stat, rescale, thr});
 }
 
 inline int chunks_for(int n4) {
@@ -1029,6 +1445,107 @@ int vf_sampler_step_cfg_rng(const float* unet_out, const int* off, const float* 
     hipLaunchKernelGGL(sampler_step_cfg_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
                        (hipStream_t)stream, unet_out, off, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev,
                        y_next, weights, Cout, HW, maxV, weighting, g);
+    VF_RETURN_LAST_ERROR();
+}
+
+// ---- dynamic thresholding / guidance rescaling (the head of this file) ----
+// eps [B][3][HW]; part: DEVICE double [B * 64 * 4]; g NULL: unguided (eps_g = eps_c, unet_out has off[B] rows);
+// fused: which tail follows (1 vf_p_sample_tail_eps(_rng), 0 vf_sampler_step_eps(_rng)), as in vf_sample_stat.
+int vf_compose_eps(const float* unet_out, const int* off, const float* g, float* eps, float* weights, double* part,
+                   int B, int Cout, int HW, int maxV, int weighting, int fused, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !eps || !part) return (int)hipErrorInvalidValue;
+    const dim3 grid(chunks_for(3 * HW / 4), B), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (g && fused)
+        hipLaunchKernelGGL((compose_eps_kernel<true, true>), grid, block, 0, st, unet_out, off, g, eps, weights, part,
+                           Cout, HW, maxV, weighting);
+    else if (g)
+        hipLaunchKernelGGL((compose_eps_kernel<true, false>), grid, block, 0, st, unet_out, off, g, eps, weights, part,
+                           Cout, HW, maxV, weighting);
+    else
+        hipLaunchKernelGGL((compose_eps_kernel<false, false>), grid, block, 0, st, unet_out, off, g, eps, weights, part,
+                           Cout, HW, maxV, weighting);
+    VF_RETURN_LAST_ERROR();
+}
+
+// stat [B][2] = {r_b, s_b}.  phi <= 0: no rescale; k < 0: no threshold; cmax: the cap on s_b (+inf for none).
+// idx = t (ta, tb = sqrt_recip_gammas, sqrt_recipm1_gammas; fused = 1) or kidx (ta, tb = the plan's a, b; fused = 0).
+int vf_sample_stat(const float* eps, const double* part, const float* y, const long long* idx, const float* ta,
+                   const float* tb, float* stat, int B, int HW, float phi, int k, float frac, float cmax, int fused,
+                   void* stream) {
+    if (B <= 0) return 0;
+    const long long n = 3ll * HW;
+    if (HW <= 0 || (HW & 3) || n > 0x7fffffffll || !stat || !eps || !y) return (int)hipErrorInvalidValue;
+    if (phi > 0.0f && (!part || !(phi <= 1.0f))) return (int)hipErrorInvalidValue;
+    if (k >= 0 && (k >= n || !(frac >= 0.0f && frac < 1.0f) || (frac != 0.0f && k + 1 >= n) || !(cmax >= 1.0f) || !idx ||
+                   !ta || !tb))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_stat_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, eps, part,
+                       chunks_for(3 * HW / 4), y, idx, ta, tb, (float2*)stat, (int)n, phi, k, frac, cmax, fused);
+    VF_RETURN_LAST_ERROR();
+}
+
+// out[b] = x_s[k] + frac (x_s[k+1] - x_s[k]), x_s = sort(|x[b][0..n)|): the selection of vf_sample_stat on a plain buffer
+int vf_abs_quantile(const float* x, int B, int n, int k, float frac, float* out, void* stream) {
+    if (B <= 0) return 0;
+    if (n <= 0 || k < 0 || k >= n || !(frac >= 0.0f && frac < 1.0f) || (frac != 0.0f && k + 1 >= n) || !x || !out)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(abs_quantile_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, x, out, n, k, frac);
+    VF_RETURN_LAST_ERROR();
+}
+
+static inline bool eps_tail_args_ok(const float* eps, const float* stat, int HW, int rescale, int thr) {
+    return HW > 0 && !(HW & 3) && eps && (stat || !(rescale || thr));
+}
+
+int vf_p_sample_tail_eps(const float* eps, const float* stat, const float* y_t, const float* z, const long long* t,
+                         const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                         const float* posterior_log_variance, const float* posterior_mean_coef1,
+                         const float* posterior_mean_coef2, float* y_next, float* mean_out, int B, int HW, int clip,
+                         int rescale, int thr, void* stream) {
+    if (B <= 0) return 0;
+    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(p_sample_tail_eps_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream, eps,
+                       (const float2*)stat, y_t, z, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
+                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, HW, clip, rescale, thr);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_p_sample_tail_eps_rng(const float* eps, const float* stat, const float* y_t, unsigned long long seed,
+                             const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                             const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                             const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
+                             float* mean_out, int B, int HW, int clip, int rescale, int thr, void* stream) {
+    if (B <= 0) return 0;
+    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(p_sample_tail_eps_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       eps, (const float2*)stat, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas,
+                       posterior_log_variance, posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, HW, clip,
+                       rescale, thr);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_sampler_step_eps(const float* eps, const float* stat, const float* y_t, const float* z, const long long* kidx,
+                        const float* a, const float* b, const float* cy, const float* c0, const float* c1,
+                        const float* sigma, float* y0_prev, float* y_next, int B, int HW, int rescale, int thr,
+                        void* stream) {
+    if (B <= 0) return 0;
+    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr) || !y_next) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sampler_step_eps_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream, eps,
+                       (const float2*)stat, y_t, z, kidx, a, b, cy, c0, c1, sigma, y0_prev, y_next, HW, rescale, thr);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_sampler_step_eps_rng(const float* eps, const float* stat, const float* y_t, unsigned long long seed,
+                            const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                            const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                            float* y0_prev, float* y_next, int B, int HW, int rescale, int thr, void* stream) {
+    if (B <= 0) return 0;
+    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr) || !y_next) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(sampler_step_eps_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
+                       eps, (const float2*)stat, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev, y_next, HW,
+                       rescale, thr);
     VF_RETURN_LAST_ERROR();
 }
 

@@ -39,14 +39,16 @@ def _eval_mode(model):
 # reverse step i) so that its output can be compared with the CPU oracle.  seed= (and sample_ids=) reach generate() the
 # same way: the draws then come from the counter-based generator of csrc/rng.h, keyed per sample.  So do sample_steps= /
 # solver= / eta= (few-step sampling: K steps over a sub-sequence of the trained schedule instead of all T) and guidance=
-# (classifier-free guidance: a scale, or one per sample; ViewFusion.generate).
+# (classifier-free guidance: a scale, or one per sample; ViewFusion.generate), and with it threshold= / threshold_max= /
+# guidance_rescale= (dynamic thresholding of y0_hat, the guided noise rescaled; ViewFusion.generate).
 @torch.no_grad()
 def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None, **inject):
     """Generate with MORE views than the model was trained on (view_count ~ U[max_views+1, 24)),
     experiment.py:472-488.
     cond (B,23,3,H,W), angle (B,1) -> (generated_batch (B,1+k,3,H,W), logit_arr, weight_arr, view_count).
     **inject reaches generate(): y_t, z_seq, seed, sample_ids, use_graph, sample_steps / solver / eta for a
-    few-step chain and guidance (a classifier-free guidance scale, or one per sample) (ViewFusion.generate)."""
+    few-step chain, guidance (a classifier-free guidance scale, or one per sample) and threshold / threshold_max /
+    guidance_rescale (ViewFusion.generate)."""
     B = cond.shape[0]
     if view_count is None:
         view_count = torch.randint(max_views + 1, 24, (B,), generator=generator)
@@ -58,14 +60,16 @@ def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None
 
 @torch.no_grad()
 def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, seed=None, sample_ids=None,
-                           sample_steps=None, solver="ddim", eta=0.0, guidance=None):
+                           sample_steps=None, solver="ddim", eta=0.0, guidance=None, threshold=None,
+                           threshold_max=None, guidance_rescale=None):
     """Start from ONE view and synthesise the orbit view by view, feeding every sample back as an
     extra conditioning view (count = 1 .. steps; angle = 2*pi/24 * count), experiment.py:516-544.
     first_view (B,3,H,W) -> samples (B,steps,3,H,W).  y_t / z_seq: per-count lists of injected randomness.
     seed: the draws of rollout step `count` of object b use the id sample_ids[b] * steps + count - 1 (sample_ids
     defaults to arange(B)), so every step of every object has noise of its own, independent of the batch.
     sample_steps / solver / eta: the few-step sampler of every generate() call (`steps` is the rollout length).
-    guidance: the classifier-free guidance scale of every generate() call (a number, or one per object)."""
+    guidance: the classifier-free guidance scale of every generate() call (a number, or one per object).
+    threshold / threshold_max / guidance_rescale: likewise, of every generate() call (ViewFusion.generate)."""
     cond = first_view[:, None].contiguous()
     B = cond.shape[0]
     out = []
@@ -84,6 +88,10 @@ def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, se
                 inject.update(sample_steps=sample_steps, solver=solver, eta=eta)
             if guidance is not None:
                 inject.update(guidance=guidance)
+            for name, val in (("threshold", threshold), ("threshold_max", threshold_max),
+                              ("guidance_rescale", guidance_rescale)):
+                if val is not None:
+                    inject[name] = val
             *_, sample = model(y_cond=cond, view_count=view_count, angle=angle, generate=True, **inject)
             cond = torch.cat((cond, sample[:, None]), dim=1)
             out.append(sample)
@@ -98,7 +106,7 @@ def orbit_frames(model, all_views, n=24, **inject):
     -> (generated_batch (n,1+k,3,H,W) clamped to [0,1], logit_arr, weight_arr, cond_views (n,6,3,H,W), angles (n,1));
     the frame i of the animation shows weight_arr[i] next to cond_views[i] and generated_batch[i].
     **inject reaches generate() (sample_steps / solver / eta among it: 24 frames in K instead of T steps; guidance: a
-    classifier-free guidance scale, or one per frame)."""
+    classifier-free guidance scale, or one per frame; threshold / threshold_max / guidance_rescale with it)."""
     assert all_views.shape[0] == 24 and n % 24 == 0
     dev = all_views.device
     angles = torch.tensor([2 * math.pi / n * i for i in range(n)], dtype=torch.float32, device=dev).unsqueeze(1)
@@ -254,7 +262,7 @@ def _barrier():
 
 @torch.no_grad()
 def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, seed=None, lpips=None,
-             guidance=None, **inject):
+             guidance=None, threshold=None, threshold_max=None, guidance_rescale=None, **inject):
     """The eval reduction of Experiment.eval (experiment.py:314-370): every rank generates its shard of the validation
     batches (view_count ~ U[1, max_views] per sample), PSNR per image on the GPU (utils/metrics.py:6-8), mean over the
     rank's images, barrier, all_reduce(AVG) of the scalars, barrier.  `batches`: iterable of dicts with target (B,3,H,W),
@@ -270,9 +278,14 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ss
     sample_steps / solver / eta (through **inject): evaluate with a K-step sampler (ViewFusion.generate); which K is
     good enough for a checkpoint is what this function measures.
     guidance (default None: the unguided sampler): a classifier-free guidance scale for every generate() call -- which
-    scale suits a checkpoint trained with set_cond_dropout is, likewise, what this function measures."""
+    scale suits a checkpoint trained with set_cond_dropout is, likewise, what this function measures.
+    threshold / threshold_max / guidance_rescale (default None: off): dynamic thresholding and guidance rescaling of
+    every generate() call (ViewFusion.generate) -- what keeps a sweep over g > 1 from measuring saturation alone."""
     if guidance is not None:
         inject = dict(inject, guidance=guidance)
+    for name, val in (("threshold", threshold), ("threshold_max", threshold_max), ("guidance_rescale", guidance_rescale)):
+        if val is not None:
+            inject[name] = val
     gen, gt = [], []
     seen = 0
     with _eval_mode(model):                        # Experiment.eval: self.model.eval() (experiment.py:316)

@@ -73,6 +73,9 @@ _CALL_KIND = {"vf_wino44_pack_weights": "pack", "vf_wino44_pack_weights_multi": 
               "vf_stack_views_cfg": "diffusion", "vf_draw_cond_drop": "diffusion", "vf_p_sample_tail_cfg": "diffusion",
               "vf_p_sample_tail_cfg_rng": "diffusion", "vf_sampler_step_cfg": "diffusion",
               "vf_sampler_step_cfg_rng": "diffusion",
+              "vf_compose_eps": "diffusion", "vf_sample_stat": "diffusion", "vf_abs_quantile": "diffusion",
+              "vf_p_sample_tail_eps": "diffusion", "vf_p_sample_tail_eps_rng": "diffusion",
+              "vf_sampler_step_eps": "diffusion", "vf_sampler_step_eps_rng": "diffusion",
               "vf_grad_sumsq_multi": "adam", "vf_grad_norm_finish": "adam", "vf_adam_multi_ex": "adam",
               "vf_adam_multi_ex_dev": "adam", "vf_adam_set_scalars_ex": "adam", "vf_swap_multi": "adam", "vf_grad_accum_multi": "adam"}
 

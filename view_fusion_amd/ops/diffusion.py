@@ -2,6 +2,7 @@
 and SSIM (reference model/view_fusion.py:70-177, 229-300; utils/metrics.py:6-12)."""
 import ctypes
 import math
+import struct
 
 import torch
 
@@ -219,6 +220,102 @@ def _check_guidance(guidance, unet_out, B, S):
                          f"for S = {int(S)} views of {B} samples")
 
 
+# ---- dynamic thresholding / guidance rescaling (csrc/diffusion.hip holds the definition) ----
+def quantile_position(n, q):
+    """The two order statistics behind the q-quantile of n values, torch.quantile's linear interpolation:
+    pos = q (n - 1) in float64, -> (k, frac) with k = floor(pos) and frac = float32(pos - k) in [0, 1); the quantile is
+    x[k] + frac (x[k+1] - x[k]).  frac == 0 wherever x[k+1] would not exist (q = 1, n = 1); a frac that rounds to 1 in
+    float32 is handed back as (k + 1, 0)."""
+    n, q = int(n), float(q)
+    if n < 1:
+        raise ValueError(f"a quantile needs at least one value, got n = {n}")
+    if not 0.0 <= q <= 1.0:                        # (also refuses NaN)
+        raise ValueError(f"a quantile level must be in [0, 1], got {q}")
+    pos = q * (n - 1)
+    k = int(math.floor(pos))
+    frac = struct.unpack("f", struct.pack("f", pos - k))[0]
+    if frac >= 1.0:
+        k, frac = k + 1, 0.0
+    if k >= n - 1:
+        k, frac = n - 1, 0.0
+    return k, frac
+
+
+def abs_quantile(x, q):
+    """The q-quantile (q in [0, 1]) of |x| along the last dimension of a (B, n) tensor -> (B,), as
+    torch.quantile(x.abs(), q, dim=1) defines it: exact radix selection of the two order statistics on the device, one
+    workgroup per row, no sort, no host sync; the same bits on every call.  (The selection of the reverse step's dynamic
+    threshold on a plain buffer; on its own e.g. a percentile stretch.)"""
+    if x.dim() != 2:
+        raise ValueError(f"abs_quantile takes a (B, n) tensor, got {tuple(x.shape)}")
+    B, n = x.shape
+    k, frac = quantile_position(n, q)
+    x = _c(x)
+    _check(x)
+    out = torch.empty(B, device=x.device, dtype=torch.float32)
+    _call("vf_abs_quantile", _ptr(x), B, n, k, frac, _ptr(out), _stream())
+    return out
+
+
+def threshold_settings(threshold=None, threshold_max=None, guidance_rescale=None, guided=False, clip=True):
+    """The checked settings of a reverse step's dynamic threshold and guidance rescale -> (q | None, cmax, phi):
+    q in (0, 1] the quantile level (None: off, the static clamp), cmax >= 1 the cap on the threshold (inf: none),
+    phi in (0, 1] the rescale strength (0.0: off; guidance_rescale=0 is "off").  ValueError for anything else, for a
+    rescale without guidance, a cap without a threshold, and a threshold with clip_denoised=False.  Host only."""
+    q, cmax, phi = None, math.inf, 0.0
+    if threshold is not None:
+        q = float(threshold)
+        if not 0.0 < q <= 1.0:
+            raise ValueError(f"threshold (the quantile of |y0_hat|) must be in (0, 1], got {q}")
+        if not clip:
+            raise ValueError("threshold= replaces the clamp of y0_hat: it cannot be combined with clip_denoised=False")
+    if threshold_max is not None:
+        cmax = float(threshold_max)
+        if not cmax >= 1.0:
+            raise ValueError(f"threshold_max must be >= 1, got {cmax}")
+        if q is None:
+            raise ValueError("threshold_max= caps the dynamic threshold: it needs threshold=")
+    if guidance_rescale is not None:
+        phi = float(guidance_rescale)
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f"guidance_rescale must be in [0, 1], got {phi}")
+        if phi > 0.0 and not guided:
+            raise ValueError("guidance_rescale= rescales the guided noise: it needs guidance=")
+    return q, cmax, phi
+
+
+def threshold_scratch(y):
+    """What the thresholded / rescaled step keeps between its three launches, for a batch like y (B,3,H,W): the composed
+    eps, the partial sums and stat = {r_b, s_b}.  generate() makes it once per call."""
+    B = y.shape[0]
+    return dict(eps=torch.empty_like(y), part=torch.empty(B * 64 * 4, device=y.device, dtype=torch.float64),
+                stat=torch.empty(B, 2, device=y.device, dtype=torch.float32))
+
+
+def _eps_front(unet_out, off, y, idx, ta, tb, B, max_views, weighting, want_weights, guidance, q, cmax, phi, scratch,
+               fused):
+    """The two launches in front of an *_eps tail: the composed (+ guided) eps with the weights and the partial sums,
+    then the per-sample statistics -> (scratch, weights | None).  fused: how that tail rounds y0_hat (the ancestral
+    one fuses, the few-step one does not; csrc/diffusion.hip, y0_hat_as)."""
+    _, Cout, H, W = unet_out.shape
+    if scratch is None:
+        scratch = threshold_scratch(y)
+    eps, part, stat = scratch["eps"], scratch["part"], scratch["stat"]
+    _check(eps, stat)
+    if eps.shape != y.shape or stat.numel() != 2 * B or part.dtype != torch.float64 or part.numel() < B * 64 * 4 \
+            or not part.is_cuda or not part.is_contiguous():
+        raise ValueError("scratch= does not fit this batch (ops.threshold_scratch(y))")
+    wts = None
+    if weighting and want_weights:
+        wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)
+    _call("vf_compose_eps", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(guidance), _ptr(eps), _ptr(wts),
+          ctypes.c_void_p(part.data_ptr()), B, Cout, H * W, max_views, int(weighting), int(fused), _stream())
+    k, frac = (-1, 0.0) if q is None else quantile_position(3 * H * W, q)
+    _call("vf_sample_stat", _ptr(eps), ctypes.c_void_p(part.data_ptr()), _ptr(y), ctypes.c_void_p(idx.data_ptr()),
+          _ptr(ta), _ptr(tb), _ptr(stat), B, H * W, phi, k, frac, cmax, int(fused), _stream())
+    return scratch, wts
+
+
 class _ComposeLossFn(torch.autograd.Function):
     """MSE(target, compose(unet_out)) fused: softmax over each sample's views (or mean)."""
 
@@ -324,13 +421,20 @@ def compose(unet_out, off, B, max_views, weighting, want_weights=True):
 
 
 def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip=True, want_weights=True,
-                  want_mean=False, inplace=False, seed=None, ids=None, guidance=None, S=None):
+                  want_mean=False, inplace=False, seed=None, ids=None, guidance=None, S=None, threshold=None,
+                  threshold_max=None, guidance_rescale=None, scratch=None):
     """Fused compose -> y0_hat -> clamp -> posterior mean -> + z*sigma.
     Returns (y_next, mean | None, weights | None).  seed= (with z=None): z is drawn inside the kernel from
     (seed, ids[b], t[b], element) and is 0 where t[b] == 0; ids defaults to arange(B).
     guidance (device fp32 (B,), ops.guidance_scales) with S= (view_offsets' S = off[B], checked against unet_out's row
     count): unet_out has S + B rows, the null rows last, and the composed noise is g eps_c + (1 - g) eps_u
-    (classifier-free guidance); the weights stay the conditional ones."""
+    (classifier-free guidance); the weights stay the conditional ones.
+    threshold (q in (0, 1], optional threshold_max >= 1) / guidance_rescale (phi in (0, 1], needs guidance): dynamic
+    thresholding of y0_hat in place of the static clamp / the guided noise rescaled to the conditional one's standard
+    deviation (csrc/diffusion.hip holds the definition).  Either one runs three launches instead of one -- the composed
+    eps (+ weights), the per-sample statistics, the tail on the eps buffer; scratch= (ops.threshold_scratch) lets a loop
+    allocate their buffers once."""
+    q, cmax, phi = threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip)
     _check(unet_out, y_t, z)
     if guidance is not None:
         _check_guidance(guidance, unet_out, B, S)
@@ -342,6 +446,21 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
     t = _c(t.to(torch.int64))
     y_next = y_t if inplace else torch.empty_like(y_t)     # elementwise: safe to overwrite y_t
     mean = torch.empty_like(y_t) if want_mean else None
+    if q is not None or phi > 0.0:
+        scratch, wts = _eps_front(unet_out, off, y_t, t, sched["sqrt_recip_gammas"], sched["sqrt_recipm1_gammas"], B,
+                                  max_views, weighting, want_weights, guidance, q, cmax, phi, scratch, True)
+        tabs = [_ptr(sched[n]) for n in ("sqrt_recip_gammas", "sqrt_recipm1_gammas", "posterior_log_variance_clipped",
+                                         "posterior_mean_coef1", "posterior_mean_coef2")]
+        tail = (_ptr(y_next), _ptr(mean), B, H * W, int(clip), int(phi > 0.0), int(q is not None), _stream())
+        if seed is not None:
+            ids = sample_ids(y_t.device, B, ids)
+            _check_ids(ids, B)
+            _call("vf_p_sample_tail_eps_rng", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y_t), _seed(seed),
+                  ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(t.data_ptr()), *tabs, *tail)
+        else:
+            _call("vf_p_sample_tail_eps", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y_t), _ptr(z),
+                  ctypes.c_void_p(t.data_ptr()), *tabs, *tail)
+        return y_next, mean, wts
     wts = None
     if weighting and want_weights:
         wts = torch.empty(B, max_views, 3, H, W, device=y_t.device, dtype=torch.float32)
@@ -363,14 +482,17 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
 
 
 def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_prev=None, want_weights=True,
-                 inplace=False, seed=None, ids=None, guidance=None, S=None):
+                 inplace=False, seed=None, ids=None, guidance=None, S=None, threshold=None, threshold_max=None,
+                 guidance_rescale=None, scratch=None):
     """One step of a few-step sampler (strided DDIM / DPM-Solver++ 2M), fused like p_sample_tail:
     compose -> y0 = clamp(a[k] y - b[k] eps) -> y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z, k = kidx[b].
     tables: the fp32 device tables a, b, cy, c0, c1, sigma (K,) and tau (K,) int64 (ViewFusion._sampler_plan).
     y0_prev (like y, optional): the multistep history, updated in place; it is not read where c1[k] == 0.
     Returns (y_next, weights | None).  seed= (with z=None): z is drawn inside the kernel from
     (seed, ids[b], tau[k], element); where sigma[k] == 0 no z is loaded or drawn at all.
-    guidance (device fp32 (B,)) with S=: the guided tail, as in p_sample_tail."""
+    guidance (device fp32 (B,)) with S=: the guided tail, as in p_sample_tail.
+    threshold / threshold_max / guidance_rescale / scratch: as in p_sample_tail; y0_prev receives the thresholded y0."""
+    q, cmax, phi = threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None)
     _check(unet_out, y, z, y0_prev, *(tables[n] for n in ("a", "b", "cy", "c0", "c1", "sigma")))
     if guidance is not None:
         _check_guidance(guidance, unet_out, B, S)
@@ -380,6 +502,24 @@ def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_
     _, Cout, H, W = unet_out.shape
     kidx = _c(kidx.to(torch.int64))
     y_next = y if inplace else torch.empty_like(y)         # elementwise: safe to overwrite y
+    if q is not None or phi > 0.0:
+        scratch, wts = _eps_front(unet_out, off, y, kidx, tables["a"], tables["b"], B, max_views, weighting,
+                                  want_weights, guidance, q, cmax, phi, scratch, False)
+        tabs = [_ptr(tables[n]) for n in ("a", "b", "cy", "c0", "c1", "sigma")]
+        tail = (_ptr(y0_prev), _ptr(y_next), B, H * W, int(phi > 0.0), int(q is not None), _stream())
+        if seed is not None:
+            ids = sample_ids(y.device, B, ids)
+            _check_ids(ids, B)
+            tau = tables["tau"]
+            if not tau.is_cuda or tau.dtype != torch.int64 or not tau.is_contiguous():
+                raise _lib.VFHipError("tables['tau'] must be a contiguous device int64 tensor")
+            _call("vf_sampler_step_eps_rng", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y), _seed(seed),
+                  ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(kidx.data_ptr()), ctypes.c_void_p(tau.data_ptr()),
+                  *tabs, *tail)
+        else:
+            _call("vf_sampler_step_eps", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y), _ptr(z),
+                  ctypes.c_void_p(kidx.data_ptr()), *tabs, *tail)
+        return y_next, wts
     wts = None
     if weighting and want_weights:
         wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)

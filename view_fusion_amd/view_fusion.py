@@ -27,6 +27,10 @@ Classifier-free guidance (csrc/diffusion.hip holds the definition; both halves o
 the launches it ran before): `set_cond_dropout(p)` zeroes the conditioning views of a training sample with probability
 p, and `generate(..., guidance=g)` (also `forward(generate=True)`, `p_sample`, `p_mean_variance`) runs one unconditional
 row per sample next to the conditional ones and extrapolates the noise prediction, g eps_c + (1 - g) eps_u.
+`threshold=q` (optional `threshold_max=c`) and `guidance_rescale=phi` on the same four entry points are the two remedies
+for what g > 1 does to a pixel-space sample: dynamic thresholding of y0_hat (clamp to the per-sample q-quantile of
+|y0_hat|, then divide by it) in place of the static clamp, and the guided noise rescaled to the conditional one's
+standard deviation.  Both off by default; both defined at the head of csrc/diffusion.hip.
 """
 import torch
 from torch import nn
@@ -157,21 +161,28 @@ class ViewFusion(nn.Module):
                                               null_rows=null_rows)
         return x, self.denoise_fn(x, angle_s, level_s)
 
-    def p_mean_variance(self, y_t, y_cond, view_count, angle, t, clip_denoised: bool, guidance=None):
-        """guidance (a scale, or one per sample): the mean of the guided step; logits are the S conditional rows'."""
+    def p_mean_variance(self, y_t, y_cond, view_count, angle, t, clip_denoised: bool, guidance=None, threshold=None,
+                        threshold_max=None, guidance_rescale=None):
+        """guidance (a scale, or one per sample): the mean of the guided step; logits are the S conditional rows'.
+        threshold / threshold_max / guidance_rescale: as in generate()."""
         from . import ops
+        ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
+        dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
         _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None)
         w_on = bool(self.weighting_inference)
         _, mean, weights = ops.p_sample_tail(out, off, y_t, None, t, self._sched(), y_t.shape[0], max_v, w_on,
-                                             clip=clip_denoised, want_mean=True, guidance=gs, S=S)
+                                             clip=clip_denoised, want_mean=True, guidance=gs, S=S, **dyn)
         logits = out[:S, 3:, ...] if w_on else None
         return mean, self._at(self.posterior_log_variance_clipped, t), logits, weights
 
     @torch.no_grad()
-    def p_sample(self, y_t, y_cond, view_count, angle, t, clip_denoised=True, z=None, guidance=None):
+    def p_sample(self, y_t, y_cond, view_count, angle, t, clip_denoised=True, z=None, guidance=None, threshold=None,
+                 threshold_max=None, guidance_rescale=None):
         from . import ops
+        ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
+        dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
         _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None)
@@ -181,12 +192,13 @@ class ViewFusion(nn.Module):
             z = None
         w_on = bool(self.weighting_inference)
         y, _, weights = ops.p_sample_tail(out, off, y_t, z, t, self._sched(), y_t.shape[0], max_v, w_on,
-                                          clip=clip_denoised, guidance=gs, S=S)
+                                          clip=clip_denoised, guidance=gs, S=S, **dyn)
         return y, (out[:S, 3:, ...] if w_on else None), weights
 
     @torch.no_grad()
     def generate(self, y_cond, view_count, angle, y_t=None, sample_num=8, z_seq=None, use_graph=None, seed=None,
-                 sample_ids=None, sample_steps=None, solver="ddim", eta=0.0, guidance=None):
+                 sample_ids=None, sample_steps=None, solver="ddim", eta=0.0, guidance=None, threshold=None,
+                 threshold_max=None, guidance_rescale=None):
         """Reverse diffusion over all T steps (reference view_fusion.py:179-214).
 
         use_graph (default: on for GPU tensors with S <= 16 stacked views): one reverse step -- level gather, re-stack of
@@ -210,8 +222,19 @@ class ViewFusion(nn.Module):
         every tail (ancestral or few-step, loaded or drawn z) uses eps = g eps_c + (1 - g) eps_u.  g = 1 is the
         unguided sampler, g = 0 the unconditional model, g > 1 extrapolates.  The returned logits are those of the S
         real rows and the weights stay the conditional softmax; the use_graph default compares S + B.
+
+        threshold (default None: the static clamp to [-1, 1]): q in (0, 1] -- dynamic thresholding, every step: s = the
+        q-quantile of |y0_hat| over the sample's 3 H W values (torch.quantile's interpolation), at least 1 and at most
+        threshold_max (c >= 1) when that is given; y0 = clamp(y0_hat, -s, s) / s.
+        guidance_rescale (default None; 0 is "off"; needs guidance): phi in (0, 1] -- the guided noise is multiplied by
+        phi sigma(eps_c) / sigma(eps_g) + 1 - phi, per sample, which takes its standard deviation back to (phi = 1) the
+        conditional prediction's.  Either one turns the tail into three launches (composed eps, per-sample statistics,
+        tail) that stay inside the captured step; their scratch buffers are made once per call.  Both combine with
+        everything above.  No schedule of q / phi over the steps.
         """
         from . import ops
+        q_on, _, phi = ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None)
+        dyn = {}
         plan = tau = None
         if sample_steps is not None:                      # argument errors first: nothing has been launched yet
             _schedule.check_sampler(solver, eta)
@@ -244,6 +267,9 @@ class ViewFusion(nn.Module):
             hist = torch.empty_like(y) if plan["multistep"] else None      # y0 of the step before; never read first
             if not any(plan["noisy"]):                    # eta = 0: no z anywhere -- no buffer, no draw
                 z_seed = z = None
+        if q_on is not None or phi > 0.0:                 # the three-launch tail and what it keeps between its launches
+            dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale,
+                       scratch=ops.threshold_scratch(y))
         y_cond = y_cond.contiguous()
         angle = angle.contiguous()
         # the conditioning half of the stacked input never changes: copy it once (guided: the null rows' zeros too)
@@ -253,10 +279,10 @@ class ViewFusion(nn.Module):
             _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False, levels=levels, null_rows=guided)
             if plan is not None:
                 _, weights = ops.sampler_step(out, off, y, z, t, plan, b, max_v, w_on, y0_prev=hist, inplace=True,
-                                              seed=z_seed, ids=ids, guidance=gs, S=S)
+                                              seed=z_seed, ids=ids, guidance=gs, S=S, **dyn)
                 return out, weights
             _, _, weights = ops.p_sample_tail(out, off, y, z, t, sched, b, max_v, w_on, inplace=True, seed=z_seed,
-                                              ids=ids, guidance=gs, S=S)
+                                              ids=ids, guidance=gs, S=S, **dyn)
             return out, weights
 
         graph = None
@@ -304,11 +330,12 @@ class ViewFusion(nn.Module):
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
                 z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0,
-                guidance=None, cond_drop=None):
+                guidance=None, cond_drop=None, threshold=None, threshold_max=None, guidance_rescale=None):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
             return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
                                  sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta,
-                                 guidance=guidance)
+                                 guidance=guidance, threshold=threshold, threshold_max=threshold_max,
+                                 guidance_rescale=guidance_rescale)
         from . import ops
         b = y_0.shape[0]
         dev = y_0.device
