@@ -6,16 +6,34 @@
 // All HBM-bound and tiny next to the UNet; their point is that NOTHING here needs a host
 // sync: ragged view counts come in as a device prefix-sum array `off[B+1]`.
 //
-// Seeded draws (rng.h: Philox4x32-10 keyed by seed and a per-sample id): draw_train, randn_ids and the reverse-step
-// tail that computes its own z.  Opt-in; the unseeded kernels and entry points are untouched.
-//
-// Few-step sampling: sampler_step(_rng)_kernel is the same tail with a table-driven linear-multistep update
-// (strided DDIM / DPM-Solver++ 2M) instead of the one-step DDPM posterior; the p_sample_tail kernels stay as they are.
-//
-// Loss options (loss_weight.h holds the specification): compose_loss_fwd / _finish / _bwd are siblings of the MSE
-// kernels with a penalty template (mse / l1 / huber), a per-sample noise-level weight (min-SNR, P2), the per-sample
-// loss handed back and an optional loss-by-level histogram -- same launch count, no atomics.  Opt-in; the MSE kernels
-// and their entry points are untouched.
+// A map of this file, in the order of the file:
+//   stacking        stack_views_kernel (on the training step) and stack_views_cfg_kernel, the same kernel with
+//                   conditioning dropout and null rows -- two kernels on purpose: behind a shared body the compiler
+//                   generates other code for the plain one (profiles/tail_templates.md); draw_cond_drop_kernel.
+//   composition     compose4 (softmax over the views, or the mean), guide4, write_weights (the softmax weights handed
+//                   back by the tails; compose_fwd_kernel and compose_eps_kernel keep that loop written out, for the
+//                   same reason).
+//   training loss   compose_fwd / loss_finish / compose_mse_bwd: the MSE pair of the benchmarked step; further down their
+//                   siblings compose_loss_fwd / _finish / _bwd<PEN> with a penalty (mse / l1 / huber), a per-sample
+//                   noise-level weight (min-SNR, P2), the per-sample loss and a loss-by-level histogram -- same launch
+//                   count, no atomics; loss_weight.h holds the specification.
+//   step arithmetic y0_hat, y0_hat_as, posterior_update, multistep_base / _add: how each product and sum of a reverse
+//                   step is rounded, and why it is written operation by operation; EpsBound / EpsBuffer: what a tail on
+//                   the eps buffer knows about its sample.
+//   the tails       p_sample_tail_kernel<CFG, EPS, RNG> (ancestral: the one-step DDPM posterior) and
+//                   sampler_step_kernel<CFG, EPS, RNG> (few-step: a table-driven linear-multistep update, strided DDIM /
+//                   DPM-Solver++ 2M).  Three switches: CFG -- the composed eps is guided by the sample's null row; EPS --
+//                   eps is read back from the composed-eps pass (rescaled, dynamically thresholded) instead of composed
+//                   here, which implies !CFG; RNG -- z is drawn in the kernel (rng.h: Philox4x32-10 keyed by seed and a
+//                   per-sample id) instead of loaded.  Six instantiations of each.  In front of them the two noise sources
+//                   (load_z, draw_z) and the common prologue (tail_sample, tail_eps).
+//   draws, metrics  draw_train, randn_ids, philox_ids (rng.h), gather_level, psnr.
+//   three launches  compose_eps_kernel<CFG, FUSED_TAIL> -> sample_stat_kernel (abs_select, quantile_lerp; the same
+//                   selection on a plain buffer: abs_quantile_kernel) -> an EPS tail: the thresholded / rescaled step.
+//   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
+//                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
+//                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.
+// With every option off a path runs the launches and the bits it ran before the option existed.
 //
 // Classifier-free guidance (Ho & Salimans, "Classifier-Free Diffusion Guidance").  This comment is the ONE written
 // definition; tests/guidance_ref.py restates it.  Opt-in: siblings of the kernels above, which are untouched.
@@ -207,6 +225,24 @@ __device__ __forceinline__ float4 compose4(const float* __restrict__ out, int Co
     return make_float4(acc.x * inv.x, acc.y * inv.y, acc.z * inv.z, acc.w * inv.w);
 }
 
+// The softmax weights of float4 i = (c, p) of sample b into weights[B][maxV][3][HW], zero for the views the sample does
+// not have; (mx, inv) as compose4 hands them back.
+__device__ __forceinline__ void write_weights(const float* __restrict__ out, float* __restrict__ weights, int Cout,
+                                              int HW, int maxV, int v0, int v1, int c, int p, int i,
+                                              const float4& mx, const float4& inv) {
+    const int b = blockIdx.y;
+    const size_t vs = (size_t)Cout * HW;
+    for (int j = 0; j < maxV; ++j) {
+        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (v0 + j < v1) {
+            const float4 l = *reinterpret_cast<const float4*>(out + (size_t)(v0 + j) * vs + (size_t)(3 + c) * HW + p);
+            w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
+                            expf(l.w - mx.w) * inv.w);
+        }
+        *reinterpret_cast<float4*>(weights + (((size_t)b * maxV + j) * 3) * HW + 4 * (size_t)i) = w;
+    }
+}
+
 // grid (chunks, B).  Writes noise_hat[B][3][HW]; optional weights[B][maxV][3][HW] (zero padded);
 // optional per-block partial sums of (target - noise_hat)^2 into loss_part[B*chunks].
 __global__ __launch_bounds__(256) void compose_fwd_kernel(const float* __restrict__ out, const int* __restrict__ off,
@@ -390,47 +426,106 @@ struct EpsBuffer {
     }
 };
 
-// One reverse step after the UNet: compose -> y0_hat = a_t y_t - b_t eps -> clamp ->
-// mean = c1 y0_hat + c2 y_t -> y_{t-1} = mean + z * exp(0.5 logvar).
-// `noise(i, o)` gives z for float4 i of the sample (o = its float offset in [B][3][HW]): a load, or a Philox draw.
-// CFG: `out` has off[B] + B rows and the composed eps is guided by the sample's null row with the scale gscale[b].
-// EPS (the source of eps): false -- composed (+ guided) here from `out`, static clamp, weights written; true -- read
-// back from the composed-eps pass through `src` (EpsBuffer below: rescale, dynamic threshold), and `out`, `off`,
-// `weights`, `gscale` and the four ints after `weights` are not touched.  Everything from y0 on is shared.
-template <bool CFG, bool EPS = false, class Noise>
-__device__ __forceinline__ void p_sample_tail_body(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
-    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
-    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip, const float* __restrict__ gscale,
-    Noise noise, EpsBuffer src = EpsBuffer{}) {
-    const int b = blockIdx.y;
+// ---- the reverse-step tails: two kernel templates, three switches each ----
+//   CFG: `out` has off[B] + B rows and the composed eps is guided by the sample's null row with the scale gscale[b].
+//   EPS (the source of eps, implies !CFG): false -- composed (+ guided) here from `out`, static clamp, weights written;
+//        true -- read back from the composed-eps pass (eps_buf, stat, rescale, thr: EpsBuffer above; dynamic threshold),
+//        and `out`, `off`, `weights`, `gscale`, Cout, maxV and weighting are not touched.
+//   RNG: false -- z is loaded (z == null: no noise); true -- z is drawn here from (seed, ids[b], step, float4 index).
+// Every instantiation has the one argument list; what its switches do not use is dead (the launchers pass null / 0).
+// t / kidx / ids / stat live in device memory, so a captured launch replays for every step.  grid (chunks, B).
+
+// The two noise sources, each defined here and nowhere else: noise(i, o) gives z for float4 i of the sample
+// (o = its float offset in [B][3][HW]).  Loaded: z[o], and no buffer is no noise.  Drawn: Philox, kind 3, block = the
+// float4 index, keyed by the sample's id and the tail's `step`; ZERO_AT_0 (the ancestral chain): z = 0 where step == 0.
+__device__ __forceinline__ auto load_z(const float* z) {
+    return [z](int, size_t o) {
+        float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (z) zz = *reinterpret_cast<const float4*>(z + o);
+        return zz;
+    };
+}
+template <bool ZERO_AT_0>
+__device__ __forceinline__ auto draw_z(unsigned long long seed, unsigned long long id, long long step) {
+    return [seed, id, step](int i, size_t) {
+        float n[4] = {0.f, 0.f, 0.f, 0.f};
+        if (!ZERO_AT_0 || step != 0) vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)step, (uint32_t)i, n);
+        return make_float4(n[0], n[1], n[2], n[3]);
+    };
+}
+template <bool RNG, bool ZERO_AT_0>
+__device__ __forceinline__ auto tail_noise(const float* z, unsigned long long seed, const long long* ids,
+                                           long long step) {
+    if constexpr (RNG) return draw_z<ZERO_AT_0>(seed, (unsigned long long)ids[blockIdx.y], step);
+    else return load_z(z);
+}
+
+// The common prologue of the two tails.  What a workgroup knows about its sample b = blockIdx.y before the element loop:
+// its rows [v0, v1) of `out`, its guidance scale g (gm = 1 - g) and null row eu, its rescale and threshold lim ...
+struct TailSample {
     int v0 = 0, v1 = 0;
-    if constexpr (!EPS) {
-        v0 = off[b];
-        v1 = off[b + 1];
-    }
-    const int n4 = 3 * HW / 4;
     float g = 1.0f, gm = 0.0f;
     const float* eu = nullptr;
-    if constexpr (CFG) {
-        g = gscale[b];
-        gm = 1.0f - g;
-        eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
+    EpsBound lim;
+};
+template <bool CFG, bool EPS>
+__device__ __forceinline__ TailSample tail_sample(const float* __restrict__ out, const int* __restrict__ off,
+                                                  const float* __restrict__ gscale, const EpsBuffer& src, int Cout,
+                                                  int HW) {
+    const int b = blockIdx.y;
+    TailSample s;
+    if constexpr (!EPS) {
+        s.v0 = off[b];
+        s.v1 = off[b + 1];
     }
-    const EpsBound lim = src.bound(b);
+    if constexpr (CFG) {
+        s.g = gscale[b];
+        s.gm = 1.0f - s.g;
+        s.eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
+    }
+    s.lim = src.bound(b);
+    return s;
+}
+// ... and the eps of its float4 (c, p) at float offset o: compose -> guide, or the load from the eps buffer.
+template <bool CFG, bool EPS>
+__device__ __forceinline__ float4 tail_eps(const TailSample& s, const float* __restrict__ out, const EpsBuffer& src,
+                                           int Cout, int HW, int weighting, int c, int p, size_t o, float4* mx,
+                                           float4* inv) {
+    if constexpr (EPS) {
+        return src.load(o, s.lim);
+    } else {
+        float4 eps = compose4(out, Cout, HW, s.v0, s.v1, c, p, weighting, mx, inv);
+        if constexpr (CFG) eps = guide4(eps, s.eu + (size_t)c * HW + p, s.g, s.gm);
+        return eps;
+    }
+}
+
+// One reverse step after the UNet: compose -> y0_hat = a_t y_t - b_t eps -> clamp ->
+// mean = c1 y0_hat + c2 y_t -> y_{t-1} = mean + z * exp(0.5 logvar).
+// RNG: step = t[b], and z = 0 where t[b] == 0.  Everything from y0 on is shared by all six instantiations.
+template <bool CFG, bool EPS, bool RNG>
+__global__ __launch_bounds__(256) void p_sample_tail_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ eps_buf,
+    const float2* __restrict__ stat, const float* __restrict__ y_t, const float* __restrict__ z,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
+    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
+    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
+    float* __restrict__ mean_out, float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip,
+    const float* __restrict__ gscale, int rescale, int thr) {
+    static_assert(!(CFG && EPS), "guidance happens in the composed-eps pass");
+    const int b = blockIdx.y;
+    const EpsBuffer src{eps_buf, stat, rescale, thr};
+    const TailSample s = tail_sample<CFG, EPS>(out, off, gscale, src, Cout, HW);
+    const int n4 = 3 * HW / 4;
     const long long tb = t[b];
+    const auto noise = tail_noise<RNG, true>(z, seed, ids, tb);
     const float a_t = sqrt_recip[tb], b_t = sqrt_recipm1[tb], c1 = coef1[tb], c2 = coef2[tb];
     const float sd = expf(0.5f * logvar[tb]);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        float4 mx, inv;
-        float4 eps;
-        if constexpr (!EPS) eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
-        if constexpr (CFG) eps = guide4(eps, eu + (size_t)c * HW + p, g, gm);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
-        if constexpr (EPS) eps = src.load(o, lim);
+        float4 mx, inv;
+        const float4 eps = tail_eps<CFG, EPS>(s, out, src, Cout, HW, weighting, c, p, o, &mx, &inv);
         const float4 y = *reinterpret_cast<const float4*>(y_t + o);
         float y0[4] = {y0_hat(a_t, y.x, b_t, eps.x), y0_hat(a_t, y.y, b_t, eps.y), y0_hat(a_t, y.z, b_t, eps.z),
                        y0_hat(a_t, y.w, b_t, eps.w)};
@@ -446,142 +541,53 @@ __device__ __forceinline__ void p_sample_tail_body(
         const float zs[4] = {zz.x, zz.y, zz.z, zz.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            if constexpr (EPS) y0[k] = lim(y0[k], clip);
+            if constexpr (EPS) y0[k] = s.lim(y0[k], clip);
             else if (clip) y0[k] = fminf(fmaxf(y0[k], -1.0f), 1.0f);
             posterior_update<EPS>(c1, c2, sd, y0[k], ys[k], zs[k], m[k], r[k]);
         }
         if (y_next) *reinterpret_cast<float4*>(y_next + o) = make_float4(r[0], r[1], r[2], r[3]);
         if (mean_out) *reinterpret_cast<float4*>(mean_out + o) = make_float4(m[0], m[1], m[2], m[3]);
-        if constexpr (EPS) continue;
-        if (weights && weighting) {
-            const size_t vs = (size_t)Cout * HW;
-            for (int j = 0; j < maxV; ++j) {
-                float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (v0 + j < v1) {
-                    const float4 l = *reinterpret_cast<const float4*>(out + (size_t)(v0 + j) * vs +
-                                                                     (size_t)(3 + c) * HW + p);
-                    w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
-                                    expf(l.w - mx.w) * inv.w);
-                }
-                *reinterpret_cast<float4*>(weights + (((size_t)b * maxV + j) * 3) * HW + 4 * (size_t)i) = w;
-            }
-        }
+        if constexpr (!EPS)
+            if (weights && weighting) write_weights(out, weights, Cout, HW, maxV, s.v0, s.v1, c, p, i, mx, inv);
     }
-}
-
-__global__ __launch_bounds__(256) void p_sample_tail_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
-    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
-    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
-    p_sample_tail_body<false>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
-                       weights, Cout, HW, maxV, weighting, clip, nullptr, [z](int, size_t o) {
-                           float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-                           if (z) zz = *reinterpret_cast<const float4*>(z + o);
-                           return zz;
-                       });
-}
-
-// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
-__global__ __launch_bounds__(256) void p_sample_tail_cfg_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
-    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
-    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip,
-    const float* __restrict__ g) {
-    p_sample_tail_body<true>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
-                       weights, Cout, HW, maxV, weighting, clip, g, [z](int, size_t o) {
-                           float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-                           if (z) zz = *reinterpret_cast<const float4*>(z + o);
-                           return zz;
-                       });
-}
-
-// The same step with z drawn in the kernel: kind 3, step = t[b], block = the float4 index; z = 0 where t[b] == 0.
-// t and ids come from device memory, so a captured launch replays for every step.
-__global__ __launch_bounds__(256) void p_sample_tail_rng_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
-    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
-    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
-    float* __restrict__ mean_out, float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip) {
-    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
-    const long long tb = t[blockIdx.y];
-    p_sample_tail_body<false>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
-                       weights, Cout, HW, maxV, weighting, clip, nullptr, [seed, id, tb](int i, size_t) {
-                           float n[4] = {0.f, 0.f, 0.f, 0.f};
-                           if (tb != 0) vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
-                           return make_float4(n[0], n[1], n[2], n[3]);
-                       });
-}
-
-// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
-__global__ __launch_bounds__(256) void p_sample_tail_cfg_rng_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
-    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
-    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
-    float* __restrict__ mean_out, float* __restrict__ weights, int Cout, int HW, int maxV, int weighting, int clip,
-    const float* __restrict__ g) {
-    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
-    const long long tb = t[blockIdx.y];
-    p_sample_tail_body<true>(out, off, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next, mean_out,
-                       weights, Cout, HW, maxV, weighting, clip, g, [seed, id, tb](int i, size_t) {
-                           float n[4] = {0.f, 0.f, 0.f, 0.f};
-                           if (tb != 0) vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
-                           return make_float4(n[0], n[1], n[2], n[3]);
-                       });
 }
 
 // One linear-multistep reverse step after the UNet (strided DDIM, DPM-Solver++ 2M; schedule.sampler_tables):
 //   y0 = clamp(a[k] y - b[k] eps, -1, 1);  y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z;  y0_prev <- y0
 // with k = kidx[b] read from device memory.  sigma[k] == 0: `noise` is never called (no load, no draw);
 // c1[k] == 0 or no history buffer: y0_prev is not read (it may hold anything before the first multistep step).
-// Elementwise: y_next may be y, and y0_prev is read and written by the same thread.  CFG: as in p_sample_tail_body.
-// EPS: the source of eps, as in p_sample_tail_body.
-template <bool CFG, bool EPS = false, class Noise>
-__device__ __forceinline__ void sampler_step_body(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const long long* __restrict__ kidx, const float* __restrict__ ta, const float* __restrict__ tb,
+// Elementwise: y_next may be y, and y0_prev is read and written by the same thread.
+// RNG: step = the MODEL timestep tau[k], so a strided chain and the full chain draw the same z at the same noise level.
+template <bool CFG, bool EPS, bool RNG>
+__global__ __launch_bounds__(256) void sampler_step_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ eps_buf,
+    const float2* __restrict__ stat, const float* __restrict__ y_t, const float* __restrict__ z,
+    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
+    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
     const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
-    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
-    int Cout, int HW, int maxV, int weighting, const float* __restrict__ gscale, Noise noise,
-    EpsBuffer src = EpsBuffer{}) {
+    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights, int Cout,
+    int HW, int maxV, int weighting, const float* __restrict__ gscale, int rescale, int thr) {
+    static_assert(!(CFG && EPS), "guidance happens in the composed-eps pass");
     const int b = blockIdx.y;
-    int v0 = 0, v1 = 0;
-    if constexpr (!EPS) {
-        v0 = off[b];
-        v1 = off[b + 1];
-    }
-    const EpsBound lim = src.bound(b);
+    const EpsBuffer src{eps_buf, stat, rescale, thr};
+    const TailSample s = tail_sample<CFG, EPS>(out, off, gscale, src, Cout, HW);
     const int n4 = 3 * HW / 4;
-    float g = 1.0f, gm = 0.0f;
-    const float* eu = nullptr;
-    if constexpr (CFG) {
-        g = gscale[b];
-        gm = 1.0f - g;
-        eu = out + (size_t)(off[gridDim.y] + b) * Cout * HW;
-    }
     const long long k = kidx[b];
+    const auto noise = tail_noise<RNG, false>(z, seed, ids, RNG ? (uint32_t)tau[k] : 0u);
     const float a_k = ta[k], b_k = tb[k], cy = tcy[k], c0 = tc0[k], c1 = tc1[k], sg = tsigma[k];
     const bool hist = y0_prev != nullptr && c1 != 0.0f, noisy = sg != 0.0f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        float4 mx, inv;
-        float4 eps;
-        if constexpr (!EPS) eps = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
-        if constexpr (CFG) eps = guide4(eps, eu + (size_t)c * HW + p, g, gm);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
-        if constexpr (EPS) eps = src.load(o, lim);
+        float4 mx, inv;
+        const float4 eps = tail_eps<CFG, EPS>(s, out, src, Cout, HW, weighting, c, p, o, &mx, &inv);
         const float4 y = *reinterpret_cast<const float4*>(y_t + o);
         const float ys[4] = {y.x, y.y, y.z, y.w};
         const float es[4] = {eps.x, eps.y, eps.z, eps.w};
         float y0[4], r[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if constexpr (EPS) y0[j] = lim(y0_hat_as<false>(a_k, ys[j], b_k, es[j]), 1);
+            if constexpr (EPS) y0[j] = s.lim(y0_hat_as<false>(a_k, ys[j], b_k, es[j]), 1);
             else y0[j] = fminf(fmaxf(y0_hat(a_k, ys[j], b_k, es[j]), -1.0f), 1.0f);
             r[j] = multistep_base<EPS>(cy, ys[j], c0, y0[j], j);
         }
@@ -591,96 +597,15 @@ __device__ __forceinline__ void sampler_step_body(
             r[2] = multistep_add<EPS>(r[2], c1, h.z); r[3] = multistep_add<EPS>(r[3], c1, h.w);
         }
         if (noisy) {
-            const float4 z = noise(i, o);
-            r[0] = multistep_add<EPS>(r[0], sg, z.x); r[1] = multistep_add<EPS>(r[1], sg, z.y);
-            r[2] = multistep_add<EPS>(r[2], sg, z.z); r[3] = multistep_add<EPS>(r[3], sg, z.w);
+            const float4 zz = noise(i, o);
+            r[0] = multistep_add<EPS>(r[0], sg, zz.x); r[1] = multistep_add<EPS>(r[1], sg, zz.y);
+            r[2] = multistep_add<EPS>(r[2], sg, zz.z); r[3] = multistep_add<EPS>(r[3], sg, zz.w);
         }
         if (y0_prev) *reinterpret_cast<float4*>(y0_prev + o) = make_float4(y0[0], y0[1], y0[2], y0[3]);
         *reinterpret_cast<float4*>(y_next + o) = make_float4(r[0], r[1], r[2], r[3]);
-        if constexpr (EPS) continue;
-        if (weights && weighting) {
-            const size_t vs = (size_t)Cout * HW;
-            for (int j = 0; j < maxV; ++j) {
-                float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (v0 + j < v1) {
-                    const float4 l = *reinterpret_cast<const float4*>(out + (size_t)(v0 + j) * vs +
-                                                                     (size_t)(3 + c) * HW + p);
-                    w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
-                                    expf(l.w - mx.w) * inv.w);
-                }
-                *reinterpret_cast<float4*>(weights + (((size_t)b * maxV + j) * 3) * HW + 4 * (size_t)i) = w;
-            }
-        }
+        if constexpr (!EPS)
+            if (weights && weighting) write_weights(out, weights, Cout, HW, maxV, s.v0, s.v1, c, p, i, mx, inv);
     }
-}
-
-// z loaded from a buffer; z == null is "no noise" whatever sigma says
-__global__ __launch_bounds__(256) void sampler_step_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ kidx, const float* __restrict__ ta,
-    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
-    const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting) {
-    sampler_step_body<false>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
-                      maxV, weighting, nullptr, [z](int, size_t o) {
-                          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-                          if (z) zz = *reinterpret_cast<const float4*>(z + o);
-                          return zz;
-                      });
-}
-
-// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
-__global__ __launch_bounds__(256) void sampler_step_cfg_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ kidx, const float* __restrict__ ta,
-    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
-    const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next,
-    float* __restrict__ weights, int Cout, int HW, int maxV, int weighting,
-    const float* __restrict__ g) {
-    sampler_step_body<true>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
-                      maxV, weighting, g, [z](int, size_t o) {
-                          float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-                          if (z) zz = *reinterpret_cast<const float4*>(z + o);
-                          return zz;
-                      });
-}
-
-// z drawn in the kernel, keyed as in p_sample_tail_rng_kernel with the MODEL timestep tau[k] as the step, so a
-// strided chain and the full chain draw the same z at the same noise level.
-__global__ __launch_bounds__(256) void sampler_step_rng_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
-    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
-    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
-    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
-    int Cout, int HW, int maxV, int weighting) {
-    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
-    const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
-    sampler_step_body<false>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
-                      maxV, weighting, nullptr, [seed, id, step](int i, size_t) {
-                          float n[4];
-                          vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
-                          return make_float4(n[0], n[1], n[2], n[3]);
-                      });
-}
-
-// ... guided: `out` has off[B] + B rows, g [B] the guidance scales (the head of this file)
-__global__ __launch_bounds__(256) void sampler_step_cfg_rng_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
-    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
-    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
-    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
-    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, float* __restrict__ weights,
-    int Cout, int HW, int maxV, int weighting,
-    const float* __restrict__ g) {
-    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
-    const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
-    sampler_step_body<true>(out, off, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, weights, Cout, HW,
-                      maxV, weighting, g, [seed, id, step](int i, size_t) {
-                          float n[4];
-                          vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
-                          return make_float4(n[0], n[1], n[2], n[3]);
-                      });
 }
 
 // Training draws of sample b (kind 0): t[b] in [1, T-1] as int64, u[b] in [0, 1) (optional output) and
@@ -1082,79 +1007,59 @@ __global__ __launch_bounds__(1024) void abs_quantile_kernel(const float* __restr
     if (threadIdx.x == 0) out[blockIdx.x] = quantile_lerp(xk, xk1, frac);
 }
 
-// The four tails on the composed-eps buffer: grid (chunks, B) as their composing siblings, the same z conventions.
-__global__ __launch_bounds__(256) void p_sample_tail_eps_kernel(
-    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ t, const float* __restrict__ sqrt_recip,
-    const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar, const float* __restrict__ coef1,
-    const float* __restrict__ coef2, float* __restrict__ y_next, float* __restrict__ mean_out, int HW, int clip,
-    int rescale, int thr) {
-    p_sample_tail_body<false, true>(nullptr, nullptr, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next,
-                                    mean_out, nullptr, 0, HW, 0, 0, clip, nullptr,
-                                    [z](int, size_t o) {
-                                        float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-                                        if (z) zz = *reinterpret_cast<const float4*>(z + o);
-                                        return zz;
-                                    },
-                                    EpsBuffer{eps, stat, rescale, thr});
-}
-
-__global__ __launch_bounds__(256) void p_sample_tail_eps_rng_kernel(
-    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
-    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ t,
-    const float* __restrict__ sqrt_recip, const float* __restrict__ sqrt_recipm1, const float* __restrict__ logvar,
-    const float* __restrict__ coef1, const float* __restrict__ coef2, float* __restrict__ y_next,
-    float* __restrict__ mean_out, int HW, int clip, int rescale, int thr) {
-    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
-    const long long tb = t[blockIdx.y];
-    p_sample_tail_body<false, true>(nullptr, nullptr, y_t, t, sqrt_recip, sqrt_recipm1, logvar, coef1, coef2, y_next,
-                                    mean_out, nullptr, 0, HW, 0, 0, clip, nullptr,
-                                    [seed, id, tb](int i, size_t) {
-                                        float n[4] = {0.f, 0.f, 0.f, 0.f};
-                                        if (tb != 0)
-                                            vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, (uint32_t)tb, (uint32_t)i, n);
-                                        return make_float4(n[0], n[1], n[2], n[3]);
-                                    },
-                                    EpsBuffer{eps, stat, rescale, thr});
-}
-
-__global__ __launch_bounds__(256) void sampler_step_eps_kernel(
-    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
-    const float* __restrict__ z, const long long* __restrict__ kidx, const float* __restrict__ ta,
-    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
-    const float* __restrict__ tc1, const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, int HW,
-    int rescale, int thr) {
-    sampler_step_body<false, true>(nullptr, nullptr, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, nullptr,
-                                   0, HW, 0, 0, nullptr,
-                                   [z](int, size_t o) {
-                                       float4 zz = make_float4(0.f, 0.f, 0.f, 0.f);
-                                       if (z) zz = *reinterpret_cast<const float4*>(z + o);
-                                       return zz;
-                                   },
-                                   EpsBuffer{eps, stat, rescale, thr});
-}
-
-__global__ __launch_bounds__(256) void sampler_step_eps_rng_kernel(
-    const float* __restrict__ eps, const float2* __restrict__ stat, const float* __restrict__ y_t,
-    unsigned long long seed, const long long* __restrict__ ids, const long long* __restrict__ kidx,
-    const long long* __restrict__ tau, const float* __restrict__ ta, const float* __restrict__ tb,
-    const float* __restrict__ tcy, const float* __restrict__ tc0, const float* __restrict__ tc1,
-    const float* __restrict__ tsigma, float* y0_prev, float* __restrict__ y_next, int HW, int rescale, int thr) {
-    const unsigned long long id = (unsigned long long)ids[blockIdx.y];
-    const uint32_t step = (uint32_t)tau[kidx[blockIdx.y]];
-    sampler_step_body<false, true>(nullptr, nullptr, y_t, kidx, ta, tb, tcy, tc0, tc1, tsigma, y0_prev, y_next, nullptr,
-                                   0, HW, 0, 0, nullptr,
-                                   [seed, id, step](int i, size_t) {
-                                       float n[4];
-                                       vf_rng_normal4(seed, id, VF_RNG_STEP_NOISE, step, (uint32_t)i, n);
-                                       return make_float4(n[0], n[1], n[2], n[3]);
-                                   },
-                                   EpsBuffer{eps, stat, rescale, thr});
-}
-
 inline int chunks_for(int n4) {
     int c = (n4 + 255) / 256;
     return c < 1 ? 1 : (c > 64 ? 64 : c);
+}
+
+// ---- the reverse-step tails: one launcher per flavour behind twelve entry points ----
+// Each entry point names its instantiation and hands its own arguments on; what its variant does not have is null / 0.
+//   plain: unet_out [off[B]][Cout][HW];   _cfg: + g [B], unet_out is [off[B] + B][Cout][HW] (the null rows last);
+//   _eps:  eps [B][3][HW] and stat [B][2] from vf_compose_eps / vf_sample_stat instead of unet_out;
+//   _rng:  seed and ids [B] instead of z.
+// What an entry refuses is what it always refused, which is not the same for every variant: a missing g only where there
+// is one; HW <= 0, a missing eps and a missing stat under rescale / thr only in the _eps entries (the others launch a
+// kernel with nothing to do for HW == 0); Cout only where there is a unet_out; a missing y_next only in the few-step
+// entries (the ancestral kernel skips a null y_next); no other pointer is looked at.
+template <bool CFG, bool EPS>
+inline bool tail_args_ok(const float* eps, const float* stat, const float* g, int Cout, int HW, int weighting,
+                         int rescale, int thr) {
+    if (HW & 3) return false;
+    if (EPS) return HW > 0 && eps && (stat || !(rescale || thr));
+    return Cout >= 3 && (!weighting || Cout >= 6) && (!CFG || g);
+}
+
+template <bool CFG, bool EPS, bool RNG>
+int p_sample_tail(const float* unet_out, const int* off, const float* eps, const float* stat, const float* y_t,
+                  const float* z, unsigned long long seed, const long long* ids, const long long* t,
+                  const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                  const float* posterior_log_variance, const float* posterior_mean_coef1,
+                  const float* posterior_mean_coef2, float* y_next, float* mean_out, float* weights, int B,
+                  int Cout, int HW, int maxV, int weighting, int clip, const float* g, int rescale, int thr,
+                  void* stream) {
+    if (B <= 0) return 0;
+    if (!tail_args_ok<CFG, EPS>(eps, stat, g, Cout, HW, weighting, rescale, thr)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((p_sample_tail_kernel<CFG, EPS, RNG>), dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, eps, (const float2*)stat, y_t, z, seed, ids, t,
+                       sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance, posterior_mean_coef1,
+                       posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV, weighting, clip, g, rescale, thr);
+    VF_RETURN_LAST_ERROR();
+}
+
+// the few-step tail (tables: schedule.sampler_tables)
+template <bool CFG, bool EPS, bool RNG>
+int sampler_step(const float* unet_out, const int* off, const float* eps, const float* stat, const float* y_t,
+                 const float* z, unsigned long long seed, const long long* ids, const long long* kidx,
+                 const long long* tau, const float* a, const float* b, const float* cy, const float* c0,
+                 const float* c1, const float* sigma, float* y0_prev, float* y_next, float* weights, int B,
+                 int Cout, int HW, int maxV, int weighting, const float* g, int rescale, int thr, void* stream) {
+    if (B <= 0) return 0;
+    if (!tail_args_ok<CFG, EPS>(eps, stat, g, Cout, HW, weighting, rescale, thr) || !y_next)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((sampler_step_kernel<CFG, EPS, RNG>), dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, eps, (const float2*)stat, y_t, z, seed, ids, kidx, tau, a, b,
+                       cy, c0, c1, sigma, y0_prev, y_next, weights, Cout, HW, maxV, weighting, g, rescale, thr);
+    VF_RETURN_LAST_ERROR();
 }
 
 }  // namespace
@@ -1276,20 +1181,6 @@ int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, 
     return 0;
 }
 
-int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* t,
-                     const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
-                     const float* posterior_log_variance, const float* posterior_mean_coef1,
-                     const float* posterior_mean_coef2, float* y_next, float* mean_out, float* weights, int B,
-                     int Cout, int HW, int maxV, int weighting, int clip, void* stream) {
-    if (B <= 0) return 0;
-    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(p_sample_tail_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       unet_out, off, y_t, z, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
-                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV,
-                       weighting, clip);
-    VF_RETURN_LAST_ERROR();
-}
-
 // ---- seeded draws (rng.h) ----
 static inline bool rng_args_ok(int kind, int step) { return kind >= 0 && kind <= 3 && step >= 0 && step < (1 << 28); }
 
@@ -1320,48 +1211,7 @@ int vf_philox_ids(unsigned long long seed, const long long* ids, int kind, int s
     VF_RETURN_LAST_ERROR();
 }
 
-int vf_p_sample_tail_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
-                         const long long* ids, const long long* t, const float* sqrt_recip_gammas,
-                         const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
-                         const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
-                         float* mean_out, float* weights, int B, int Cout, int HW, int maxV, int weighting, int clip,
-                         void* stream) {
-    if (B <= 0) return 0;
-    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(p_sample_tail_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       unet_out, off, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
-                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV, weighting,
-                       clip);
-    VF_RETURN_LAST_ERROR();
-}
-
-// ---- few-step samplers: one linear-multistep tail (tables: schedule.sampler_tables) ----
-int vf_sampler_step(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* kidx,
-                    const float* a, const float* b, const float* cy, const float* c0, const float* c1,
-                    const float* sigma, float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW,
-                    int maxV, int weighting, void* stream) {
-    if (B <= 0) return 0;
-    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !y_next) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sampler_step_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       unet_out, off, y_t, z, kidx, a, b, cy, c0, c1, sigma, y0_prev, y_next, weights, Cout, HW, maxV,
-                       weighting);
-    VF_RETURN_LAST_ERROR();
-}
-
-int vf_sampler_step_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
-                        const long long* ids, const long long* kidx, const long long* tau, const float* a,
-                        const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
-                        float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW, int maxV,
-                        int weighting, void* stream) {
-    if (B <= 0) return 0;
-    if ((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !y_next) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sampler_step_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       unet_out, off, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev, y_next, weights,
-                       Cout, HW, maxV, weighting);
-    VF_RETURN_LAST_ERROR();
-}
-
-// ---- classifier-free guidance (the head of this file): conditioning dropout, null rows, guided tails ----
+// ---- classifier-free guidance (the head of this file): conditioning dropout, null rows ----
 // vf_stack_views with drop (DEVICE uint8 [B] | NULL) and null_rows: x [S (+ B)][Cc+3][HW], level_s / angle_s [S (+ B)].
 int vf_stack_views_cfg(const float* y_cond, const float* y_t, const float* noise, const float* level,
                        const float* angle, const int* off, const unsigned char* drop, float* x, float* level_s,
@@ -1386,65 +1236,6 @@ int vf_draw_cond_drop(unsigned long long seed, const long long* ids, unsigned th
     if (thr > (1u << 24)) return (int)hipErrorInvalidValue;
     hipLaunchKernelGGL(draw_cond_drop_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, seed, ids, thr,
                        drop, B);
-    VF_RETURN_LAST_ERROR();
-}
-
-static inline bool tail_args_ok(int Cout, int HW, int weighting, const float* g) {
-    return !((HW & 3) || Cout < 3 || (weighting && Cout < 6) || !g);
-}
-
-// The four guided tails: the sibling's arguments + g [B]; unet_out is [off[B] + B][Cout][HW].
-int vf_p_sample_tail_cfg(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* t,
-                         const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
-                         const float* posterior_log_variance, const float* posterior_mean_coef1,
-                         const float* posterior_mean_coef2, float* y_next, float* mean_out, float* weights, int B,
-                         int Cout, int HW, int maxV, int weighting, int clip, const float* g, void* stream) {
-    if (B <= 0) return 0;
-    if (!tail_args_ok(Cout, HW, weighting, g)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(p_sample_tail_cfg_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       unet_out, off, y_t, z, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
-                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, Cout, HW, maxV,
-                       weighting, clip, g);
-    VF_RETURN_LAST_ERROR();
-}
-
-int vf_p_sample_tail_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
-                             const long long* ids, const long long* t, const float* sqrt_recip_gammas,
-                             const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
-                             const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
-                             float* mean_out, float* weights, int B, int Cout, int HW, int maxV, int weighting,
-                             int clip, const float* g, void* stream) {
-    if (B <= 0) return 0;
-    if (!tail_args_ok(Cout, HW, weighting, g)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(p_sample_tail_cfg_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
-                       (hipStream_t)stream, unet_out, off, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas,
-                       posterior_log_variance, posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights,
-                       Cout, HW, maxV, weighting, clip, g);
-    VF_RETURN_LAST_ERROR();
-}
-
-int vf_sampler_step_cfg(const float* unet_out, const int* off, const float* y_t, const float* z,
-                        const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
-                        const float* c1, const float* sigma, float* y0_prev, float* y_next, float* weights, int B,
-                        int Cout, int HW, int maxV, int weighting, const float* g, void* stream) {
-    if (B <= 0) return 0;
-    if (!tail_args_ok(Cout, HW, weighting, g) || !y_next) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sampler_step_cfg_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       unet_out, off, y_t, z, kidx, a, b, cy, c0, c1, sigma, y0_prev, y_next, weights, Cout, HW, maxV,
-                       weighting, g);
-    VF_RETURN_LAST_ERROR();
-}
-
-int vf_sampler_step_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
-                            const long long* ids, const long long* kidx, const long long* tau, const float* a,
-                            const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
-                            float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW, int maxV,
-                            int weighting, const float* g, void* stream) {
-    if (B <= 0) return 0;
-    if (!tail_args_ok(Cout, HW, weighting, g) || !y_next) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sampler_step_cfg_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
-                       (hipStream_t)stream, unet_out, off, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev,
-                       y_next, weights, Cout, HW, maxV, weighting, g);
     VF_RETURN_LAST_ERROR();
 }
 
@@ -1495,8 +1286,50 @@ int vf_abs_quantile(const float* x, int B, int n, int k, float frac, float* out,
     VF_RETURN_LAST_ERROR();
 }
 
-static inline bool eps_tail_args_ok(const float* eps, const float* stat, int HW, int rescale, int thr) {
-    return HW > 0 && !(HW & 3) && eps && (stat || !(rescale || thr));
+int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* t,
+                     const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                     const float* posterior_log_variance, const float* posterior_mean_coef1,
+                     const float* posterior_mean_coef2, float* y_next, float* mean_out, float* weights, int B,
+                     int Cout, int HW, int maxV, int weighting, int clip, void* stream) {
+    return p_sample_tail<false, false, false>(unet_out, off, nullptr, nullptr, y_t, z, 0, nullptr, t, sqrt_recip_gammas,
+                                              sqrt_recipm1_gammas, posterior_log_variance, posterior_mean_coef1,
+                                              posterior_mean_coef2, y_next, mean_out, weights, B, Cout, HW, maxV,
+                                              weighting, clip, nullptr, 0, 0, stream);
+}
+
+int vf_p_sample_tail_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                         const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                         const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                         const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
+                         float* mean_out, float* weights, int B, int Cout, int HW, int maxV, int weighting, int clip,
+                         void* stream) {
+    return p_sample_tail<false, false, true>(unet_out, off, nullptr, nullptr, y_t, nullptr, seed, ids, t,
+                                             sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
+                                             posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, B,
+                                             Cout, HW, maxV, weighting, clip, nullptr, 0, 0, stream);
+}
+
+int vf_p_sample_tail_cfg(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* t,
+                         const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
+                         const float* posterior_log_variance, const float* posterior_mean_coef1,
+                         const float* posterior_mean_coef2, float* y_next, float* mean_out, float* weights, int B,
+                         int Cout, int HW, int maxV, int weighting, int clip, const float* g, void* stream) {
+    return p_sample_tail<true, false, false>(unet_out, off, nullptr, nullptr, y_t, z, 0, nullptr, t, sqrt_recip_gammas,
+                                             sqrt_recipm1_gammas, posterior_log_variance, posterior_mean_coef1,
+                                             posterior_mean_coef2, y_next, mean_out, weights, B, Cout, HW, maxV,
+                                             weighting, clip, g, 0, 0, stream);
+}
+
+int vf_p_sample_tail_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                             const long long* ids, const long long* t, const float* sqrt_recip_gammas,
+                             const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
+                             const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
+                             float* mean_out, float* weights, int B, int Cout, int HW, int maxV, int weighting,
+                             int clip, const float* g, void* stream) {
+    return p_sample_tail<true, false, true>(unet_out, off, nullptr, nullptr, y_t, nullptr, seed, ids, t,
+                                            sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
+                                            posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, weights, B,
+                                            Cout, HW, maxV, weighting, clip, g, 0, 0, stream);
 }
 
 int vf_p_sample_tail_eps(const float* eps, const float* stat, const float* y_t, const float* z, const long long* t,
@@ -1504,12 +1337,10 @@ int vf_p_sample_tail_eps(const float* eps, const float* stat, const float* y_t, 
                          const float* posterior_log_variance, const float* posterior_mean_coef1,
                          const float* posterior_mean_coef2, float* y_next, float* mean_out, int B, int HW, int clip,
                          int rescale, int thr, void* stream) {
-    if (B <= 0) return 0;
-    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(p_sample_tail_eps_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream, eps,
-                       (const float2*)stat, y_t, z, t, sqrt_recip_gammas, sqrt_recipm1_gammas, posterior_log_variance,
-                       posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, HW, clip, rescale, thr);
-    VF_RETURN_LAST_ERROR();
+    return p_sample_tail<false, true, false>(nullptr, nullptr, eps, stat, y_t, z, 0, nullptr, t, sqrt_recip_gammas,
+                                             sqrt_recipm1_gammas, posterior_log_variance, posterior_mean_coef1,
+                                             posterior_mean_coef2, y_next, mean_out, nullptr, B, 0, HW, 0, 0, clip,
+                                             nullptr, rescale, thr, stream);
 }
 
 int vf_p_sample_tail_eps_rng(const float* eps, const float* stat, const float* y_t, unsigned long long seed,
@@ -1517,36 +1348,66 @@ int vf_p_sample_tail_eps_rng(const float* eps, const float* stat, const float* y
                              const float* sqrt_recipm1_gammas, const float* posterior_log_variance,
                              const float* posterior_mean_coef1, const float* posterior_mean_coef2, float* y_next,
                              float* mean_out, int B, int HW, int clip, int rescale, int thr, void* stream) {
-    if (B <= 0) return 0;
-    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr)) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(p_sample_tail_eps_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       eps, (const float2*)stat, y_t, seed, ids, t, sqrt_recip_gammas, sqrt_recipm1_gammas,
-                       posterior_log_variance, posterior_mean_coef1, posterior_mean_coef2, y_next, mean_out, HW, clip,
-                       rescale, thr);
-    VF_RETURN_LAST_ERROR();
+    return p_sample_tail<false, true, true>(nullptr, nullptr, eps, stat, y_t, nullptr, seed, ids, t, sqrt_recip_gammas,
+                                            sqrt_recipm1_gammas, posterior_log_variance, posterior_mean_coef1,
+                                            posterior_mean_coef2, y_next, mean_out, nullptr, B, 0, HW, 0, 0, clip,
+                                            nullptr, rescale, thr, stream);
+}
+
+int vf_sampler_step(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* kidx,
+                    const float* a, const float* b, const float* cy, const float* c0, const float* c1,
+                    const float* sigma, float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW,
+                    int maxV, int weighting, void* stream) {
+    return sampler_step<false, false, false>(unet_out, off, nullptr, nullptr, y_t, z, 0, nullptr, kidx, nullptr, a, b,
+                                             cy, c0, c1, sigma, y0_prev, y_next, weights, B, Cout, HW, maxV, weighting,
+                                             nullptr, 0, 0, stream);
+}
+
+int vf_sampler_step_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                        const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                        const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                        float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW, int maxV,
+                        int weighting, void* stream) {
+    return sampler_step<false, false, true>(unet_out, off, nullptr, nullptr, y_t, nullptr, seed, ids, kidx, tau, a, b,
+                                            cy, c0, c1, sigma, y0_prev, y_next, weights, B, Cout, HW, maxV, weighting,
+                                            nullptr, 0, 0, stream);
+}
+
+int vf_sampler_step_cfg(const float* unet_out, const int* off, const float* y_t, const float* z,
+                        const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                        const float* c1, const float* sigma, float* y0_prev, float* y_next, float* weights, int B,
+                        int Cout, int HW, int maxV, int weighting, const float* g, void* stream) {
+    return sampler_step<true, false, false>(unet_out, off, nullptr, nullptr, y_t, z, 0, nullptr, kidx, nullptr, a, b, cy,
+                                            c0, c1, sigma, y0_prev, y_next, weights, B, Cout, HW, maxV, weighting, g, 0,
+                                            0, stream);
+}
+
+int vf_sampler_step_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                            const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                            const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
+                            float* y0_prev, float* y_next, float* weights, int B, int Cout, int HW, int maxV,
+                            int weighting, const float* g, void* stream) {
+    return sampler_step<true, false, true>(unet_out, off, nullptr, nullptr, y_t, nullptr, seed, ids, kidx, tau, a, b, cy,
+                                           c0, c1, sigma, y0_prev, y_next, weights, B, Cout, HW, maxV, weighting, g, 0,
+                                           0, stream);
 }
 
 int vf_sampler_step_eps(const float* eps, const float* stat, const float* y_t, const float* z, const long long* kidx,
                         const float* a, const float* b, const float* cy, const float* c0, const float* c1,
                         const float* sigma, float* y0_prev, float* y_next, int B, int HW, int rescale, int thr,
                         void* stream) {
-    if (B <= 0) return 0;
-    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr) || !y_next) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sampler_step_eps_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream, eps,
-                       (const float2*)stat, y_t, z, kidx, a, b, cy, c0, c1, sigma, y0_prev, y_next, HW, rescale, thr);
-    VF_RETURN_LAST_ERROR();
+    return sampler_step<false, true, false>(nullptr, nullptr, eps, stat, y_t, z, 0, nullptr, kidx, nullptr, a, b, cy, c0,
+                                            c1, sigma, y0_prev, y_next, nullptr, B, 0, HW, 0, 0, nullptr, rescale, thr,
+                                            stream);
 }
 
 int vf_sampler_step_eps_rng(const float* eps, const float* stat, const float* y_t, unsigned long long seed,
                             const long long* ids, const long long* kidx, const long long* tau, const float* a,
                             const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
                             float* y0_prev, float* y_next, int B, int HW, int rescale, int thr, void* stream) {
-    if (B <= 0) return 0;
-    if (!eps_tail_args_ok(eps, stat, HW, rescale, thr) || !y_next) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(sampler_step_eps_rng_kernel, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0, (hipStream_t)stream,
-                       eps, (const float2*)stat, y_t, seed, ids, kidx, tau, a, b, cy, c0, c1, sigma, y0_prev, y_next, HW,
-                       rescale, thr);
-    VF_RETURN_LAST_ERROR();
+    return sampler_step<false, true, true>(nullptr, nullptr, eps, stat, y_t, nullptr, seed, ids, kidx, tau, a, b, cy, c0,
+                                           c1, sigma, y0_prev, y_next, nullptr, B, 0, HW, 0, 0, nullptr, rescale, thr,
+                                           stream);
 }
 
 // Host mirrors: the same inline functions on the CPU, HOST pointers, no stream (the CPU suite's side of the parity).

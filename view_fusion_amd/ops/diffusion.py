@@ -292,10 +292,9 @@ def threshold_scratch(y):
                 stat=torch.empty(B, 2, device=y.device, dtype=torch.float32))
 
 
-def _eps_front(unet_out, off, y, idx, ta, tb, B, max_views, weighting, want_weights, guidance, q, cmax, phi, scratch,
-               fused):
-    """The two launches in front of an *_eps tail: the composed (+ guided) eps with the weights and the partial sums,
-    then the per-sample statistics -> (scratch, weights | None).  fused: how that tail rounds y0_hat (the ancestral
+def _eps_front(unet_out, off, y, idx, ta, tb, B, max_views, weighting, wts, guidance, q, cmax, phi, scratch, fused):
+    """The two launches in front of an *_eps tail: the composed (+ guided) eps with the weights (into wts | None) and
+    the partial sums, then the per-sample statistics -> scratch.  fused: how that tail rounds y0_hat (the ancestral
     one fuses, the few-step one does not; csrc/diffusion.hip, y0_hat_as)."""
     _, Cout, H, W = unet_out.shape
     if scratch is None:
@@ -305,15 +304,22 @@ def _eps_front(unet_out, off, y, idx, ta, tb, B, max_views, weighting, want_weig
     if eps.shape != y.shape or stat.numel() != 2 * B or part.dtype != torch.float64 or part.numel() < B * 64 * 4 \
             or not part.is_cuda or not part.is_contiguous():
         raise ValueError("scratch= does not fit this batch (ops.threshold_scratch(y))")
-    wts = None
-    if weighting and want_weights:
-        wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)
     _call("vf_compose_eps", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(guidance), _ptr(eps), _ptr(wts),
           ctypes.c_void_p(part.data_ptr()), B, Cout, H * W, max_views, int(weighting), int(fused), _stream())
     k, frac = (-1, 0.0) if q is None else quantile_position(3 * H * W, q)
     _call("vf_sample_stat", _ptr(eps), ctypes.c_void_p(part.data_ptr()), _ptr(y), ctypes.c_void_p(idx.data_ptr()),
           _ptr(ta), _ptr(tb), _ptr(stat), B, H * W, phi, k, frac, cmax, int(fused), _stream())
-    return scratch, wts
+    return scratch
+
+
+def _tail_noise(z, seed, ids, device, B):
+    """The noise source of a tail -> (entry-point suffix, arguments): "" and z (None: no noise), or "_rng" and
+    seed + ids for a draw inside the kernel."""
+    if seed is None:
+        return "", (_ptr(z),)
+    ids = sample_ids(device, B, ids)
+    _check_ids(ids, B)
+    return "_rng", (_seed(seed), ctypes.c_void_p(ids.data_ptr()))
 
 
 class _ComposeLossFn(torch.autograd.Function):
@@ -438,46 +444,30 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
     _check(unet_out, y_t, z)
     if guidance is not None:
         _check_guidance(guidance, unet_out, B, S)
-    cfg = "" if guidance is None else "_cfg"
-    gargs = () if guidance is None else (_ptr(guidance),)
     if seed is not None and z is not None:
         raise ValueError("p_sample_tail takes either z or seed=, not both")
-    _, Cout, H, W = unet_out.shape
     t = _c(t.to(torch.int64))
     y_next = y_t if inplace else torch.empty_like(y_t)     # elementwise: safe to overwrite y_t
     mean = torch.empty_like(y_t) if want_mean else None
-    if q is not None or phi > 0.0:
-        scratch, wts = _eps_front(unet_out, off, y_t, t, sched["sqrt_recip_gammas"], sched["sqrt_recipm1_gammas"], B,
-                                  max_views, weighting, want_weights, guidance, q, cmax, phi, scratch, True)
-        tabs = [_ptr(sched[n]) for n in ("sqrt_recip_gammas", "sqrt_recipm1_gammas", "posterior_log_variance_clipped",
-                                         "posterior_mean_coef1", "posterior_mean_coef2")]
-        tail = (_ptr(y_next), _ptr(mean), B, H * W, int(clip), int(phi > 0.0), int(q is not None), _stream())
-        if seed is not None:
-            ids = sample_ids(y_t.device, B, ids)
-            _check_ids(ids, B)
-            _call("vf_p_sample_tail_eps_rng", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y_t), _seed(seed),
-                  ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(t.data_ptr()), *tabs, *tail)
-        else:
-            _call("vf_p_sample_tail_eps", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y_t), _ptr(z),
-                  ctypes.c_void_p(t.data_ptr()), *tabs, *tail)
-        return y_next, mean, wts
+    _, Cout, H, W = unet_out.shape
+    tabs = [sched[n] for n in ("sqrt_recip_gammas", "sqrt_recipm1_gammas", "posterior_log_variance_clipped",
+                               "posterior_mean_coef1", "posterior_mean_coef2")]
     wts = None
     if weighting and want_weights:
         wts = torch.empty(B, max_views, 3, H, W, device=y_t.device, dtype=torch.float32)
-    if seed is not None:
-        ids = sample_ids(y_t.device, B, ids)
-        _check_ids(ids, B)
-        _call(f"vf_p_sample_tail{cfg}_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _seed(seed),
-              ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(t.data_ptr()), _ptr(sched["sqrt_recip_gammas"]),
-              _ptr(sched["sqrt_recipm1_gammas"]), _ptr(sched["posterior_log_variance_clipped"]),
-              _ptr(sched["posterior_mean_coef1"]), _ptr(sched["posterior_mean_coef2"]), _ptr(y_next), _ptr(mean),
-              _ptr(wts), B, Cout, H * W, max_views, int(weighting), int(clip), *gargs, _stream())
-        return y_next, mean, wts
-    _call(f"vf_p_sample_tail{cfg}", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_t), _ptr(z),
-              ctypes.c_void_p(t.data_ptr()), _ptr(sched["sqrt_recip_gammas"]), _ptr(sched["sqrt_recipm1_gammas"]),
-              _ptr(sched["posterior_log_variance_clipped"]), _ptr(sched["posterior_mean_coef1"]),
-              _ptr(sched["posterior_mean_coef2"]), _ptr(y_next), _ptr(mean), _ptr(wts), B, Cout, H * W, max_views,
-              int(weighting), int(clip), *gargs, _stream())
+    # the entry point: vf_p_sample_tail + the source of eps ("" | "_cfg" | "_eps") + the source of z ("" | "_rng")
+    if q is not None or phi > 0.0:
+        scratch = _eps_front(unet_out, off, y_t, t, tabs[0], tabs[1], B, max_views, weighting, wts, guidance, q, cmax,
+                             phi, scratch, True)
+        eps, src = "_eps", (_ptr(scratch["eps"]), _ptr(scratch["stat"]))
+        sizes = (B, H * W, int(clip), int(phi > 0.0), int(q is not None))
+    else:
+        eps, src = "" if guidance is None else "_cfg", (_ptr(unet_out), ctypes.c_void_p(off.data_ptr()))
+        sizes = (_ptr(wts), B, Cout, H * W, max_views, int(weighting), int(clip),
+                 *(() if guidance is None else (_ptr(guidance),)))
+    rng, noise = _tail_noise(z, seed, ids, y_t.device, B)
+    _call(f"vf_p_sample_tail{eps}{rng}", *src, _ptr(y_t), *noise, ctypes.c_void_p(t.data_ptr()),
+          *(_ptr(tab) for tab in tabs), _ptr(y_next), _ptr(mean), *sizes, _stream())
     return y_next, mean, wts
 
 
@@ -496,48 +486,33 @@ def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_
     _check(unet_out, y, z, y0_prev, *(tables[n] for n in ("a", "b", "cy", "c0", "c1", "sigma")))
     if guidance is not None:
         _check_guidance(guidance, unet_out, B, S)
-    cfg = "" if guidance is None else "_cfg"
     if seed is not None and z is not None:
         raise ValueError("sampler_step takes either z or seed=, not both")
-    _, Cout, H, W = unet_out.shape
     kidx = _c(kidx.to(torch.int64))
     y_next = y if inplace else torch.empty_like(y)         # elementwise: safe to overwrite y
-    if q is not None or phi > 0.0:
-        scratch, wts = _eps_front(unet_out, off, y, kidx, tables["a"], tables["b"], B, max_views, weighting,
-                                  want_weights, guidance, q, cmax, phi, scratch, False)
-        tabs = [_ptr(tables[n]) for n in ("a", "b", "cy", "c0", "c1", "sigma")]
-        tail = (_ptr(y0_prev), _ptr(y_next), B, H * W, int(phi > 0.0), int(q is not None), _stream())
-        if seed is not None:
-            ids = sample_ids(y.device, B, ids)
-            _check_ids(ids, B)
-            tau = tables["tau"]
-            if not tau.is_cuda or tau.dtype != torch.int64 or not tau.is_contiguous():
-                raise _lib.VFHipError("tables['tau'] must be a contiguous device int64 tensor")
-            _call("vf_sampler_step_eps_rng", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y), _seed(seed),
-                  ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(kidx.data_ptr()), ctypes.c_void_p(tau.data_ptr()),
-                  *tabs, *tail)
-        else:
-            _call("vf_sampler_step_eps", _ptr(scratch["eps"]), _ptr(scratch["stat"]), _ptr(y), _ptr(z),
-                  ctypes.c_void_p(kidx.data_ptr()), *tabs, *tail)
-        return y_next, wts
+    _, Cout, H, W = unet_out.shape
+    tabs = [tables[n] for n in ("a", "b", "cy", "c0", "c1", "sigma")]
     wts = None
     if weighting and want_weights:
         wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)
-    tabs = [_ptr(tables[n]) for n in ("a", "b", "cy", "c0", "c1", "sigma")]
-    tail = (_ptr(y0_prev), _ptr(y_next), _ptr(wts), B, Cout, H * W, max_views, int(weighting),
-            *(() if guidance is None else (_ptr(guidance),)), _stream())
-    if seed is not None:
-        ids = sample_ids(y.device, B, ids)
-        _check_ids(ids, B)
+    # the entry point: vf_sampler_step + the source of eps ("" | "_cfg" | "_eps") + the source of z ("" | "_rng")
+    if q is not None or phi > 0.0:
+        scratch = _eps_front(unet_out, off, y, kidx, tabs[0], tabs[1], B, max_views, weighting, wts, guidance, q, cmax,
+                             phi, scratch, False)
+        eps, src = "_eps", (_ptr(scratch["eps"]), _ptr(scratch["stat"]))
+        sizes = (B, H * W, int(phi > 0.0), int(q is not None))
+    else:
+        eps, src = "" if guidance is None else "_cfg", (_ptr(unet_out), ctypes.c_void_p(off.data_ptr()))
+        sizes = (_ptr(wts), B, Cout, H * W, max_views, int(weighting), *(() if guidance is None else (_ptr(guidance),)))
+    rng, noise = _tail_noise(z, seed, ids, y.device, B)
+    idx = (ctypes.c_void_p(kidx.data_ptr()),)
+    if rng:                                                # the drawn z is keyed by the model timestep tau[k]
         tau = tables["tau"]
         if not tau.is_cuda or tau.dtype != torch.int64 or not tau.is_contiguous():
             raise _lib.VFHipError("tables['tau'] must be a contiguous device int64 tensor")
-        _call(f"vf_sampler_step{cfg}_rng", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _seed(seed),
-              ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(kidx.data_ptr()), ctypes.c_void_p(tau.data_ptr()),
-              *tabs, *tail)
-        return y_next, wts
-    _call(f"vf_sampler_step{cfg}", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _ptr(z),
-          ctypes.c_void_p(kidx.data_ptr()), *tabs, *tail)
+        idx += (ctypes.c_void_p(tau.data_ptr()),)
+    _call(f"vf_sampler_step{eps}{rng}", *src, _ptr(y), *noise, *idx, *(_ptr(tab) for tab in tabs), _ptr(y0_prev),
+          _ptr(y_next), *sizes, _stream())
     return y_next, wts
 
 
