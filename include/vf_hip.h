@@ -284,6 +284,34 @@ int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* targ
 int vf_compose_loss_bwd(const float* unet_out, const int* off, const float* target, const float* noise_hat,
                         const float* gloss, const float* sample_w, float* dout, int B, int Cout, int HW, int weighting,
                         int penalty, float delta, void* stream);
+/* vf_compose_loss_fwd with a per-sample scale (DEVICE float [B]; csrc/level_sampler.h's importance weight).  With a
+ * scale, sample_w holds 2 B floats: w_b scale_b (what loss and vf_compose_loss_bwd use), then w_b alone; sample_loss and
+ * the histogram stay unweighted.  scale == NULL: vf_compose_loss_fwd itself. */
+int vf_compose_loss_fwd_scaled(const float* unet_out, const int* off, const float* target, const float* level,
+                               const float* scale /*[B]|NULL*/, float* noise_hat, float* loss_part /*[B*64]*/,
+                               float* sample_loss /*[B]*/, float* sample_w /*[2B] ([B] without scale)*/, float* loss,
+                               float* bin_sum /*[K]|NULL*/, int* bin_cnt /*[K]|NULL*/, int B, int Cout, int HW,
+                               int weighting, int penalty, float delta, int weight_kind, float a, float b, int K,
+                               void* stream);
+/* ---- loss-aware noise-level sampling (csrc/level_sampler.h holds the specification): K bins over the timesteps
+ *      1..T-1, a fixed-point proposal table c [K+1] (64-bit cut points, c[0] = 0, c[K] = 2^32), iw [K] and ready [1],
+ *      all in DEVICE memory; 1 <= K <= min(T-1, 1024). ---- */
+/* vf_draw_train's sibling.  Exactly one of ids (with seed: word 0 of the training-scalars call) and words (int64 [B],
+ * values in [0, 2^32)).  *ready == 0: the uniform draw and iw_out = 1.  u / level: seeded path only, each |NULL. */
+int vf_draw_level(unsigned long long seed, const long long* ids /*|NULL*/, const long long* words /*|NULL*/,
+                  const float* gammas, int T, int K, const unsigned long long* c, const float* iw, const int* ready,
+                  long long* t, float* u /*|NULL*/, float* level /*|NULL*/, float* iw_out /*[B]*/, int B, void* stream);
+/* r_b = (sample_w[b] sample_loss[b])^2 (sample_w NULL: 1; non-finite r_b skipped) into bin(t[b]): m / seen [K] updated
+ * with the EMA factor beta in [0, 1); then ready = min seen >= warmup && sum n_k sqrt(m_k) finite and positive, and,
+ * when ready, c / iw rebuilt with the uniform share eps (eps 2^32 >= 2 (T-1)).  One workgroup, no atomics. */
+int vf_level_stats(const float* sample_loss, const float* sample_w /*|NULL*/, const long long* t, int B, int T, int K,
+                   float beta, int warmup, double eps, float* m, int* seen, unsigned long long* c, float* iw,
+                   int* ready, void* stream);
+/* Host mirrors: HOST pointers, no stream, no GPU needed.  masses q [K] -> c [K+1], lo [K+1], iw [K];
+ * words x [n] + table -> t [n], iw_out [n]. */
+int vf_level_table_host(const double* q, int T, int K, double eps, unsigned long long* c, int* lo, float* iw);
+int vf_level_draw_host(const unsigned* x, int n, int T, int K, const unsigned long long* c, const float* iw,
+                       long long* t, float* iw_out);
 /* Host mirror of the weight function: HOST pointers, no stream, no GPU needed. */
 int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, float* out /*[B]*/);
 int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,

@@ -28,6 +28,8 @@
 //                   per-sample id) instead of loaded.  Six instantiations of each.  In front of them the two noise sources
 //                   (load_z, draw_z) and the common prologue (tail_sample, tail_eps).
 //   draws, metrics  draw_train, randn_ids, philox_ids (rng.h), gather_level, psnr.
+//   level sampling  compose_loss_finish_scaled_kernel, draw_level_kernel, level_stats_kernel: importance-sampled timesteps
+//                   from a proposal table the loss statistics rebuild on the device (level_sampler.h).
 //   three launches  compose_eps_kernel<CFG, FUSED_TAIL> -> sample_stat_kernel (abs_select, quantile_lerp; the same
 //                   selection on a plain buffer: abs_quantile_kernel) -> an EPS tail: the thresholded / rescaled step.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
@@ -78,6 +80,7 @@
 //   atomics do not make the result depend on their order), and writes stat[b] = {r_b, s_b}; the *_eps tails read eps_g and
 //   stat.  t / kidx / stat all live in device memory: a captured step replays for every step.
 #include "common.h"
+#include "level_sampler.h"
 #include "loss_weight.h"
 #include "rng.h"
 
@@ -799,6 +802,138 @@ __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __re
     }
 }
 
+// ---- loss-aware noise-level sampling (level_sampler.h holds the specification) ----
+// compose_loss_finish_kernel with a per-sample scale (the importance weight of the draw): sample_w[s] = w_s scale[s] is
+// what the loss and the backward kernel use, sample_w[B + s] = w_s alone is what level_stats_kernel reads; sample_loss
+// and the histogram stay unweighted.  A sibling written out, not a shared body: the kernel above keeps its code.
+__global__ __launch_bounds__(64) void compose_loss_finish_scaled_kernel(const float* __restrict__ part,
+                                                                        const float* __restrict__ level,
+                                                                        const float* __restrict__ scale,
+                                                                        float* __restrict__ sample_loss,
+                                                                        float* __restrict__ sample_w,
+                                                                        float* __restrict__ loss,
+                                                                        float* __restrict__ bin_sum,
+                                                                        int* __restrict__ bin_cnt, int B, int ch, int K,
+                                                                        float inv_n, int kind, float a, float b) {
+    for (int s = threadIdx.x; s < B; s += 64) {
+        float acc = 0.f;
+        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
+        sample_loss[s] = acc * inv_n;
+        const float w = vf_loss_weight(kind, a, b, level[s]);
+        sample_w[s] = w * scale[s];
+        sample_w[B + s] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
+        *loss = acc / (float)B;
+    }
+    if (bin_sum == nullptr) return;
+    for (int k = threadIdx.x; k < K; k += 64) {
+        float sum = 0.f;
+        int cnt = 0;
+        for (int s = 0; s < B; ++s) {
+            int bin = (int)(level[s] * (float)K);
+            bin = bin > K - 1 ? K - 1 : bin;
+            if (bin == k) {
+                sum += sample_loss[s];
+                ++cnt;
+            }
+        }
+        bin_sum[k] += sum;
+        bin_cnt[k] += cnt;
+    }
+}
+
+// draw_train_kernel's sibling: t from the proposal table (c [K + 1], iw [K], *ready in device memory) instead of the
+// uniform map, and the draw's importance weight.  The word is word 0 of the sample's training-scalars call (ids != null)
+// or words[b] (the unseeded path: int64 values in [0, 2^32)); u / level (seeded only, both optional) as draw_train_kernel.
+__global__ void draw_level_kernel(unsigned long long seed, const long long* __restrict__ ids,
+                                  const long long* __restrict__ words, const float* __restrict__ gammas, int T, int K,
+                                  const unsigned long long* __restrict__ c, const float* __restrict__ iw,
+                                  const int* __restrict__ ready, long long* __restrict__ t, float* __restrict__ u,
+                                  float* __restrict__ level, float* __restrict__ iw_out, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (ids) vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+    else w[0] = (uint32_t)words[b];
+    long long tb;
+    float wb = 1.0f;
+    if (*ready) {
+        int k;
+        tb = vf_level_draw(w[0], c, T, K, &k);
+        tb = tb < 1 ? 1 : (tb > T - 1 ? T - 1 : tb);     // (a table that breaks its invariants must not index past gammas)
+        wb = iw[k];
+    } else {
+        tb = vf_rng_timestep(w[0], T);
+    }
+    t[b] = tb;
+    iw_out[b] = wb;
+    if (ids == nullptr) return;
+    const float ub = vf_rng_uniform24(w[1]);
+    if (u) u[b] = ub;
+    if (level) {
+        const float hi = gammas[tb], lo = gammas[tb - 1];
+        level[b] = (hi - lo) * ub + lo;
+    }
+}
+
+// One workgroup of 256 threads.  One thread per bin (strided): walks the samples in index order, updates m / seen of its
+// own bin and leaves the bin's mass in LDS; one thread then decides `ready` and, when ready, scans the masses into the cut
+// points (float64, index order); one thread per bin then takes iw from the cut points.  Every address is written by
+// exactly one thread: no atomics, the same bits on every run.
+__global__ __launch_bounds__(256) void level_stats_kernel(const float* __restrict__ sample_loss,
+                                                          const float* __restrict__ sample_w,
+                                                          const long long* __restrict__ t, int B, int T, int K,
+                                                          float beta, int warmup, double eps, float* __restrict__ m,
+                                                          int* __restrict__ seen, unsigned long long* __restrict__ c,
+                                                          float* __restrict__ iw, int* __restrict__ ready) {
+    __shared__ double q[VF_LEVEL_MAX_BINS];
+    __shared__ unsigned long long cut[VF_LEVEL_MAX_BINS + 1];
+    __shared__ int min_seen[256];
+    __shared__ int is_ready;
+    int least = 0x7fffffff;
+    for (int k = threadIdx.x; k < K; k += 256) {
+        float sum = 0.f;
+        int cnt = 0;
+        for (int s = 0; s < B; ++s) {
+            if (vf_level_bin(t[s], T, K) != k) continue;
+            const float ws = (sample_w ? sample_w[s] : 1.0f) * sample_loss[s];
+            const float r = ws * ws;
+            if (!(fabsf(r) < INFINITY)) continue;        // NaN or Inf: skipped
+            sum += r;
+            ++cnt;
+        }
+        float mk = m[k];
+        int sk = seen[k];
+        if (cnt > 0) {
+            const float mean = sum / (float)cnt;
+            mk = sk == 0 ? mean : mk + (1.0f - beta) * (mean - mk);
+            sk += cnt;
+            m[k] = mk;
+            seen[k] = sk;
+        }
+        q[k] = vf_level_mass(mk, vf_level_lo(k + 1, T, K) - vf_level_lo(k, T, K));
+        least = sk < least ? sk : least;
+    }
+    min_seen[threadIdx.x] = least;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = 1; i < 256; ++i) least = min_seen[i] < least ? min_seen[i] : least;
+        const int ok = least >= warmup && vf_level_cuts(q, T, K, eps, cut);
+        is_ready = ok;
+        *ready = ok;
+    }
+    __syncthreads();
+    if (!is_ready) return;
+    for (int k = threadIdx.x; k <= K; k += 256) {
+        c[k] = cut[k];
+        if (k < K) iw[k] = vf_level_iw(vf_level_lo(k + 1, T, K) - vf_level_lo(k, T, K), T, cut[k + 1] - cut[k]);
+    }
+}
+
 // ---- dynamic thresholding / guidance rescaling (the head of this file) ----
 // grid (chunks, B).  eps_g [B][3][HW] (= eps_c when !CFG); the conditional weights as compose_fwd_kernel writes them;
 // part[(b * chunks + chunk) * 4 + {0..3}] = this workgroup's sums of eps_c, eps_c^2, eps_g, eps_g^2.
@@ -1172,6 +1307,95 @@ int vf_compose_loss_bwd(const float* unet_out, const int* off, const float* targ
         hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
                            gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
     VF_RETURN_LAST_ERROR();
+}
+
+// vf_compose_loss_fwd with a per-sample scale (DEVICE float [B], the importance weight of level_sampler.h): sample_w then
+// holds 2 B floats, w_b scale_b (what the loss and vf_compose_loss_bwd use) and then w_b alone.  scale == NULL is
+// vf_compose_loss_fwd itself.
+int vf_compose_loss_fwd_scaled(const float* unet_out, const int* off, const float* target, const float* level,
+                               const float* scale, float* noise_hat, float* loss_part, float* sample_loss,
+                               float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B, int Cout, int HW,
+                               int weighting, int penalty, float delta, int weight_kind, float a, float b, int K,
+                               void* stream) {
+    if (scale == nullptr)
+        return vf_compose_loss_fwd(unet_out, off, target, level, noise_hat, loss_part, sample_loss, sample_w, loss,
+                                   bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream);
+    if (B <= 0) return 0;
+    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
+    if (!target || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = chunks_for(3 * HW / 4);
+    const dim3 grid(ch, B), block(256);
+    if (penalty == VF_LOSS_L1)
+        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_L1>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           loss_part, Cout, HW, weighting, delta);
+    else if (penalty == VF_LOSS_HUBER)
+        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_HUBER>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           loss_part, Cout, HW, weighting, delta);
+    else
+        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
+                           loss_part, Cout, HW, weighting, delta);
+    hipLaunchKernelGGL(compose_loss_finish_scaled_kernel, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
+                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b);
+    VF_RETURN_LAST_ERROR();
+}
+
+// ---- loss-aware noise-level sampling (level_sampler.h) ----
+// Either (seed, ids) or words (DEVICE int64 [B], values in [0, 2^32)); c [K + 1], iw [K], ready [1] in device memory.
+// u / level: seeded path only, both optional.
+int vf_draw_level(unsigned long long seed, const long long* ids, const long long* words, const float* gammas, int T,
+                  int K, const unsigned long long* c, const float* iw, const int* ready, long long* t, float* u,
+                  float* level, float* iw_out, int B, void* stream) {
+    if (B <= 0) return 0;
+    if (!vf_level_args_ok(T, K) || (ids == nullptr) == (words == nullptr)) return (int)hipErrorInvalidValue;
+    if (!c || !iw || !ready || !t || !iw_out || (level && !gammas) || (!ids && (u || level)))
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(draw_level_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, seed, ids, words, gammas,
+                       T, K, c, iw, ready, t, u, level, iw_out, B);
+    VF_RETURN_LAST_ERROR();
+}
+
+// One step's statistics into m / seen [K], then ready and (when ready) c [K + 1] / iw [K].  sample_w NULL: w = 1.
+int vf_level_stats(const float* sample_loss, const float* sample_w, const long long* t, int B, int T, int K, float beta,
+                   int warmup, double eps, float* m, int* seen, unsigned long long* c, float* iw, int* ready,
+                   void* stream) {
+    if (B <= 0) return 0;
+    if (!vf_level_args_ok(T, K) || !(beta >= 0.0f && beta < 1.0f) || warmup < 0) return (int)hipErrorInvalidValue;
+    if (!(eps * 4294967296.0 >= 2.0 * (double)(T - 1)) || !(eps <= 1.0)) return (int)hipErrorInvalidValue;
+    if (!sample_loss || !t || !m || !seen || !c || !iw || !ready) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(level_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, sample_loss, sample_w, t, B, T, K,
+                       beta, warmup, eps, m, seen, c, iw, ready);
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirrors: the functions of level_sampler.h on the CPU.  HOST pointers, no stream.
+// masses q [K] (>= 0, finite positive sum) -> c [K + 1], lo [K + 1] (lo[K] = T), iw [K]
+int vf_level_table_host(const double* q, int T, int K, double eps, unsigned long long* c, int* lo, float* iw) {
+    if (!vf_level_args_ok(T, K) || !(eps * 4294967296.0 >= 2.0 * (double)(T - 1)) || !(eps <= 1.0))
+        return (int)hipErrorInvalidValue;
+    for (int k = 0; k < K; ++k)
+        if (!(q[k] >= 0.0)) return (int)hipErrorInvalidValue;
+    if (!vf_level_cuts(q, T, K, eps, c)) return (int)hipErrorInvalidValue;
+    for (int k = 0; k <= K; ++k) lo[k] = vf_level_lo(k, T, K);
+    for (int k = 0; k < K; ++k) iw[k] = vf_level_iw(lo[k + 1] - lo[k], T, c[k + 1] - c[k]);
+    return 0;
+}
+
+// words x [n] + the table -> t [n], iw_out [n] (the `ready` draw)
+int vf_level_draw_host(const unsigned* x, int n, int T, int K, const unsigned long long* c, const float* iw,
+                       long long* t, float* iw_out) {
+    if (n < 0 || !vf_level_args_ok(T, K) || c[0] != 0 || c[K] != (1ull << 32)) return (int)hipErrorInvalidValue;
+    for (int k = 0; k < K; ++k)
+        if (c[k + 1] <= c[k]) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i) {
+        int k;
+        t[i] = vf_level_draw(x[i], c, T, K, &k);
+        iw_out[i] = iw[k];
+    }
+    return 0;
 }
 
 // Host mirror: vf_loss_weight itself on the CPU.  HOST pointers, no stream.

@@ -133,13 +133,17 @@ def save_checkpoint(path, model, optimizer, **extra):
 def load_checkpoint(path, model, optimizer=None, device=None):
     """Loads "model" (and "optimizer" if given and present); returns the remaining entries.
     An "ema" entry (save_checkpoint(..., ema=trainer.ema_state_dict())) is restored into an optimizer that keeps a
-    weight EMA (optim.FusedAdam(ema_decay=...)) and, like every extra entry, also returned."""
+    weight EMA (optim.FusedAdam(ema_decay=...)) and, like every extra entry, also returned.  A "level_sampler" entry
+    (save_checkpoint(..., level_sampler=model.level_sampler.state_dict())) is restored into a model that has had the same
+    set_level_sampler(...) call: the statistics and the proposal table continue where they were."""
     sd = torch.load(path, map_location=device, weights_only=False)
     model.load_state_dict(sd["model"])
     if optimizer is not None and "optimizer" in sd and sd["optimizer"].get("state"):
         optimizer.load_state_dict(sd["optimizer"])
     if sd.get("ema") and getattr(optimizer, "ema_decay", None) is not None:
         optimizer.load_ema_state_dict(sd["ema"])
+    if sd.get("level_sampler") and getattr(model, "level_sampler", None) is not None:
+        model.level_sampler.load_state_dict(sd["level_sampler"])
     return {k: v for k, v in sd.items() if k not in ("model", "optimizer")}
 
 

@@ -363,8 +363,8 @@ class _ComposeLossOptFn(torch.autograd.Function):
     (non-differentiable) output: the same two launches forward and one backward."""
 
     @staticmethod
-    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt):
-        _check(out, target, level, bin_sum)
+    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, scale=None):
+        _check(out, target, level, bin_sum, scale)
         S, Cout, H, W = out.shape
         if level.numel() != B:
             raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
@@ -374,43 +374,222 @@ class _ComposeLossOptFn(torch.autograd.Function):
             if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
                 raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
         nh = torch.empty(B, 3, H, W, device=out.device, dtype=torch.float32)
-        buf = torch.empty(B * 66 + 1, device=out.device, dtype=torch.float32)   # partials | sample_loss | sample_w | loss
-        sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * 66:]
-        _call("vf_compose_loss_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(level), _ptr(nh),
-              _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
-              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
-              delta, kind, a, b, K, _stream())
+        if scale is None:
+            buf = torch.empty(B * 66 + 1, device=out.device, dtype=torch.float32)   # partials | sample_loss | sample_w | loss
+            sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * 66:]
+            _call("vf_compose_loss_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(level), _ptr(nh),
+                  _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
+                  None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
+                  delta, kind, a, b, K, _stream())
+            weight = sample_w
+        else:                     # partials | sample_loss | w scale | w | loss  (csrc/level_sampler.h)
+            if scale.numel() != B:
+                raise ValueError(f"compose_loss needs one scale per sample: {scale.numel()} for a batch of {B}")
+            buf = torch.empty(B * 67 + 1, device=out.device, dtype=torch.float32)
+            sample_loss, sample_w, weight, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * 66:B * 67], buf[B * 67:]
+            _call("vf_compose_loss_fwd_scaled", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(level),
+                  _ptr(scale), _ptr(nh), _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
+                  None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
+                  delta, kind, a, b, K, _stream())
         ctx.save_for_backward(out, target, nh, off, sample_w)
         ctx.B, ctx.weighting, ctx.penalty, ctx.delta = B, int(weighting), penalty, delta
-        ctx.mark_non_differentiable(sample_loss)
-        return loss.reshape(()), sample_loss
+        ctx.mark_non_differentiable(sample_loss, weight)
+        return loss.reshape(()), sample_loss, weight
 
     @staticmethod
-    def backward(ctx, gloss, _gsample):
+    def backward(ctx, gloss, _gsample, _gweight):
         out, target, nh, off, sample_w = ctx.saved_tensors
         S, Cout, H, W = out.shape
         gloss = _c(gloss.reshape(1).float())
         dout = torch.empty_like(out)
         _call("vf_compose_loss_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(nh), _ptr(gloss),
               _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, _stream())
-        return (dout,) + (None,) * 12
+        return (dout,) + (None,) * 13
 
 
 def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delta=1.0, weight_kind=None, a=0.0, b=0.0,
-                 hist=None):
+                 hist=None, sample_scale=None, want_weight=False):
     """compose_mse_loss with options: -> (loss, sample_loss).  d = compose(unet_out) - target;
     penalty "mse" d^2 | "l1" |d| | "huber" (F.huber_loss with `delta`);  sample_loss[b] = mean_i rho(d_bi) (B,), detached;
     weight_kind None | "min_snr" (w = min(1, a (1 - g) / g)) | "p2" (w = (a + g / (1 - g))^-b) of g = level[b], the
     sample's gamma (device float32 (B,));  loss = sum_b w_b sample_loss[b] / B, differentiable in unet_out.
     hist = (bin_sum float32 [K], bin_cnt int32 [K]) device accumulators: bin min(K - 1, int(g K)) receives the
-    UNWEIGHTED sample_loss[b] and a count; they persist across calls (the caller zeroes them)."""
+    UNWEIGHTED sample_loss[b] and a count; they persist across calls (the caller zeroes them).
+    sample_scale (device float32 (B,), default None: the launches above, untouched): a per-sample factor on w_b -- the
+    importance weight of a non-uniform timestep draw (draw_level); loss = sum_b w_b scale_b sample_loss[b] / B through a
+    sibling of the finish kernel, sample_loss and the histogram stay unweighted.
+    want_weight=True: -> (loss, sample_loss, w) with w (B,) the noise-level weight ALONE (what level_stats reads)."""
     if penalty not in PENALTIES:
         raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
     if weight_kind not in WEIGHT_KINDS:
         raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2'")
     bin_sum, bin_cnt = hist if hist is not None else (None, None)
-    return _ComposeLossOptFn.apply(unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty],
-                                   float(delta), WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt)
+    if sample_scale is not None:
+        sample_scale = _c(sample_scale.reshape(-1))
+    loss, sample_loss, weight = _ComposeLossOptFn.apply(
+        unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty], float(delta),
+        WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, sample_scale)
+    return (loss, sample_loss, weight) if want_weight else (loss, sample_loss)
+
+
+# ---- loss-aware noise-level sampling (csrc/level_sampler.h holds the specification) ----
+LEVEL_MAX_BINS = 1024
+LEVEL_KINDS = ("loss_aware", "fixed")
+
+
+def level_table_host(q, T, K, uniform_mix):
+    """The host mirror of the table: masses q (K,) -> (c int64 (K+1,), lo int32 (K+1,), iw float32 (K,)) CPU tensors."""
+    q = torch.as_tensor(q, dtype=torch.float64).reshape(-1).contiguous()
+    if q.numel() != K:
+        raise ValueError(f"the proposal needs one mass per bin: {q.numel()} masses for {K} bins")
+    c = torch.empty(K + 1, dtype=torch.int64)
+    lo = torch.empty(K + 1, dtype=torch.int32)
+    iw = torch.empty(K, dtype=torch.float32)
+    rc = _lib.load().vf_level_table_host(ctypes.c_void_p(q.data_ptr()), int(T), int(K), float(uniform_mix),
+                                         ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(lo.data_ptr()),
+                                         ctypes.c_void_p(iw.data_ptr()))
+    if rc != 0:
+        raise ValueError("the proposal masses must be non-negative with a finite positive sum (and T, K, uniform_mix valid)")
+    return c, lo, iw
+
+
+def level_draw_host(x, T, K, c, iw):
+    """The host mirror of the draw: words x (any integer tensor, values in [0, 2^32)) + table -> (t int64, iw float32)."""
+    x = torch.as_tensor(x).reshape(-1).to(torch.int64)
+    x32 = torch.from_numpy((x.numpy() & 0xFFFFFFFF).astype("uint32").view("int32"))      # the 32-bit patterns
+    c, iw = c.to(torch.int64).contiguous(), iw.to(torch.float32).contiguous()
+    t = torch.empty(x.numel(), dtype=torch.int64)
+    w = torch.empty(x.numel(), dtype=torch.float32)
+    rc = _lib.load().vf_level_draw_host(ctypes.c_void_p(x32.data_ptr()), x.numel(), int(T), int(K),
+                                        ctypes.c_void_p(c.data_ptr()), ctypes.c_void_p(iw.data_ptr()),
+                                        ctypes.c_void_p(t.data_ptr()), ctypes.c_void_p(w.data_ptr()))
+    if rc != 0:
+        raise ValueError("not a proposal table: c must rise strictly from 0 to 2^32 over K + 1 entries")
+    return t, w
+
+
+def check_level_sampler(kind, T, bins, probs, ema, warmup, uniform_mix):
+    """The checked settings of a level sampler -> (K, probs | None as a float64 CPU tensor, ema, warmup, uniform_mix);
+    ValueError for anything else.  Host only, no GPU."""
+    if kind not in LEVEL_KINDS:
+        raise ValueError(f"unknown level sampler {kind!r}: one of None, 'loss_aware', 'fixed'")
+    if isinstance(bins, bool) or not isinstance(bins, int) or bins < 1:
+        raise ValueError(f"bins must be a positive integer, got {bins!r}")
+    if bins > min(T - 1, LEVEL_MAX_BINS):
+        raise ValueError(f"bins must be at most min(T - 1, {LEVEL_MAX_BINS}) = {min(T - 1, LEVEL_MAX_BINS)}, got {bins}")
+    ema, uniform_mix = float(ema), float(uniform_mix)
+    if not 0.0 <= ema < 1.0:
+        raise ValueError(f"ema must be in [0, 1), got {ema}")
+    if isinstance(warmup, bool) or not isinstance(warmup, int) or warmup < 0:
+        raise ValueError(f"warmup must be a non-negative integer, got {warmup!r}")
+    if not uniform_mix <= 1.0 or uniform_mix * 2.0 ** 32 < 2 * (T - 1):
+        raise ValueError(f"uniform_mix must be in [2 (T - 1) / 2^32, 1] = [{2 * (T - 1) / 2.0 ** 32:.3g}, 1] so that every "
+                         f"timestep keeps at least one word, got {uniform_mix}")
+    if kind == "fixed":
+        if probs is None:
+            raise ValueError("a 'fixed' level sampler needs probs= (one mass per bin)")
+        probs = torch.as_tensor(probs, dtype=torch.float64).detach().cpu().reshape(-1)
+        if probs.numel() != bins:
+            raise ValueError(f"probs needs one mass per bin: {probs.numel()} masses for {bins} bins")
+        if not bool(torch.isfinite(probs).all()) or bool((probs < 0).any()):
+            raise ValueError("probs must be finite and non-negative")
+        if not float(probs.sum()) > 0:
+            raise ValueError("probs must not be all zero")
+    elif probs is not None:
+        raise ValueError("probs= belongs to the 'fixed' level sampler")
+    return bins, probs, ema, warmup, uniform_mix
+
+
+class LevelSampler:
+    """The device state of a noise-level sampler over T timesteps in K bins (csrc/level_sampler.h): the proposal table
+    c int64 (K+1,) / iw float32 (K,), ready int32 (1,) and, for "loss_aware", the statistics m float32 (K,) /
+    seen int32 (K,).  "fixed": the table of `probs`, normalised by the host mirror, ready from the start and never
+    updated.  "loss_aware": starts not ready (the uniform draw, weight 1) with a uniform table; level_stats() feeds it.
+    The tensors are updated in place for the sampler's whole life: captured launches address them."""
+
+    def __init__(self, kind, T, device, bins, probs=None, ema=0.9, warmup=10, uniform_mix=0.01):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("a level sampler lives on the GPU (its draw and statistics are HIP kernels)")
+        K, probs, ema, warmup, uniform_mix = check_level_sampler(kind, int(T), bins, probs, ema, warmup, uniform_mix)
+        self.kind, self.T, self.K, self.ema, self.warmup, self.uniform_mix = kind, int(T), K, ema, warmup, uniform_mix
+        c, lo, iw = level_table_host(torch.ones(K, dtype=torch.float64) if probs is None else probs, self.T, K, uniform_mix)
+        self.n = (lo[1:] - lo[:-1]).to(device)
+        self.c, self.iw = c.to(device), iw.to(device)
+        self.ready = torch.full((1,), int(kind == "fixed"), dtype=torch.int32, device=device)
+        self.m = torch.zeros(K, dtype=torch.float32, device=device)
+        self.seen = torch.zeros(K, dtype=torch.int32, device=device)
+
+    def proposal(self):
+        """-> (p (K,) float64: the bin masses width_k / 2^32 of the table as it stands, or n_k / (T - 1) while not ready;
+        seen (K,) int32; ready (1,) bool).  Device tensors, no sync."""
+        p = (self.c[1:] - self.c[:-1]).to(torch.float64) / 2.0 ** 32
+        ready = self.ready != 0
+        return torch.where(ready, p, self.n.to(torch.float64) / (self.T - 1)), self.seen.clone(), ready
+
+    def state_dict(self):
+        return dict(kind=self.kind, T=self.T, bins=self.K, ema=self.ema, warmup=self.warmup, uniform_mix=self.uniform_mix,
+                    c=self.c.cpu(), iw=self.iw.cpu(), ready=self.ready.cpu(), m=self.m.cpu(), seen=self.seen.cpu())
+
+    def load_state_dict(self, sd):
+        for k, mine in (("kind", self.kind), ("T", self.T), ("bins", self.K)):
+            if sd[k] != mine:
+                raise ValueError(f"the saved level sampler has {k} = {sd[k]!r}, this one {mine!r}")
+        c = torch.as_tensor(sd["c"]).to(torch.int64).cpu()
+        if c.numel() != self.K + 1 or int(c[0]) != 0 or int(c[-1]) != 1 << 32 or not bool((c[1:] > c[:-1]).all()):
+            raise ValueError("the saved proposal table does not rise strictly from 0 to 2^32 over bins + 1 entries")
+        self.ema, self.warmup, self.uniform_mix = float(sd["ema"]), int(sd["warmup"]), float(sd["uniform_mix"])
+        self.c.copy_(c)
+        for name in ("iw", "ready", "m", "seen"):
+            dst = getattr(self, name)
+            dst.copy_(torch.as_tensor(sd[name]).to(dst.dtype).reshape(dst.shape))
+
+
+def draw_level(sampler, gammas, seed=None, ids=None, words=None, want_u=False):
+    """draw_train through a LevelSampler's table: -> (t (B,) int64, level (B,) | None, u (B,) | None, iw (B,) float32).
+    Either seed + ids (word 0 of the sample's training-scalars call picks t; u and level as draw_train) or words, a device
+    int64 (B,) of values in [0, 2^32) (the unseeded path: level and u are None, the caller draws u).  While the sampler
+    is not ready: draw_train's t and iw = 1.  One launch, no host sync."""
+    _check(gammas)
+    if gammas.numel() != sampler.T:
+        raise ValueError(f"the level sampler was built for T = {sampler.T}, the schedule has {gammas.numel()} levels")
+    if (seed is None) == (words is None):
+        raise ValueError("draw_level takes either seed= (with ids=) or words=")
+    dev = gammas.device
+    if words is None:
+        B = ids.numel()
+        _check_ids(ids, B)
+        src = (_seed(seed), ctypes.c_void_p(ids.data_ptr()), None)
+    else:
+        B = words.numel()
+        if not words.is_cuda or words.dtype != torch.int64 or not words.is_contiguous():
+            raise _lib.VFHipError("words must be a contiguous device int64 tensor (values in [0, 2^32))")
+        src = (0, None, ctypes.c_void_p(words.data_ptr()))
+    t = torch.empty(B, device=dev, dtype=torch.int64)
+    iw = torch.empty(B, device=dev, dtype=torch.float32)
+    level = torch.empty(B, device=dev, dtype=torch.float32) if words is None else None
+    u = torch.empty(B, device=dev, dtype=torch.float32) if (want_u and words is None) else None
+    _call("vf_draw_level", *src, _ptr(gammas), sampler.T, sampler.K, ctypes.c_void_p(sampler.c.data_ptr()),
+          _ptr(sampler.iw), ctypes.c_void_p(sampler.ready.data_ptr()), ctypes.c_void_p(t.data_ptr()), _ptr(u),
+          _ptr(level), _ptr(iw), B, _stream())
+    return t, level, u, iw
+
+
+def level_stats(sampler, sample_loss, sample_w, t):
+    """One step's statistics into a "loss_aware" sampler, then its table: r_b = (sample_w[b] sample_loss[b])^2 into
+    bin(t[b]) (sample_w None: 1; it is the noise-level weight ALONE), EMA per bin, ready / c / iw rebuilt on the device.
+    One one-workgroup launch, no host sync, no atomics."""
+    if sampler.kind != "loss_aware":
+        raise ValueError("only a 'loss_aware' level sampler keeps statistics")
+    _check(sample_loss, sample_w)
+    B = sample_loss.numel()
+    if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != B or \
+            (sample_w is not None and sample_w.numel() != B):
+        raise _lib.VFHipError(f"level_stats needs t (contiguous device int64) and sample_w with {B} elements each")
+    _call("vf_level_stats", _ptr(sample_loss), _ptr(sample_w), ctypes.c_void_p(t.data_ptr()), B, sampler.T, sampler.K,
+          sampler.ema, sampler.warmup, sampler.uniform_mix, _ptr(sampler.m),
+          ctypes.c_void_p(sampler.seen.data_ptr()), ctypes.c_void_p(sampler.c.data_ptr()), _ptr(sampler.iw),
+          ctypes.c_void_p(sampler.ready.data_ptr()), _stream())
 
 
 def compose(unet_out, off, B, max_views, weighting, want_weights=True):

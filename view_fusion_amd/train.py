@@ -132,7 +132,8 @@ def split_batch(batch, extra, accum_steps):
 class _StepGraph:
     """One captured training iteration (forward, backward, Adam) for one batch geometry -- or, with accum_steps > 1, one
     captured micro-batch (forward, backward, the accumulate launch)."""
-    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum", "sample", "drop")
+    __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum", "sample", "drop",
+                 "level")
 
     def __init__(self):
         self.graph, self.seen, self.accum = None, 0, None
@@ -199,7 +200,19 @@ class Trainer:
     model's too, and p is part of the same key: a change between steps drops the captured steps.  With seed= a sample's
     mask is a function of (seed, sample id) -- the same under accum_steps, graph replay and any split over ranks;
     `model.last_cond_drop` is a static buffer of the captured step (the last micro-batch's with accum_steps > 1).  An
-    injected `cond_drop=` mask runs the step eagerly, like every injected argument that is not a graph input."""
+    injected `cond_drop=` mask runs the step eagerly, like every injected argument that is not a graph input.
+
+    Noise-level sampling (`model.set_level_sampler(...)`, csrc/level_sampler.h; default None: nothing above changes) is the
+    model's as well, and every call of it drops the captured steps.  Its three launches -- the table draw in place of the
+    uniform one, the scaled loss finish, the statistics update -- are part of the captured step: the table, the
+    statistics and the ready flag live in device memory that the sampler keeps for its whole life, so a replay draws from
+    the table as the step before left it, and replay equals eager bit for bit.  `model.last_t` /
+    `model.last_importance_weight` are static buffers of the captured step; level_proposal() reads the table.  With
+    accum_steps > 1 every micro-batch draws from the table as it stands and then updates it, so later micro-batches of a
+    step see an updated proposal: equality with the undivided batch is NOT claimed then (each micro-batch is still
+    unbiased on its own).  Single process, GPU model only: world > 1 or a CPU model with a level sampler raises ValueError
+    (the statistics would be rank-local and the ranks' proposals would drift apart; a reduction of them is not built).
+    Checkpoints: drivers.save_checkpoint(..., level_sampler=model.level_sampler.state_dict())."""
     GRAPH_AFTER = 2
     GRAPH_MAX = 96
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
@@ -229,6 +242,8 @@ class Trainer:
                                torch.zeros(loss_bins, device=dev, dtype=torch.int32))
         self.loss_bins = loss_bins
         self.module = model
+        self.world = world
+        self._check_level_sampler()
         # seed: the training draws come from the counter-based generator (csrc/rng.h) keyed by a global sample index
         # (step_sample_ids), not from torch's device generator; None (default): as before
         self.seed, self.global_batch = seed, global_batch
@@ -291,7 +306,6 @@ class Trainer:
         self._loss_key = None       # ViewFusion.loss_key() the kept graphs were captured under
         self._graph_epoch = None    # FusedAdam.graph_epoch the kept graphs were captured under (None: none captured)
         self.graph_steps = 0        # iterations (accum_steps > 1: micro-batches) that ran as a replay (diagnostics / tests)
-        self.world = world
         self._check_base = self.GRAPH_AFTER     # multi-rank agreement: flag read at _check_base + 1, 4, 16, then every AGREE_EVERY
         self.demotions = 0
 
@@ -326,6 +340,25 @@ class Trainer:
             bin_sum.zero_()
             bin_cnt.zero_()
         return mean, count
+
+    def _check_level_sampler(self):
+        if getattr(self.module, "_level_spec", None) is None:
+            return
+        if self.world > 1:
+            raise ValueError("a level sampler is single-process only: its loss statistics are rank-local, so the ranks' "
+                             "proposals would differ, and a reduction of them across ranks is not built")
+        if not next(self.module.parameters()).is_cuda:
+            raise ValueError("a level sampler draws and updates inside HIP kernels: the model must be on the GPU")
+
+    def level_proposal(self):
+        """-> (p (K,) float64, seen (K,) int32, ready (1,) bool) of the model's level sampler: the probability of each
+        bin of timesteps as the table stands (the uniform n_k / (T - 1) while a "loss_aware" sampler is warming up), how
+        many samples each bin's statistic has seen, and whether the table is in use.  Device tensors, computed without a
+        host sync: reading them is the caller's sync."""
+        smp = getattr(self.module, "level_sampler", None)
+        if smp is None:
+            raise ValueError("level_proposal needs model.set_level_sampler(...) on a GPU model")
+        return smp.proposal()
 
     def ema_state_dict(self):
         return self.opt.ema_state_dict()
@@ -494,9 +527,11 @@ class Trainer:
         e.loss, e.graph = loss.detach(), g
         # the loss-option kernels' per-sample outputs are static buffers of this graph (None on the default path)
         e.sample = None
-        if getattr(self.module, "_loss", None) is not None or getattr(self.module, "loss_hist", None) is not None:
+        if getattr(self.module, "_loss", None) is not None or getattr(self.module, "loss_hist", None) is not None or \
+                getattr(self.module, "_level_spec", None) is not None:
             e.sample = (self.module.last_sample_loss, self.module.last_level)
         e.drop = getattr(self.module, "last_cond_drop", None)      # conditioning dropout: the step's mask, likewise
+        e.level = (getattr(self.module, "last_t", None), getattr(self.module, "last_importance_weight", None))
         e.grads = list(grads)
         # what the captured launches address besides the graph's own pool
         e.keep = (fix, tables, offs, getattr(self.module, "gammas", None))
@@ -516,6 +551,8 @@ class Trainer:
             self.module.last_sample_loss, self.module.last_level = e.sample
         if hasattr(self.module, "last_cond_drop"):
             self.module.last_cond_drop = e.drop
+        if hasattr(self.module, "last_t"):             # the level sampler's draw: static buffers of the graph, likewise
+            self.module.last_t, self.module.last_importance_weight = e.level
         if accum is not None:                          # a micro-batch: its gradient goes into the accumulators, which
             self.opt.accum_tick(e.accum, *accum)       # the optimizer step after the last one reads and leaves in .grad
             e.graph.replay()
@@ -603,6 +640,7 @@ class Trainer:
             if self._graphs:
                 self._drop_graphs()
             self._loss_key = loss_key
+            self._check_level_sampler()
         key, vc = self._graph_key(batch, extra) or (None, None)
         if key is not None and accum is None and self._graph_epoch is not None and \
                 self.opt.graph_epoch != self._graph_epoch:      # (a micro-batch graph addresses no Adam state)

@@ -31,6 +31,10 @@ row per sample next to the conditional ones and extrapolates the noise predictio
 for what g > 1 does to a pixel-space sample: dynamic thresholding of y0_hat (clamp to the per-sample q-quantile of
 |y0_hat|, then divide by it) in place of the static clamp, and the guided noise rescaled to the conditional one's
 standard deviation.  Both off by default; both defined at the head of csrc/diffusion.hip.
+
+`set_level_sampler(...)` (default None: uniform timesteps, every launch as before) draws a training sample's timestep
+from a proposal over bins of timesteps -- a fixed one, or one that follows the loss's second moment per bin -- and
+multiplies the sample's loss by the importance weight that keeps the objective unbiased; see csrc/level_sampler.h.
 """
 import torch
 from torch import nn
@@ -52,6 +56,12 @@ class ViewFusion(nn.Module):
         # conditioning dropout (set_cond_dropout) and the mask of the last training forward: plain attributes too
         self._cond_drop_p = 0.0
         self.last_cond_drop = None
+        # noise-level sampling (set_level_sampler): the settings, the device state (ops.LevelSampler; GPU models only) and
+        # the last training forward's draw: plain attributes too
+        self._level_spec = None
+        self._level_gen = 0
+        self.level_sampler = None
+        self.last_t = self.last_importance_weight = None
 
     # -- training objective -------------------------------------------------------------------
     def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
@@ -98,12 +108,49 @@ class ViewFusion(nn.Module):
             raise ValueError(f"the conditioning-dropout probability must be in [0, 1], got {p}")
         self._cond_drop_p = p
 
+    def set_level_sampler(self, kind=None, bins=None, probs=None, ema=0.9, warmup=10, uniform_mix=0.01):
+        """How forward() draws a training sample's timestep when `t` is not injected (csrc/level_sampler.h).
+
+        kind None (the default): uniform on [1, T - 1], the launches and the bits of before; removes a sampler.
+        "fixed": bin k of `bins` equal bins of timesteps is drawn with probability proportional to probs[k] (K masses,
+        non-negative, not all zero; normalised on the host) -- emphasise a band of noise levels by hand.
+        "loss_aware": bin k is drawn in proportion to n_k sqrt(m_k), m_k an exponential moving average (factor `ema` per
+        update, default 0.9) of (w_b s_b)^2 over the samples that fell into the bin -- the loss-second-moment resampler of
+        Improved DDPM with one EMA per bin in place of the paper's ten-loss history per timestep.  Until every bin has
+        seen `warmup` samples (default 10, the paper's history length) the draw is the uniform one, bit for bit.
+        bins (default min(64, T - 1); at most min(T - 1, 1024)).  uniform_mix (default 0.01): the share eps of the uniform
+        proposal mixed in, p_k = (1 - eps) q_k / sum q + eps n_k / (T - 1); it bounds the importance weight by 1 / eps and
+        must be at least 2 (T - 1) / 2^32.
+        Every sample's loss is multiplied by its importance weight (T - 1)^-1 / P(t), so the expected gradient is the
+        uniform objective's; this runs the loss-option kernels (ops.compose_loss) even with set_loss() at its default, plus,
+        for "loss_aware" in training mode, one one-workgroup statistics launch after the loss.  An injected `t` bypasses
+        the sampler entirely: no weight, no update.  `last_t` / `last_importance_weight` are the last sampled forward's
+        draw (device tensors, no sync; None otherwise).  The state (`level_sampler`, an ops.LevelSampler with
+        state_dict() / load_state_dict()) is a plain attribute: no parameter, no buffer.  Needs the noise schedule
+        (set_new_noise_schedule) and, to run, a GPU model.  A Trainer drops its captured steps when this is called."""
+        from . import ops
+        self._level_gen += 1
+        if kind is None:
+            self._level_spec = self.level_sampler = None
+            return
+        T = getattr(self, "num_timesteps", None)
+        if T is None:
+            raise ValueError("set_level_sampler needs the noise schedule: call set_new_noise_schedule first")
+        if bins is None:
+            bins = min(64, T - 1)
+        K, probs, ema, warmup, uniform_mix = ops.check_level_sampler(kind, T, bins, probs, ema, warmup, uniform_mix)
+        self._level_spec = dict(kind=kind, bins=K, probs=probs, ema=ema, warmup=warmup, uniform_mix=uniform_mix)
+        dev = self.gammas.device
+        self.level_sampler = ops.LevelSampler(kind, T, dev, **{k: v for k, v in self._level_spec.items() if k != "kind"}) \
+            if dev.type == "cuda" else None
+
     def loss_key(self):
-        """What a captured training step depends on besides its inputs: the objective, the attached histogram and the
-        conditioning-dropout probability."""
+        """What a captured training step depends on besides its inputs: the objective, the attached histogram, the
+        conditioning-dropout probability and the level sampler (every set_level_sampler call counts)."""
         h = self.loss_hist
         return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
-                None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p)
+                None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p,
+                self._level_gen)
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -343,11 +390,22 @@ class ViewFusion(nn.Module):
         # conditioning dropout (set_cond_dropout): an injected mask wins; else drawn in training mode when p > 0
         drop_p = self._cond_drop_p if (cond_drop is None and self.training) else 0.0
         drop = cond_drop
+        # the level sampler (set_level_sampler) takes part only when t is drawn here
+        smp, iw = None, None
+        if self._level_spec is not None and t is None:
+            smp = self.level_sampler
+            if smp is None:
+                raise ValueError("the level sampler runs on the GPU only: move the model there and call "
+                                 "set_level_sampler again")
         if seed is not None:              # whatever was not injected comes from the counter-based generator
             ids = ops.sample_ids(dev, b, sample_ids)
             if drop_p > 0:                # word 2 of the call that gives the sample's t and u
                 drop = ops.draw_cond_drop(seed, ids, drop_p)
-            if t is None or u is None:
+            if smp is not None:           # draw_train's sibling: the same words, t through the proposal table
+                t, level_d, u_d, iw = ops.draw_level(smp, self.gammas, seed=seed, ids=ids)
+                if u is None:
+                    level = level_d
+            elif t is None or u is None:
                 t_d, level_d, u_d = ops.draw_train(seed, ids, self.gammas, want_u=t is not None)
                 if t is None and u is None:
                     t, level = t_d, level_d
@@ -358,6 +416,8 @@ class ViewFusion(nn.Module):
             if noise is None:             # a launch of its own in front of the stacking kernel (which is unchanged)
                 noise = ops.randn_ids(seed, ids, ops.diffusion.RNG_TRAIN_NOISE, 0, tuple(y_0.shape[1:]))
         # same draw order as the reference: t, u, noise
+        if t is None and smp is not None:     # one 32-bit word per sample where randint draws t
+            t, _, _, iw = ops.draw_level(smp, self.gammas, words=torch.randint(0, 2 ** 32, (b,), device=dev))
         if t is None:
             t = torch.randint(1, self.num_timesteps, (b,), device=dev).long()
         if u is None and level is None:
@@ -375,9 +435,13 @@ class ViewFusion(nn.Module):
         x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S,
                                               drop=drop)
         out = self.denoise_fn(x, angle_s, level_s)
-        if self._loss is None and self.loss_hist is None:
+        self.last_t, self.last_importance_weight = (None, None) if smp is None else (t, iw)
+        if self._loss is None and self.loss_hist is None and smp is None:
             return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
-        loss, sample_loss = ops.compose_loss(out, noise, off, b, bool(self.weighting_train), level,
-                                             **(self._loss or {}), hist=self.loss_hist)
+        loss, sample_loss, weight = ops.compose_loss(out, noise, off, b, bool(self.weighting_train), level,
+                                                     **(self._loss or {}), hist=self.loss_hist, sample_scale=iw,
+                                                     want_weight=True)
         self.last_sample_loss, self.last_level = sample_loss.detach(), level.detach()
+        if smp is not None and smp.kind == "loss_aware" and self.training:
+            ops.level_stats(smp, self.last_sample_loss, weight.detach(), t)
         return loss
