@@ -314,6 +314,23 @@ int vf_level_draw_host(const unsigned* x, int n, int T, int K, const unsigned lo
                        long long* t, float* iw_out);
 /* Host mirror of the weight function: HOST pointers, no stream, no GPU needed. */
 int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, float* out /*[B]*/);
+/* Prediction (the head of csrc/diffusion.hip holds the definition): vf_compose_loss_fwd_scaled / vf_compose_loss_bwd for
+ * pred 1 (v: target = sqrt(g) noise - sqrt(1 - g) y_0) | 2 (x0: target = y_0; noise may be NULL), g = level[b], the target
+ * formed inside the kernels; the weight is the prediction's native one (csrc/loss_weight.h).  noise_hat receives the
+ * composed output in the network's own parameterisation.  pred 0 (eps) is refused: that is the calls above.  Two launches
+ * forward, one backward, no atomics. */
+int vf_compose_loss_pred_fwd(const float* unet_out, const int* off, const float* noise /*|NULL for x0*/,
+                             const float* y_0, const float* level, const float* scale /*[B]|NULL*/, float* noise_hat,
+                             float* loss_part /*[B*64]*/, float* sample_loss /*[B]*/,
+                             float* sample_w /*[2B] ([B] without scale)*/, float* loss, float* bin_sum /*[K]|NULL*/,
+                             int* bin_cnt /*[K]|NULL*/, int B, int Cout, int HW, int weighting, int penalty, float delta,
+                             int weight_kind, float a, float b, int K, int pred, void* stream);
+int vf_compose_loss_pred_bwd(const float* unet_out, const int* off, const float* noise /*|NULL for x0*/,
+                             const float* y_0, const float* level, const float* noise_hat, const float* gloss,
+                             const float* sample_w, float* dout, int B, int Cout, int HW, int weighting, int penalty,
+                             float delta, int pred, void* stream);
+/* Host mirror of the native weight (pred 0 eps | 1 v | 2 x0): HOST pointers, no stream, no GPU needed. */
+int vf_loss_weights_pred_host(const float* level, int B, int pred, int kind, float a, float b, float* out /*[B]*/);
 int vf_p_sample_tail(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,
                      const long long* t, const float* sqrt_recip_gammas, const float* sqrt_recipm1_gammas,
                      const float* posterior_log_variance, const float* posterior_mean_coef1,

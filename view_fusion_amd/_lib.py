@@ -135,6 +135,10 @@ SIGNATURES = {
     "vf_loss_weights_host": [_P, _I, _I, _F, _F, _P],
     "vf_compose_loss_fwd_scaled": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _F, _I,
                                    _P],
+    "vf_compose_loss_pred_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _F, _F, _I,
+                                 _I, _P],
+    "vf_compose_loss_pred_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
+    "vf_loss_weights_pred_host": [_P, _I, _I, _I, _F, _F, _P],
     "vf_draw_level": [_U64, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "vf_level_stats": [_P, _P, _P, _I, _I, _I, _F, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P],
     "vf_level_table_host": [_P, _I, _I, ctypes.c_double, _P, _P, _P],

@@ -32,6 +32,9 @@
 //                   from a proposal table the loss statistics rebuild on the device (level_sampler.h).
 //   three launches  compose_eps_kernel<CFG, FUSED_TAIL> -> sample_stat_kernel (abs_select, quantile_lerp; the same
 //                   selection on a plain buffer: abs_quantile_kernel) -> an EPS tail: the thresholded / rescaled step.
+//   prediction      pred_target4, compose_loss_pred_fwd / _finish_pred / _pred_bwd<PEN, PRED>: the loss-option kernels for
+//                   v- and x0-prediction, the target formed in registers from noise, y_0 and level (same launch count).
+//                   The tails have no sibling: another parameterisation is another (a, b) table pair.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
 //                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.
@@ -79,6 +82,25 @@
 //   floats, denormals and -0 included -- with LDS histograms of 32-bit integer counts (integer adds commute, so LDS
 //   atomics do not make the result depend on their order), and writes stat[b] = {r_b, s_b}; the *_eps tails read eps_g and
 //   stat.  t / kidx / stat all live in device memory: a captured step replays for every step.
+//
+// Prediction: what channels 0..2 of the network mean (Salimans & Ho, "Progressive Distillation", v; Hang et al., Min-SNR,
+// the weights).  This comment is the ONE written definition (the weights: loss_weight.h); tests/prediction_ref.py
+// restates it.  Opt-in: "eps" runs the launches and the bits of before.
+//   g = the level the network is conditioned on: the sample's continuous `level` in training, gammas[t] / gammas[tau[k]]
+//   in sampling.  y_t = sqrt(g) y_0 + sqrt(1 - g) noise as before.  `out` = the composition over the sample's views of
+//   channels 0..2 (softmax of channels 3..5, or the mean), unchanged: the weights sum to 1 and everything below is affine
+//   in `out` with the same y_t in every view, so composing the views' outputs equals composing their noise estimates, and
+//   guiding `out` (g out_c + (1 - g) out_u) equals guiding eps.
+//     prediction   training target                       y0_hat = a y - b out                 c(g)
+//     "eps"        noise                                 a = g^-1/2, b = (1/g - 1)^1/2        1
+//     "v"          sqrt(g) noise - sqrt(1 - g) y_0       a = sqrt(g), b = sqrt(1 - g)         g
+//     "x0"         y_0                                   a = 0,       b = -1  (y0_hat == out)  g / (1 - g)
+//   c(g): the native weight per unit of epsilon-equivalent weight (loss_weight.h).  The penalties, the per-sample loss, the
+//   histogram, the level sampler's importance weight and its (w s)^2 statistic are taken on the native residual.
+//   Guidance rescaling takes sigma of the composed output in the network's own parameterisation (Lin et al.); the
+//   threshold acts on y0_hat.  Everything after y0_hat (posterior, multistep update, threshold, y0_prev) uses y0 alone:
+//   sampling in another parameterisation hands the tails another (a, b) table pair, and no tail kernel changes.
+//   With gamma_T = 0 (a zero-terminal-SNR schedule) the "eps" pair is infinite there; the "v" and "x0" pairs are finite.
 #include "common.h"
 #include "level_sampler.h"
 #include "loss_weight.h"
@@ -1197,6 +1219,185 @@ int sampler_step(const float* unet_out, const int* off, const float* eps, const 
     VF_RETURN_LAST_ERROR();
 }
 
+// ---- prediction: v- and x0-prediction losses (the head of this file; loss_weight.h holds the weights) ----
+// The training target of one element, formed in registers from the noise and y_0 the step already holds:
+//   v   sa noise - sb y_0 with sa = sqrtf(g_b), sb = sqrtf(1 - g_b): sb y_0 is rounded, the rest is one fused multiply-add,
+//       written out so that the forward and the backward kernel form the very same bits;
+//   x0  y_0 itself (the noise is not read).
+template <int PRED>
+__device__ __forceinline__ float4 pred_target4(const float* __restrict__ noise, const float* __restrict__ y_0, size_t o,
+                                               float sa, float sb) {
+    const float4 y = *reinterpret_cast<const float4*>(y_0 + o);
+    if (PRED == VF_PRED_X0) return y;
+    const float4 n = *reinterpret_cast<const float4*>(noise + o);
+    return make_float4(__builtin_fmaf(sa, n.x, -mul_rn(sb, y.x)), __builtin_fmaf(sa, n.y, -mul_rn(sb, y.y)),
+                       __builtin_fmaf(sa, n.z, -mul_rn(sb, y.z)), __builtin_fmaf(sa, n.w, -mul_rn(sb, y.w)));
+}
+
+// compose_loss_fwd_kernel's sibling: noise, y_0 and level in place of a ready-made target.  noise_hat receives the
+// composed output in the network's own parameterisation (what the backward kernel reads back).
+template <int PEN, int PRED>
+__global__ __launch_bounds__(256) void compose_loss_pred_fwd_kernel(const float* __restrict__ out,
+                                                                    const int* __restrict__ off,
+                                                                    const float* __restrict__ noise,
+                                                                    const float* __restrict__ y_0,
+                                                                    const float* __restrict__ level,
+                                                                    float* __restrict__ noise_hat,
+                                                                    float* __restrict__ loss_part, int Cout, int HW,
+                                                                    int weighting, float delta) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const float g = level[b];
+    const float sa = sqrtf(g), sb = sqrtf(1.0f - g);
+    float acc = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        *reinterpret_cast<float4*>(noise_hat + o) = nh;
+        const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
+        acc += (vf_loss_rho<PEN>(nh.x - t.x, delta) + vf_loss_rho<PEN>(nh.y - t.y, delta)) +
+               (vf_loss_rho<PEN>(nh.z - t.z, delta) + vf_loss_rho<PEN>(nh.w - t.w, delta));
+    }
+    acc = block_sum<256>(acc, red);
+    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// compose_loss_finish_kernel / _scaled_kernel with the native weight of the prediction (vf_loss_weight_pred).  scale
+// (nullable): with it sample_w holds 2 B floats, w_s scale[s] then w_s alone, as the scaled kernel writes them; without,
+// B floats.  One workgroup, every address written by one thread, sums in index order.
+__global__ __launch_bounds__(64) void compose_loss_finish_pred_kernel(const float* __restrict__ part,
+                                                                      const float* __restrict__ level,
+                                                                      const float* __restrict__ scale,
+                                                                      float* __restrict__ sample_loss,
+                                                                      float* __restrict__ sample_w,
+                                                                      float* __restrict__ loss,
+                                                                      float* __restrict__ bin_sum,
+                                                                      int* __restrict__ bin_cnt, int B, int ch, int K,
+                                                                      float inv_n, int kind, float a, float b, int pred) {
+    for (int s = threadIdx.x; s < B; s += 64) {
+        float acc = 0.f;
+        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
+        sample_loss[s] = acc * inv_n;
+        const float w = vf_loss_weight_pred(pred, kind, a, b, level[s]);
+        if (scale != nullptr) {
+            sample_w[s] = w * scale[s];
+            sample_w[B + s] = w;
+        } else {
+            sample_w[s] = w;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float acc = 0.f;
+        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
+        *loss = acc / (float)B;
+    }
+    if (bin_sum == nullptr) return;
+    for (int k = threadIdx.x; k < K; k += 64) {
+        float sum = 0.f;
+        int cnt = 0;
+        for (int s = 0; s < B; ++s) {
+            int bin = (int)(level[s] * (float)K);
+            bin = bin > K - 1 ? K - 1 : bin;
+            if (bin == k) {
+                sum += sample_loss[s];
+                ++cnt;
+            }
+        }
+        bin_sum[k] += sum;
+        bin_cnt[k] += cnt;
+    }
+}
+
+// compose_loss_bwd_kernel's sibling: the same target as the forward kernel, formed again, then the same chain rule.
+template <int PEN, int PRED>
+__global__ __launch_bounds__(256) void compose_loss_pred_bwd_kernel(const float* __restrict__ out,
+                                                                    const int* __restrict__ off,
+                                                                    const float* __restrict__ noise,
+                                                                    const float* __restrict__ y_0,
+                                                                    const float* __restrict__ level,
+                                                                    const float* __restrict__ noise_hat,
+                                                                    const float* __restrict__ gloss,
+                                                                    const float* __restrict__ sample_w,
+                                                                    float* __restrict__ dout, int Cout, int HW,
+                                                                    int weighting, float inv_nb, float delta) {
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const float gs = gloss[0] * sample_w[b] * inv_nb;
+    const float lv = level[b];
+    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    const size_t vs = (size_t)Cout * HW;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
+        const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
+        const float4 g = make_float4(gs * vf_loss_drho<PEN>(nh.x - t.x, delta), gs * vf_loss_drho<PEN>(nh.y - t.y, delta),
+                                     gs * vf_loss_drho<PEN>(nh.z - t.z, delta), gs * vf_loss_drho<PEN>(nh.w - t.w, delta));
+        if (!weighting) {
+            const float inv = 1.0f / (float)(v1 - v0);
+            const float4 d = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
+            for (int v = v0; v < v1; ++v) {
+                *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)c * HW + p) = d;
+                if (Cout > 3)
+                    *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)(3 + c) * HW + p) =
+                        make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            continue;
+        }
+        float4 mx, inv;
+        (void)compose4(out, Cout, HW, v0, v1, c, p, 1, &mx, &inv);
+        for (int v = v0; v < v1; ++v) {
+            const float* ep = out + (size_t)v * vs + (size_t)c * HW + p;
+            const float4 e = *reinterpret_cast<const float4*>(ep);
+            const float4 l = *reinterpret_cast<const float4*>(ep + (size_t)3 * HW);
+            const float4 w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
+                                         expf(l.w - mx.w) * inv.w);
+            float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
+            *reinterpret_cast<float4*>(dp) = make_float4(w.x * g.x, w.y * g.y, w.z * g.z, w.w * g.w);
+            *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
+                make_float4(w.x * (e.x - nh.x) * g.x, w.y * (e.y - nh.y) * g.y, w.z * (e.z - nh.z) * g.z,
+                            w.w * (e.w - nh.w) * g.w);
+        }
+    }
+}
+
+template <int PRED>
+void launch_pred_fwd(dim3 grid, hipStream_t st, int penalty, const float* out, const int* off, const float* noise,
+                     const float* y_0, const float* level, float* noise_hat, float* loss_part, int Cout, int HW,
+                     int weighting, float delta) {
+    const dim3 block(256);
+    if (penalty == VF_LOSS_L1)
+        hipLaunchKernelGGL((compose_loss_pred_fwd_kernel<VF_LOSS_L1, PRED>), grid, block, 0, st, out, off, noise, y_0, level,
+                           noise_hat, loss_part, Cout, HW, weighting, delta);
+    else if (penalty == VF_LOSS_HUBER)
+        hipLaunchKernelGGL((compose_loss_pred_fwd_kernel<VF_LOSS_HUBER, PRED>), grid, block, 0, st, out, off, noise, y_0,
+                           level, noise_hat, loss_part, Cout, HW, weighting, delta);
+    else
+        hipLaunchKernelGGL((compose_loss_pred_fwd_kernel<VF_LOSS_MSE, PRED>), grid, block, 0, st, out, off, noise, y_0,
+                           level, noise_hat, loss_part, Cout, HW, weighting, delta);
+}
+
+template <int PRED>
+void launch_pred_bwd(dim3 grid, hipStream_t st, int penalty, const float* out, const int* off, const float* noise,
+                     const float* y_0, const float* level, const float* noise_hat, const float* gloss,
+                     const float* sample_w, float* dout, int Cout, int HW, int weighting, float inv_nb, float delta) {
+    const dim3 block(256);
+    if (penalty == VF_LOSS_L1)
+        hipLaunchKernelGGL((compose_loss_pred_bwd_kernel<VF_LOSS_L1, PRED>), grid, block, 0, st, out, off, noise, y_0, level,
+                           noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
+    else if (penalty == VF_LOSS_HUBER)
+        hipLaunchKernelGGL((compose_loss_pred_bwd_kernel<VF_LOSS_HUBER, PRED>), grid, block, 0, st, out, off, noise, y_0,
+                           level, noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
+    else
+        hipLaunchKernelGGL((compose_loss_pred_bwd_kernel<VF_LOSS_MSE, PRED>), grid, block, 0, st, out, off, noise, y_0,
+                           level, noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1402,6 +1603,62 @@ int vf_level_draw_host(const unsigned* x, int n, int T, int K, const unsigned lo
 int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, float* out) {
     if (B < 0 || kind < VF_LOSS_W_NONE || kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
     for (int s = 0; s < B; ++s) out[s] = vf_loss_weight(kind, a, b, level[s]);
+    return 0;
+}
+
+// ---- prediction (the head of this file): vf_compose_loss_fwd(_scaled) / vf_compose_loss_bwd for pred 1 (v) | 2 (x0),
+// fed noise, y_0 and level instead of a target.  scale (nullable) as in vf_compose_loss_fwd_scaled.  noise may be NULL
+// for x0.  pred 0 (eps) is refused: its path is the entry points above. ----
+int vf_compose_loss_pred_fwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                             const float* level, const float* scale, float* noise_hat, float* loss_part,
+                             float* sample_loss, float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B,
+                             int Cout, int HW, int weighting, int penalty, float delta, int weight_kind, float a, float b,
+                             int K, int pred, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    if (pred != VF_PRED_V && pred != VF_PRED_X0) return (int)hipErrorInvalidValue;
+    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
+    if (!y_0 || (pred == VF_PRED_V && !noise) || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = chunks_for(3 * HW / 4);
+    if (pred == VF_PRED_V)
+        launch_pred_fwd<VF_PRED_V>(dim3(ch, B), st, penalty, unet_out, off, noise, y_0, level, noise_hat, loss_part, Cout,
+                                   HW, weighting, delta);
+    else
+        launch_pred_fwd<VF_PRED_X0>(dim3(ch, B), st, penalty, unet_out, off, noise, y_0, level, noise_hat, loss_part, Cout,
+                                    HW, weighting, delta);
+    hipLaunchKernelGGL(compose_loss_finish_pred_kernel, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
+                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b, pred);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_compose_loss_pred_bwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                             const float* level, const float* noise_hat, const float* gloss, const float* sample_w,
+                             float* dout, int B, int Cout, int HW, int weighting, int penalty, float delta, int pred,
+                             void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta) || !sample_w) return (int)hipErrorInvalidValue;
+    if (pred != VF_PRED_V && pred != VF_PRED_X0) return (int)hipErrorInvalidValue;
+    if (!y_0 || (pred == VF_PRED_V && !noise) || !level || !noise_hat || !gloss || !dout) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid(chunks_for(3 * HW / 4), B);
+    const float inv_nb = 1.0f / ((float)B * 3.0f * (float)HW);
+    if (pred == VF_PRED_V)
+        launch_pred_bwd<VF_PRED_V>(grid, st, penalty, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout,
+                                   Cout, HW, weighting, inv_nb, delta);
+    else
+        launch_pred_bwd<VF_PRED_X0>(grid, st, penalty, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout,
+                                    Cout, HW, weighting, inv_nb, delta);
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirror: vf_loss_weight_pred itself on the CPU (pred 0 | 1 | 2).  HOST pointers, no stream.
+int vf_loss_weights_pred_host(const float* level, int B, int pred, int kind, float a, float b, float* out) {
+    if (B < 0 || kind < VF_LOSS_W_NONE || kind > VF_LOSS_W_P2 || pred < VF_PRED_EPS || pred > VF_PRED_X0)
+        return (int)hipErrorInvalidValue;
+    for (int s = 0; s < B; ++s) out[s] = vf_loss_weight_pred(pred, kind, a, b, level[s]);
     return 0;
 }
 

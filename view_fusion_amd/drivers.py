@@ -135,8 +135,14 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     An "ema" entry (save_checkpoint(..., ema=trainer.ema_state_dict())) is restored into an optimizer that keeps a
     weight EMA (optim.FusedAdam(ema_decay=...)) and, like every extra entry, also returned.  A "level_sampler" entry
     (save_checkpoint(..., level_sampler=model.level_sampler.state_dict())) is restored into a model that has had the same
-    set_level_sampler(...) call: the statistics and the proposal table continue where they were."""
+    set_level_sampler(...) call: the statistics and the proposal table continue where they were.  A "prediction" entry
+    (save_checkpoint(..., prediction=model.prediction)) must name the model's own prediction: ValueError otherwise,
+    before anything is loaded.  Files without the entry load as before."""
     sd = torch.load(path, map_location=device, weights_only=False)
+    mine = getattr(model, "prediction", "eps")
+    if sd.get("prediction") is not None and sd["prediction"] != mine:
+        raise ValueError(f"the checkpoint was trained with prediction {sd['prediction']!r}, the model is set to {mine!r} "
+                         "(set_prediction)")
     model.load_state_dict(sd["model"])
     if optimizer is not None and "optimizer" in sd and sd["optimizer"].get("state"):
         optimizer.load_state_dict(sd["optimizer"])

@@ -50,7 +50,8 @@ from .diffusion import (  # noqa: F401
     _ComposeLossFn, _ComposeLossOptFn, compose, compose_loss, compose_mse_loss, draw_train, gather_level, p_sample_tail, philox_ids, psnr, randn_ids,
     sample_ids, sampler_step, ssim, stack_views, view_offsets, cond_drop_threshold, draw_cond_drop, guidance_scales,
     abs_quantile, quantile_position, threshold_scratch, threshold_settings,
-    LevelSampler, check_level_sampler, draw_level, level_draw_host, level_stats, level_table_host
+    LevelSampler, check_level_sampler, draw_level, level_draw_host, level_stats, level_table_host,
+    PREDICTIONS, _ComposeLossPredFn, check_prediction, loss_weights_pred_host
 )
 from .lpips import (  # noqa: F401
     LPIPS_TAPS, LPIPS_WIDTHS, lpips

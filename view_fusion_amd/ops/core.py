@@ -67,6 +67,7 @@ _CALL_KIND = {"vf_wino44_pack_weights": "pack", "vf_wino44_pack_weights_multi": 
               "vf_swish_fwd": "embed", "vf_swish_bwd": "embed",
               "vf_stack_views": "diffusion", "vf_compose_fwd": "diffusion", "vf_compose_mse_bwd": "diffusion",
               "vf_compose_loss_fwd": "diffusion", "vf_compose_loss_bwd": "diffusion",
+              "vf_compose_loss_pred_fwd": "diffusion", "vf_compose_loss_pred_bwd": "diffusion",
               "vf_compose_loss_fwd_scaled": "diffusion", "vf_draw_level": "diffusion", "vf_level_stats": "diffusion",
               "vf_gather_level": "diffusion", "vf_p_sample_tail": "diffusion",
               "vf_draw_train": "diffusion", "vf_randn_ids": "diffusion", "vf_philox_ids": "diffusion",

@@ -7,6 +7,7 @@ import struct
 import torch
 
 from .. import _lib
+from ..schedule import check_prediction
 from .state import st
 from .core import _c, _call, _check, _ptr, _stream, _workspace
 
@@ -407,8 +408,74 @@ class _ComposeLossOptFn(torch.autograd.Function):
         return (dout,) + (None,) * 13
 
 
+# ---- prediction (csrc/diffusion.hip holds the definition): what channels 0..2 of the network mean ----
+PREDICTIONS = {"eps": 0, "v": 1, "x0": 2}
+
+
+def loss_weights_pred_host(level, prediction="eps", weight_kind=None, a=0.0, b=0.0):
+    """The host mirror of the native loss weight (csrc/loss_weight.h): levels (any float tensor / sequence) -> float32
+    CPU tensor of the same length.  No GPU."""
+    check_prediction(prediction)
+    if weight_kind not in WEIGHT_KINDS:
+        raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2'")
+    lv = torch.as_tensor(level, dtype=torch.float32).detach().cpu().reshape(-1).contiguous()
+    out = torch.empty_like(lv)
+    rc = _lib.load().vf_loss_weights_pred_host(ctypes.c_void_p(lv.data_ptr()), lv.numel(), PREDICTIONS[prediction],
+                                               WEIGHT_KINDS[weight_kind], float(a), float(b),
+                                               ctypes.c_void_p(out.data_ptr()))
+    if rc != 0:
+        raise _lib.VFHipError(f"vf_loss_weights_pred_host failed with {rc}")
+    return out
+
+
+class _ComposeLossPredFn(torch.autograd.Function):
+    """_ComposeLossOptFn for v- / x0-prediction: the kernels take noise, y_0 and level and form the target themselves --
+    the same two launches forward and one backward, no target buffer."""
+
+    @staticmethod
+    def forward(ctx, out, noise, y_0, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, scale, pred):
+        _check(out, noise, y_0, level, bin_sum, scale)
+        S, Cout, H, W = out.shape
+        if level.numel() != B:
+            raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
+        if tuple(y_0.shape) != (B, 3, H, W) or tuple(noise.shape) != (B, 3, H, W):
+            raise ValueError(f"compose_loss needs noise and y_0 of shape {(B, 3, H, W)}, got {tuple(noise.shape)} and "
+                             f"{tuple(y_0.shape)}")
+        K = 0
+        if bin_sum is not None:
+            K = bin_sum.numel()
+            if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
+                raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
+        if scale is not None and scale.numel() != B:
+            raise ValueError(f"compose_loss needs one scale per sample: {scale.numel()} for a batch of {B}")
+        nh = torch.empty(B, 3, H, W, device=out.device, dtype=torch.float32)
+        nw = 1 if scale is None else 2           # partials | sample_loss | w (scale) | [w] | loss
+        buf = torch.empty(B * (65 + nw) + 1, device=out.device, dtype=torch.float32)
+        sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * (65 + nw):]
+        weight = sample_w if scale is None else buf[B * 66:B * 67]
+        _call("vf_compose_loss_pred_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(noise), _ptr(y_0), _ptr(level),
+              _ptr(scale), _ptr(nh), _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
+              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
+              delta, kind, a, b, K, pred, _stream())
+        ctx.save_for_backward(out, noise, y_0, level, nh, off, sample_w)
+        ctx.B, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred = B, int(weighting), penalty, delta, pred
+        ctx.mark_non_differentiable(sample_loss, weight)
+        return loss.reshape(()), sample_loss, weight
+
+    @staticmethod
+    def backward(ctx, gloss, _gsample, _gweight):
+        out, noise, y_0, level, nh, off, sample_w = ctx.saved_tensors
+        S, Cout, H, W = out.shape
+        gloss = _c(gloss.reshape(1).float())
+        dout = torch.empty_like(out)
+        _call("vf_compose_loss_pred_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(noise), _ptr(y_0), _ptr(level),
+              _ptr(nh), _ptr(gloss), _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty,
+              ctx.delta, ctx.pred, _stream())
+        return (dout,) + (None,) * 15
+
+
 def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delta=1.0, weight_kind=None, a=0.0, b=0.0,
-                 hist=None, sample_scale=None, want_weight=False):
+                 hist=None, sample_scale=None, want_weight=False, prediction="eps", y_0=None):
     """compose_mse_loss with options: -> (loss, sample_loss).  d = compose(unet_out) - target;
     penalty "mse" d^2 | "l1" |d| | "huber" (F.huber_loss with `delta`);  sample_loss[b] = mean_i rho(d_bi) (B,), detached;
     weight_kind None | "min_snr" (w = min(1, a (1 - g) / g)) | "p2" (w = (a + g / (1 - g))^-b) of g = level[b], the
@@ -418,14 +485,28 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
     sample_scale (device float32 (B,), default None: the launches above, untouched): a per-sample factor on w_b -- the
     importance weight of a non-uniform timestep draw (draw_level); loss = sum_b w_b scale_b sample_loss[b] / B through a
     sibling of the finish kernel, sample_loss and the histogram stay unweighted.
-    want_weight=True: -> (loss, sample_loss, w) with w (B,) the noise-level weight ALONE (what level_stats reads)."""
+    want_weight=True: -> (loss, sample_loss, w) with w (B,) the noise-level weight ALONE (what level_stats reads).
+    prediction "eps" (the default: everything above, launch for launch) | "v" | "x0" (csrc/diffusion.hip holds the
+    definition): `target` is then the NOISE and y_0 (B, 3, H, W) is required; d = compose(unet_out) - the prediction's
+    own target (v: sqrt(g) noise - sqrt(1 - g) y_0; x0: y_0), formed inside sibling kernels from noise, y_0 and level --
+    no target buffer, the same launch count -- and w the prediction's native weight (csrc/loss_weight.h)."""
     if penalty not in PENALTIES:
         raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
     if weight_kind not in WEIGHT_KINDS:
         raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2'")
+    check_prediction(prediction)
+    if prediction != "eps" and y_0 is None:
+        raise ValueError(f"prediction {prediction!r} forms its target from the noise and y_0: y_0= is required")
+    if prediction == "eps" and y_0 is not None:
+        raise ValueError("y_0= belongs to prediction 'v' / 'x0' (with 'eps' the target is handed over ready-made)")
     bin_sum, bin_cnt = hist if hist is not None else (None, None)
     if sample_scale is not None:
         sample_scale = _c(sample_scale.reshape(-1))
+    if prediction != "eps":
+        loss, sample_loss, weight = _ComposeLossPredFn.apply(
+            unet_out, _c(target), _c(y_0), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty], float(delta),
+            WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, sample_scale, PREDICTIONS[prediction])
+        return (loss, sample_loss, weight) if want_weight else (loss, sample_loss)
     loss, sample_loss, weight = _ComposeLossOptFn.apply(
         unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty], float(delta),
         WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, sample_scale)

@@ -12,7 +12,31 @@ BUFFER_NAMES = ("gammas", "sqrt_recip_gammas", "sqrt_recipm1_gammas", "posterior
                 "posterior_mean_coef1", "posterior_mean_coef2")
 
 
-def make_beta_schedule(schedule, num_timesteps, linear_start=1e-6, linear_end=1e-2, cosine_s=8e-3):
+PREDICTIONS = ("eps", "v", "x0")
+
+
+def rescale_zero_terminal_snr(betas):
+    """Lin et al., "Common Diffusion Noise Schedules and Sample Steps are Flawed", algorithm 1, in float64: sqrt(gammas)
+    is shifted and scaled so that its last value is exactly 0 and its first is unchanged -> betas (T,), the last one 1.
+    The last level is then pure noise, which is what sampling starts from.  An eps-model cannot use such a schedule
+    (g^-1/2 is infinite there); "v" and "x0" can (prediction_tables)."""
+    betas = np.asarray(betas, dtype=np.float64)
+    root = np.sqrt(np.cumprod(1.0 - betas, axis=0))
+    first, last = root[0], root[-1]
+    if not first > last:
+        raise ValueError("rescale_zero_terminal_snr needs a schedule whose signal level decreases")
+    root = (root - last) * (first / (first - last))
+    gam = root ** 2
+    alphas = np.append(gam[0], gam[1:] / gam[:-1])
+    alphas[-1] = 0.0                                   # (root[-1] - last is exactly 0 already; said once more)
+    return 1.0 - alphas
+
+
+def make_beta_schedule(schedule, num_timesteps, linear_start=1e-6, linear_end=1e-2, cosine_s=8e-3,
+                       zero_terminal_snr=False):
+    """zero_terminal_snr=True (default False: the schedule as before): rescale_zero_terminal_snr applied on top."""
+    if zero_terminal_snr:
+        return rescale_zero_terminal_snr(make_beta_schedule(schedule, num_timesteps, linear_start, linear_end, cosine_s))
     n = int(num_timesteps)
 
     def warm(frac):
@@ -49,6 +73,28 @@ def schedule_tensors(betas, device):
         vals = (gammas, np.sqrt(1.0 / gammas), np.sqrt(1.0 / gammas - 1), np.log(np.maximum(var, 1e-20)),
                 betas * np.sqrt(prev) / (1.0 - gammas), (1.0 - prev) * np.sqrt(alphas) / (1.0 - gammas))
     return {k: torch.tensor(v, dtype=torch.float32, device=device) for k, v in zip(BUFFER_NAMES, vals)}
+
+
+def check_prediction(prediction):
+    if prediction not in PREDICTIONS:
+        raise ValueError(f"unknown prediction {prediction!r}: one of {PREDICTIONS}")
+    return prediction
+
+
+def prediction_tables(betas, prediction="eps"):
+    """float64 betas (T,) -> (a, b), float64 (T,) each (rounded to fp32 once, by the caller): y0_hat = a[t] y - b[t] out
+    for a network whose output is the noise ("eps": g^-1/2, (1/g - 1)^1/2 -- schedule_tensors' own two formulas, so the
+    same fp32 values as the buffers), v = sqrt(g) noise - sqrt(1 - g) y_0 ("v": sqrt(g), sqrt(1 - g)) or y_0 itself
+    ("x0": 0, -1); csrc/diffusion.hip holds the definition.  With gamma = 0 (a zero-terminal-SNR schedule) the "eps" pair
+    is infinite there (no warning is raised here; sampling refuses it), the other two are finite."""
+    check_prediction(prediction)
+    gammas = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64), axis=0)
+    if prediction == "eps":
+        with np.errstate(divide="ignore"):
+            return np.sqrt(1.0 / gammas), np.sqrt(1.0 / gammas - 1)
+    if prediction == "v":
+        return np.sqrt(gammas), np.sqrt(1.0 - gammas)
+    return np.zeros_like(gammas), -np.ones_like(gammas)
 
 
 # ---- few-step sampling: a sub-sequence of the trained schedule and the tables of one linear-multistep tail ----------
@@ -92,8 +138,11 @@ def check_sampler(solver, eta):
         raise ValueError("dpmpp2m is deterministic: eta must be 0")
 
 
-def sampler_tables(betas, tau, solver="ddim", eta=0.0):
+def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps"):
     """float64 betas (T,), tau (K,) -> {a, b, cy, c0, c1, sigma}: float64 (K,) each (rounded to fp32 once, by the caller).
+    prediction: a, b = prediction_tables gathered at tau; cy, c0, c1, sigma do not depend on it.  Where a level of the
+    chain is 0 (zero terminal SNR) "eps" raises ValueError, and the other two give finite tables: the dpmpp2m step next
+    to lambda = -inf is first order (r = inf, c1 = 0).
 
     ddim     DDIM with eps re-derived from the clamped y0; eta = 1 on the full schedule is the ancestral sampler.
     dpmpp2m  DPM-Solver++ 2M in lambda = log(alpha / sigma); the first executed step (k = K-1, no history yet) and the
@@ -106,7 +155,11 @@ def sampler_tables(betas, tau, solver="ddim", eta=0.0):
     gt = gammas[tau]
     gp = np.append(1.0, gt[:-1])
     K = tau.shape[0]
-    out = {"a": np.sqrt(1.0 / gt), "b": np.sqrt(1.0 / gt - 1), "c1": np.zeros(K), "sigma": np.zeros(K)}
+    if check_prediction(prediction) == "eps" and (gt == 0).any():
+        raise ValueError("an eps-prediction model cannot sample from a level with gamma = 0 (zero terminal SNR): "
+                         "g^-1/2 is infinite there; use prediction 'v' or 'x0'")
+    pa, pb = prediction_tables(betas, prediction)
+    out = {"a": pa[tau], "b": pb[tau], "c1": np.zeros(K), "sigma": np.zeros(K)}
     if solver == "ddim":
         sig = float(eta) * np.sqrt((1.0 - gp) / (1.0 - gt)) * np.sqrt(1.0 - gt / gp)
         # d = sqrt(1 - gp - sig^2).  Written out, the difference loses every digit where gt << gp (a long stride at
@@ -122,7 +175,7 @@ def sampler_tables(betas, tau, solver="ddim", eta=0.0):
     g = -np.sqrt(gp) * np.expm1(-h)
     out.update(cy=np.sqrt((1.0 - gp) / (1.0 - gt)), c0=g.copy())
     for k in range(1, K - 1):
-        r = (lam[k] - lam[k + 1]) / h[k]
+        r = (lam[k] - lam[k + 1]) / h[k]                # +inf next to lambda = -inf (gamma = 0): a first-order step
         out["c0"][k] = g[k] * (1.0 + 1.0 / (2.0 * r))
-        out["c1"][k] = -g[k] / (2.0 * r)
+        out["c1"][k] = -g[k] / (2.0 * r) + 0.0          # (+ 0.0: no negative zero in the table)
     return out

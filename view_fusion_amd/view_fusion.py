@@ -35,6 +35,11 @@ standard deviation.  Both off by default; both defined at the head of csrc/diffu
 `set_level_sampler(...)` (default None: uniform timesteps, every launch as before) draws a training sample's timestep
 from a proposal over bins of timesteps -- a fixed one, or one that follows the loss's second moment per bin -- and
 multiplies the sample's loss by the importance weight that keeps the objective unbiased; see csrc/level_sampler.h.
+
+`set_prediction("eps" | "v" | "x0")` (default "eps": the launches and the bits of before) says what the network's first
+three channels mean: the noise, v = sqrt(g) noise - sqrt(1 - g) y_0, or y_0 itself.  Training forms the target inside
+the loss kernels; sampling hands every reverse-step tail the (a, b) pair of y0_hat = a y - b out that belongs to the
+prediction, so generate() and everything built on it need no new argument.  csrc/diffusion.hip holds the definition.
 """
 import torch
 from torch import nn
@@ -62,6 +67,9 @@ class ViewFusion(nn.Module):
         self._level_gen = 0
         self.level_sampler = None
         self.last_t = self.last_importance_weight = None
+        # what the network predicts (set_prediction): a plain attribute too; the (a, b) tables of v / x0, made on demand
+        self.prediction = "eps"
+        self._pred_tabs = None
 
     # -- training objective -------------------------------------------------------------------
     def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
@@ -144,13 +152,34 @@ class ViewFusion(nn.Module):
         self.level_sampler = ops.LevelSampler(kind, T, dev, **{k: v for k, v in self._level_spec.items() if k != "kind"}) \
             if dev.type == "cuda" else None
 
+    def set_prediction(self, prediction="eps"):
+        """What channels 0..2 of the network mean (csrc/diffusion.hip holds the definition; the weights: loss_weight.h).
+
+        "eps" (the default): the noise -- every launch and every bit as before.
+        "v": sqrt(g) noise - sqrt(1 - g) y_0, g the level the network is conditioned on.  "x0": y_0 itself.
+        Training: forward() takes the loss on the network's own target, formed inside the loss kernels from the noise and
+        y_0 it already holds (ops.compose_loss(prediction=): the same launch count, no target buffer); set_loss's
+        penalties apply to that residual, weighting=None is w = 1 on it, and "min_snr" / "p2" stay weights on the
+        eps-equivalent squared error (native weight w_eps(g) c(g), c = g for v and g / (1 - g) for x0).
+        Sampling: generate / p_sample / p_mean_variance, ancestral or few-step, guided, thresholded or not, run the same
+        tails with the prediction's table pair for y0_hat = a y - b out; guidance_rescale takes sigma of the composed
+        output in the network's own parameterisation.  On a zero-terminal-SNR schedule (beta_schedule
+        zero_terminal_snr=True) "v" and "x0" sample, "eps" raises ValueError.
+        A plain attribute: no buffer, no parameter, state_dict() unchanged -- save it as
+        save_checkpoint(..., prediction=model.prediction); load_checkpoint refuses a file that names another one.  A
+        Trainer drops its captured steps when it changes.  Not built: switching the parameterisation of trained weights."""
+        from .schedule import check_prediction
+        self.prediction = check_prediction(prediction)
+        self._pred_tabs = None
+        self._plan = None
+
     def loss_key(self):
         """What a captured training step depends on besides its inputs: the objective, the attached histogram, the
-        conditioning-dropout probability and the level sampler (every set_level_sampler call counts)."""
+        conditioning-dropout probability, the level sampler (every set_level_sampler call counts) and the prediction."""
         h = self.loss_hist
         return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
                 None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p,
-                self._level_gen)
+                self._level_gen, self.prediction)
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -158,6 +187,7 @@ class ViewFusion(nn.Module):
         self.num_timesteps = int(betas.shape[0])
         self.betas64 = betas                   # float64, for the few-step sampler tables; not a buffer (state_dict)
         self._plan = None
+        self._pred_tabs = None
         for name, val in _schedule.schedule_tensors(betas, device).items():
             if name in self._buffers:
                 self._buffers[name] = val
@@ -165,15 +195,32 @@ class ViewFusion(nn.Module):
                 self.register_buffer(name, val)
 
     def _sched(self):
-        return {k: getattr(self, k) for k in _schedule.BUFFER_NAMES}
+        """The tables the ancestral tail reads.  "eps": the very buffers.  "v" / "x0": the same posterior buffers, and the
+        prediction's (a, b) pair under the two names the tail reads y0_hat's coefficients from."""
+        sched = {k: getattr(self, k) for k in _schedule.BUFFER_NAMES}
+        if self.prediction == "eps":
+            return sched
+        dev = self.gammas.device
+        if self._pred_tabs is None or self._pred_tabs[0] != (self.prediction, dev):
+            a, b = _schedule.prediction_tables(self.betas64, self.prediction)
+            self._pred_tabs = ((self.prediction, dev), torch.tensor(a, dtype=torch.float32, device=dev),
+                               torch.tensor(b, dtype=torch.float32, device=dev))
+        sched["sqrt_recip_gammas"], sched["sqrt_recipm1_gammas"] = self._pred_tabs[1], self._pred_tabs[2]
+        return sched
+
+    def _check_samplable(self):
+        """ValueError, before any launch, where y0_hat cannot be formed: "eps" at a level with gamma = 0."""
+        if self.prediction == "eps" and float(self.betas64[-1]) >= 1.0:
+            raise ValueError("an eps-prediction model cannot sample on a zero-terminal-SNR schedule (gamma_T = 0: g^-1/2 "
+                             "is infinite there); use set_prediction('v') or 'x0'")
 
     def _sampler_plan(self, tau, solver, eta, device):
         """The device side of a few-step chain: the fp32 tables of schedule.sampler_tables, `tau` as int64 and
         `level` = the fp32 `gammas` buffer gathered at tau (the network sees the very levels of the full chain).
         `noisy[k]`: sigma[k] != 0, on the host.  The last plan is kept (evaluate() asks for the same one per batch)."""
-        key = (tuple(int(v) for v in tau), solver, float(eta), device)
+        key = (tuple(int(v) for v in tau), solver, float(eta), device, self.prediction)
         if self._plan is None or self._plan[0] != key:
-            tab = _schedule.sampler_tables(self.betas64, tau, solver, eta)
+            tab = _schedule.sampler_tables(self.betas64, tau, solver, eta, self.prediction)
             host = {k: torch.tensor(v, dtype=torch.float32) for k, v in tab.items()}
             plan = {k: v.to(device) for k, v in host.items()}
             plan["tau"] = torch.tensor(tau, dtype=torch.int64, device=device)
@@ -190,6 +237,11 @@ class ViewFusion(nn.Module):
     # -- small API-compat helpers (not on the fused hot path) ---------------------------------
     def predict_start_from_noise(self, y_t, t, noise):
         return self._at(self.sqrt_recip_gammas, t) * y_t - self._at(self.sqrt_recipm1_gammas, t) * noise
+
+    def predict_start(self, y_t, t, out):
+        """y0_hat = a[t] y_t - b[t] out for the model's own prediction (predict_start_from_noise under "eps")."""
+        sched = self._sched()
+        return self._at(sched["sqrt_recip_gammas"], t) * y_t - self._at(sched["sqrt_recipm1_gammas"], t) * out
 
     def q_posterior(self, y_0_hat, y_t, t):
         mean = self._at(self.posterior_mean_coef1, t) * y_0_hat + self._at(self.posterior_mean_coef2, t) * y_t
@@ -214,6 +266,7 @@ class ViewFusion(nn.Module):
         threshold / threshold_max / guidance_rescale: as in generate()."""
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
+        self._check_samplable()
         dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
@@ -229,6 +282,7 @@ class ViewFusion(nn.Module):
                  threshold_max=None, guidance_rescale=None):
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
+        self._check_samplable()
         dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
@@ -283,6 +337,7 @@ class ViewFusion(nn.Module):
         q_on, _, phi = ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None)
         dyn = {}
         plan = tau = None
+        self._check_samplable()
         if sample_steps is not None:                      # argument errors first: nothing has been launched yet
             _schedule.check_sampler(solver, eta)
             tau = _schedule.sample_timesteps(self.num_timesteps, sample_steps).tolist()
@@ -436,11 +491,13 @@ class ViewFusion(nn.Module):
                                               drop=drop)
         out = self.denoise_fn(x, angle_s, level_s)
         self.last_t, self.last_importance_weight = (None, None) if smp is None else (t, iw)
-        if self._loss is None and self.loss_hist is None and smp is None:
+        if self._loss is None and self.loss_hist is None and smp is None and self.prediction == "eps":
             return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
+        # "v" / "x0": the loss kernels form the target themselves, from the noise and y_0
+        pred = {} if self.prediction == "eps" else dict(prediction=self.prediction, y_0=y_0)
         loss, sample_loss, weight = ops.compose_loss(out, noise, off, b, bool(self.weighting_train), level,
                                                      **(self._loss or {}), hist=self.loss_hist, sample_scale=iw,
-                                                     want_weight=True)
+                                                     want_weight=True, **pred)
         self.last_sample_loss, self.last_level = sample_loss.detach(), level.detach()
         if smp is not None and smp.kind == "loss_aware" and self.training:
             ops.level_stats(smp, self.last_sample_loss, weight.detach(), t)
