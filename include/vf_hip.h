@@ -272,7 +272,7 @@ int vf_compose_mse_bwd(const float* unet_out, const int* off, const float* targe
                        const float* gloss, float* dout, int B, int Cout, int HW, int weighting, void* stream);
 /* Loss options (csrc/loss_weight.h holds the specification): the two calls above with a target, generalised.
  * penalty 0 mse | 1 l1 | 2 huber(delta > 0) of d = noise_hat - target;  weight_kind 0 none | 1 min_snr(a) | 2 p2(k = a,
- * p = b) of level[b] (DEVICE float [B], the sample's gamma).  Writes noise_hat, sample_loss[b] = mean_i rho(d_bi),
+ * p = b) | 3 trunc_snr of level[b] (DEVICE float [B], the sample's gamma).  Writes noise_hat, sample_loss[b] = mean_i rho(d_bi),
  * sample_w[b] and loss = sum_b w_b s_b / B; bin_sum (float [K]) / bin_cnt (int [K]) (both or neither): persistent
  * accumulators, bin min(K-1, (int)(level K)) += the UNWEIGHTED s_b / 1.  Two launches, no atomics. */
 int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* target, const float* level,
@@ -457,7 +457,27 @@ int vf_sampler_step_eps_rng(const float* eps, const float* stat, const float* y_
                             const long long* ids, const long long* kidx, const long long* tau, const float* a,
                             const float* b, const float* cy, const float* c0, const float* c1, const float* sigma,
                             float* y0_prev /*|NULL*/, float* y_next, int B, int HW, int rescale, int thr, void* stream);
+/* ---- progressive distillation (csrc/diffusion.hip holds the definition): the target of a student that does in one
+ *      DDIM step what its teacher does in two.  Two launches around the teacher's two forwards; the first teacher step is
+ *      vf_sampler_step(_cfg) with a history buffer. ---- */
+/* i[b] = i_in[b] clamped to 0..K-1, or mulhi32(word 0 of the kind-0 call of ids[b], K) (exactly one of i_in / ids);
+ * k1 = 2 i + 1, k0 = 2 i (int64 [B] each); level_s[b] = gammas[tau_s[i]]; z_t = sqrt(level_s) y_0 + sqrt(1 - level_s) noise
+ * ([B][n], n % 4 == 0).  tau_s: DEVICE int64 [K], 1 <= K <= 2^27. */
+int vf_distill_begin(unsigned long long seed, const long long* ids /*|NULL*/, const long long* i_in /*|NULL*/,
+                     const long long* tau_s, const float* gammas, int K, const float* y_0, const float* noise,
+                     long long* i_out, long long* k1, long long* k0, float* level_s, float* z_t, int B, int n,
+                     void* stream);
+/* The second teacher step's tail: x2 = clamp(a[k0] y - b[k0] out2, -1, 1) with out2 composed (g != NULL: and guided,
+ * unet_out [off[B] + B][Cout][HW]) from unet_out; x_tilde = clamp(w1[i] x1 + w2[i] x2, -1, 1);
+ * eps_tilde = (z_t - sqrt(level_s) x_tilde) / sqrt(1 - level_s).  y = z', x1 = the history buffer of the first step. */
+int vf_distill_target(const float* unet_out, const int* off, const float* y, const float* x1, const float* z_t,
+                      const float* level_s, const long long* idx, const long long* kidx, const float* a, const float* b,
+                      const float* w1, const float* w2, float* x_tilde, float* eps_tilde, int B, int Cout, int HW,
+                      int weighting, const float* g /*[B]|NULL*/, void* stream);
 /* Host mirrors: the same inline functions run on the CPU.  HOST pointers, no stream, no GPU needed. */
+int vf_distill_step_host(unsigned long long seed, const long long* ids, int K, long long* i_out /*[B]*/, int B);
+/* the truncated-SNR weight max(SNR, 1) / SNR in its native form for pred 0 eps | 1 v | 2 x0 (csrc/loss_weight.h, kind 3) */
+int vf_loss_weights_trunc_snr_host(const float* level, int B, int pred, float* out /*[B]*/);
 int vf_rng_host_philox(const unsigned* counter /*[4]*/, const unsigned* key /*[2]*/, unsigned* out /*[4]*/);
 int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, int step, float* out /*[B][n]*/,
                        int B, int n);

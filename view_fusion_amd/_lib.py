@@ -164,6 +164,10 @@ SIGNATURES = {
     "vf_p_sample_tail_eps_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vf_sampler_step_eps": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "vf_sampler_step_eps_rng": [_P, _P, _P, _U64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vf_distill_begin": [_U64, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "vf_distill_target": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
+    "vf_distill_step_host": [_U64, _P, _I, _P, _I],
+    "vf_loss_weights_trunc_snr_host": [_P, _I, _I, _P],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

@@ -35,6 +35,8 @@
 //   prediction      pred_target4, compose_loss_pred_fwd / _finish_pred / _pred_bwd<PEN, PRED>: the loss-option kernels for
 //                   v- and x0-prediction, the target formed in registers from noise, y_0 and level (same launch count).
 //                   The tails have no sibling: another parameterisation is another (a, b) table pair.
+//   distillation    distill_begin_kernel (the draw of i, z_t) and distill_target_kernel<CFG> (the second teacher step's tail:
+//                   x2, x~, eps~), siblings of draw_train / stack_views and of sampler_step_kernel.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
 //                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.
@@ -101,6 +103,33 @@
 //   threshold acts on y0_hat.  Everything after y0_hat (posterior, multistep update, threshold, y0_prev) uses y0 alone:
 //   sampling in another parameterisation hands the tails another (a, b) table pair, and no tail kernel changes.
 //   With gamma_T = 0 (a zero-terminal-SNR schedule) the "eps" pair is infinite there; the "v" and "x0" pairs are finite.
+//
+// Progressive distillation (Salimans & Ho, "Progressive Distillation for Fast Sampling of Diffusion Models"): the target
+// of a student that does in one deterministic DDIM step what its teacher does in two.  This comment is the ONE written
+// definition; tests/distill_ref.py restates it.  Opt-in: two sibling kernels, everything above is untouched.
+//   Grids.  K >= 1 student steps with 2K <= T: tau_S = sample_timesteps(T, K), tau_T = sample_timesteps(T, 2K), so that
+//     tau_T[2i+1] == tau_S[i], and step 0 of both lands on the clean image.
+//   Tables.  Teacher: sampler_tables(betas, tau_T, "ddim", 0, teacher.prediction) -> a_T, b_T, cy_T, c0_T.  Student:
+//     sampler_tables(betas, tau_S, "ddim", 0) -> cy_S, c0_S.  w1[i] = cy_T[2i] c0_T[2i+1] / c0_S[i], w2[i] = 1 - w1[i],
+//     formed in float64 on the host and rounded to fp32 once (schedule.distill_tables); 0 <= w1 <= 1 and w1[0] = 0.
+//   For sample b with student step i = i_b in 0..K-1:
+//   1. g = gammas[tau_S[i]] (the fp32 buffer value: the level the student's own K-step sampler conditions it on);
+//      z_t = sqrt(g) y_0 + sqrt(1 - g) noise, stack_views_kernel's expression.                       [distill_begin_kernel]
+//   2. Teacher step k1 = 2i + 1 at level gammas[tau_T[k1]], the existing sampler_step with a history buffer:
+//      x1 = clamp(a_T[k1] z_t - b_T[k1] out1, -1, 1) -> the history buffer;  z' = cy_T[k1] z_t + c0_T[k1] x1.
+//      out1: the composition of the teacher's output over the sample's views, guided by its null row when guidance is set.
+//   3. Teacher step k0 = 2i on the teacher's output at z', level gammas[tau_T[k0]]:
+//      x2 = clamp(a_T[k0] z' - b_T[k0] out2, -1, 1), rounded as sampler_step_kernel rounds y0.     [distill_target_kernel]
+//   4. x~ = clamp(fma(w1[i], x1, w2[i] x2), -1, 1): a convex combination of two clamped predictions -- the clamp only takes
+//      back a last place by which fp32 w1 + w2 may exceed 1; with i = 0 (w1 = 0, w2 = 1) x~ is x2 bit for bit.  This is the
+//      paper's x~ = (z'' - (sigma''/sigma) z_t) / (alpha'' - (sigma''/sigma) alpha_t) without its cancellation: cy_S =
+//      cy_T[2i] cy_T[2i+1] and cy_T[2i] c0_T[2i+1] + c0_T[2i] = c0_S[i], so cy_S z_t + c0_S x~ is the teacher's z''.
+//   5. eps~ = (z_t - sqrt(g) x~) / sqrt(1 - g), every operation rounded, in this order.
+//   6. The student sees z_t and g bit for bit; its loss is the existing objective with noise := eps~ and y_0 := x~ (the loss
+//      kernels then form its native target themselves: eps~, sqrt(g) eps~ - sqrt(1 - g) x~, or x~).
+//   The draw of i (seeded): i_b = mulhi32(w0, K), w0 = word 0 of the sample's kind-0 call (where t comes from otherwise);
+//   an injected i is clamped to 0..K-1 before any table is read.  i, k1, k0 (int64), g, tables and weights live in device
+//   memory: a captured phase replays for every step.  No EPS / threshold / rescale flavour.
 #include "common.h"
 #include "level_sampler.h"
 #include "loss_weight.h"
@@ -1398,6 +1427,89 @@ void launch_pred_bwd(dim3 grid, hipStream_t st, int penalty, const float* out, c
                            level, noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
 }
 
+// ---- progressive distillation (the head of this file) ----
+// The student step of sample b, its two teacher steps and its level, and z_t.  grid (chunks, B); i_in (int64 [B] | null):
+// an injected i, clamped to 0..K-1; else i = mulhi32(word 0 of the training-scalars call, K).  z_t is stack_views_kernel's
+// q_sample expression, so the student's stacked target half -- a copy of this buffer -- carries these bits.
+__global__ __launch_bounds__(256) void distill_begin_kernel(unsigned long long seed, const long long* __restrict__ ids,
+                                                            const long long* __restrict__ i_in,
+                                                            const long long* __restrict__ tau_s,
+                                                            const float* __restrict__ gammas, int K,
+                                                            const float4* __restrict__ y_0,
+                                                            const float4* __restrict__ noise, long long* __restrict__ i_out,
+                                                            long long* __restrict__ k1, long long* __restrict__ k0,
+                                                            float* __restrict__ level_s, float4* __restrict__ z_t, int n4) {
+    const int b = blockIdx.y;
+    long long i;
+    if (i_in != nullptr) {
+        i = i_in[b];
+        i = i < 0 ? 0 : (i > K - 1 ? K - 1 : i);
+    } else {
+        uint32_t w[4];
+        vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+        i = vf_rng_distill_step(w[0], K);
+    }
+    const float lv = gammas[tau_s[i]];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        i_out[b] = i;
+        k1[b] = 2 * i + 1;
+        k0[b] = 2 * i;
+        level_s[b] = lv;
+    }
+    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    const float4* t = y_0 + (size_t)b * n4;
+    const float4* z = noise + (size_t)b * n4;
+    float4* o = z_t + (size_t)b * n4;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n4; j += gridDim.x * 256) {
+        float4 y = t[j];
+        const float4 e = z[j];
+        y.x = sa * y.x + sb * e.x;
+        y.y = sa * y.y + sb * e.y;
+        y.z = sa * y.z + sb * e.z;
+        y.w = sa * y.w + sb * e.w;
+        o[j] = y;
+    }
+}
+
+// The second teacher step's tail (steps 3 - 5 of the definition): out2 composed (+ guided) with the tails' own prologue,
+// x2 as sampler_step_kernel forms y0 (both products rounded, then subtracted: y0_hat_as<false>), then x~ and eps~ in
+// pinned arithmetic.  y = z' (the first step's y_next), x1 = the history buffer that step wrote.  One read of each
+// input, one write of each output; grid (chunks, B); no atomics.
+template <bool CFG>
+__global__ __launch_bounds__(256) void distill_target_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y, const float* __restrict__ x1,
+    const float* __restrict__ z_t, const float* __restrict__ level_s, const long long* __restrict__ idx,
+    const long long* __restrict__ kidx, const float* __restrict__ ta, const float* __restrict__ tb,
+    const float* __restrict__ tw1, const float* __restrict__ tw2, float* __restrict__ x_tilde,
+    float* __restrict__ eps_tilde, int Cout, int HW, int weighting, const float* __restrict__ gscale) {
+    const int b = blockIdx.y;
+    const TailSample s = tail_sample<CFG, false>(out, off, gscale, EpsBuffer{}, Cout, HW);
+    const int n4 = 3 * HW / 4;
+    const long long i = idx[b], k = kidx[b];
+    const float a_k = ta[k], b_k = tb[k], w1 = tw1[i], w2 = tw2[i];
+    const float lv = level_s[b];
+    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < n4; j += gridDim.x * 256) {
+        const int c = (4 * j) / HW, p = 4 * j - c * HW;
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)j;
+        const float4 eps = tail_eps<CFG, false>(s, out, EpsBuffer{}, Cout, HW, weighting, c, p, o, nullptr, nullptr);
+        const float4 yy = *reinterpret_cast<const float4*>(y + o);
+        const float4 h = *reinterpret_cast<const float4*>(x1 + o);
+        const float4 zt = *reinterpret_cast<const float4*>(z_t + o);
+        const float ys[4] = {yy.x, yy.y, yy.z, yy.w}, es[4] = {eps.x, eps.y, eps.z, eps.w};
+        const float hs[4] = {h.x, h.y, h.z, h.w}, zs[4] = {zt.x, zt.y, zt.z, zt.w};
+        float xt[4], et[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float x2 = fminf(fmaxf(y0_hat_as<false>(a_k, ys[q], b_k, es[q]), -1.0f), 1.0f);
+            xt[q] = fminf(fmaxf(__builtin_fmaf(w1, hs[q], mul_rn(w2, x2)), -1.0f), 1.0f);
+            et[q] = add_rn(zs[q], -mul_rn(sa, xt[q])) / sb;
+        }
+        *reinterpret_cast<float4*>(x_tilde + o) = make_float4(xt[0], xt[1], xt[2], xt[3]);
+        *reinterpret_cast<float4*>(eps_tilde + o) = make_float4(et[0], et[1], et[2], et[3]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1469,7 +1581,7 @@ int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* targ
                         int weight_kind, float a, float b, int K, void* stream) {
     if (B <= 0) return 0;
     if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
     if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
     if (!target || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
         return (int)hipErrorInvalidValue;
@@ -1523,7 +1635,7 @@ int vf_compose_loss_fwd_scaled(const float* unet_out, const int* off, const floa
                                    bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream);
     if (B <= 0) return 0;
     if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
     if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
     if (!target || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
         return (int)hipErrorInvalidValue;
@@ -1616,7 +1728,7 @@ int vf_compose_loss_pred_fwd(const float* unet_out, const int* off, const float*
                              int K, int pred, void* stream) {
     if (B <= 0) return 0;
     if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
     if (pred != VF_PRED_V && pred != VF_PRED_X0) return (int)hipErrorInvalidValue;
     if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
     if (!y_0 || (pred == VF_PRED_V && !noise) || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
@@ -1925,6 +2037,61 @@ int vf_cond_drop_host(unsigned long long seed, const long long* ids, unsigned th
         vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
         drop[b] = (unsigned char)vf_rng_cond_drop(w[2], thr);
     }
+    return 0;
+}
+
+// ---- progressive distillation (the head of this file) ----
+// i / k1 / k0: DEVICE int64 [B]; level_s [B]; z_t [B][n]; tau_s: DEVICE int64 [K]; exactly one source of i: i_in (DEVICE
+// int64 [B], clamped to 0..K-1) or ids (with seed).  n = 3 HW, n % 4 == 0.
+int vf_distill_begin(unsigned long long seed, const long long* ids, const long long* i_in, const long long* tau_s,
+                     const float* gammas, int K, const float* y_0, const float* noise, long long* i_out, long long* k1,
+                     long long* k0, float* level_s, float* z_t, int B, int n, void* stream) {
+    if (B <= 0) return 0;
+    if (K < 1 || K > (1 << 27) || n <= 0 || (n & 3) || B > 65535) return (int)hipErrorInvalidValue;
+    if ((ids == nullptr) == (i_in == nullptr)) return (int)hipErrorInvalidValue;
+    if (!tau_s || !gammas || !y_0 || !noise || !i_out || !k1 || !k0 || !level_s || !z_t) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(distill_begin_kernel, dim3(chunks_for(n / 4), B), dim3(256), 0, (hipStream_t)stream, seed, ids, i_in,
+                       tau_s, gammas, K, (const float4*)y_0, (const float4*)noise, i_out, k1, k0, level_s, (float4*)z_t,
+                       n / 4);
+    VF_RETURN_LAST_ERROR();
+}
+
+// unet_out [off[B] (+ B with g)][Cout][HW]: the teacher's output at y = z'.  idx = i, kidx = k0: DEVICE int64 [B];
+// a / b: the teacher's 2K-entry tables, w1 / w2: the K-entry weights; g (DEVICE fp32 [B] | NULL): guidance scales.
+int vf_distill_target(const float* unet_out, const int* off, const float* y, const float* x1, const float* z_t,
+                      const float* level_s, const long long* idx, const long long* kidx, const float* a, const float* b,
+                      const float* w1, const float* w2, float* x_tilde, float* eps_tilde, int B, int Cout, int HW,
+                      int weighting, const float* g, void* stream) {
+    if (B <= 0) return 0;
+    if (HW <= 0 || (HW & 3) || Cout < 3 || (weighting && Cout < 6) || B > 65535) return (int)hipErrorInvalidValue;
+    if (!unet_out || !off || !y || !x1 || !z_t || !level_s || !idx || !kidx || !a || !b || !w1 || !w2 || !x_tilde ||
+        !eps_tilde)
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(chunks_for(3 * HW / 4), B);
+    if (g)
+        hipLaunchKernelGGL(distill_target_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, unet_out, off, y, x1, z_t,
+                           level_s, idx, kidx, a, b, w1, w2, x_tilde, eps_tilde, Cout, HW, weighting, g);
+    else
+        hipLaunchKernelGGL(distill_target_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, unet_out, off, y, x1, z_t,
+                           level_s, idx, kidx, a, b, w1, w2, x_tilde, eps_tilde, Cout, HW, weighting, g);
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirrors.  The seeded draw of i on the CPU: i[b] = mulhi32(word 0, K) for the ids (HOST int64 [B]) ...
+int vf_distill_step_host(unsigned long long seed, const long long* ids, int K, long long* i_out, int B) {
+    if (B < 0 || K < 1 || K > (1 << 27)) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b) {
+        uint32_t w[4];
+        vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+        i_out[b] = vf_rng_distill_step(w[0], K);
+    }
+    return 0;
+}
+
+// ... and vf_loss_weight_pred of the truncated-SNR kind (pred 0 | 1 | 2), which the two mirrors above do not take.
+int vf_loss_weights_trunc_snr_host(const float* level, int B, int pred, float* out) {
+    if (B < 0 || pred < VF_PRED_EPS || pred > VF_PRED_X0) return (int)hipErrorInvalidValue;
+    for (int s = 0; s < B; ++s) out[s] = vf_loss_weight_pred(pred, VF_LOSS_W_TRUNC_SNR, 0.0f, 0.0f, level[s]);
     return 0;
 }
 

@@ -19,6 +19,7 @@
 //
 // One Philox call gives four 32-bit words w0..w3.
 //   t = 1 + mulhi32(w0, T - 1)          in [1, T - 1] = the reference's randint(1, T); exact integer arithmetic
+//   i = mulhi32(w0, K)                  in [0, K): the student step of a distillation sample (diffusion.hip), in place of t
 //   u = (w1 >> 8) * 2^-24               in [0, 1) as torch.rand; exact in fp32
 //   drop = (w2 >> 8) < thr              conditioning dropout (classifier-free guidance, diffusion.hip): thr = ceil(p * 2^24)
 //                                       from the host, an integer compare like the view store's 10 % draw below, so no
@@ -99,6 +100,9 @@ VF_RNG_HD void vf_rng_words(uint64_t seed, uint64_t id, uint32_t kind, uint32_t 
 VF_RNG_HD long long vf_rng_timestep(uint32_t w0, int T) {
     return 1 + (long long)(((uint64_t)w0 * (uint32_t)(T - 1)) >> 32);
 }
+
+// the student step of progressive distillation (diffusion.hip): mulhi32(w0, K) in [0, K), from the word that gives t otherwise
+VF_RNG_HD long long vf_rng_distill_step(uint32_t w0, int K) { return (long long)(((uint64_t)w0 * (uint32_t)K) >> 32); }
 
 VF_RNG_HD float vf_rng_uniform24(uint32_t w1) { return (float)(w1 >> 8) * 5.9604644775390625e-8f; }   // 2^-24
 

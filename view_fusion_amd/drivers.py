@@ -120,10 +120,19 @@ def orbit_frames(model, all_views, n=24, **inject):
 
 
 # ---- checkpoint wire format --------------------------------------------------------------------
+def _check_distill_extra(d):
+    k = d.get("steps") if isinstance(d, dict) else None
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"the checkpoint's distill entry must be dict(steps=K) with an integer K >= 1, got {d!r}")
+
+
 def save_checkpoint(path, model, optimizer, **extra):
     """{"model": state_dict, "optimizer": state_dict, + extra (it, t, run_id, ssim, psnr)} -- the
-    reference's file layout, so either side can load the other's checkpoints."""
+    reference's file layout, so either side can load the other's checkpoints.  distill=dict(steps=K) records the stage of
+    a progressive distillation (load_checkpoint); the teacher's weights are not part of the file."""
     out = dict(extra)
+    if out.get("distill") is not None:
+        _check_distill_extra(out["distill"])
     out["model"] = model.state_dict()
     out["optimizer"] = optimizer.state_dict()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -137,8 +146,13 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     (save_checkpoint(..., level_sampler=model.level_sampler.state_dict())) is restored into a model that has had the same
     set_level_sampler(...) call: the statistics and the proposal table continue where they were.  A "prediction" entry
     (save_checkpoint(..., prediction=model.prediction)) must name the model's own prediction: ValueError otherwise,
-    before anything is loaded.  Files without the entry load as before."""
+    before anything is loaded.  A "distill" entry (save_checkpoint(..., distill=dict(steps=K)): the stage of a progressive
+    distillation the weights were saved in -- the model samples in K steps, and its next stage is K / 2 with these weights
+    as the teacher) is a plain dict with an integer steps >= 1, checked (ValueError otherwise) and returned with the other
+    extras: the caller builds the teacher and calls set_distill.  Files without the entry load as before."""
     sd = torch.load(path, map_location=device, weights_only=False)
+    if sd.get("distill") is not None:
+        _check_distill_extra(sd["distill"])
     mine = getattr(model, "prediction", "eps")
     if sd.get("prediction") is not None and sd["prediction"] != mine:
         raise ValueError(f"the checkpoint was trained with prediction {sd['prediction']!r}, the model is set to {mine!r} "
@@ -151,6 +165,48 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     if sd.get("level_sampler") and getattr(model, "level_sampler", None) is not None:
         model.level_sampler.load_state_dict(sd["level_sampler"])
     return {k: v for k, v in sd.items() if k not in ("model", "optimizer")}
+
+
+# ---- progressive distillation -----------------------------------------------------------------
+def progressive_distill(trainer, teacher, batches, start_steps, end_steps, iters_per_stage, guidance=None,
+                        from_ema=False):
+    """Salimans & Ho's outer loop around ViewFusion.set_distill (csrc/diffusion.hip holds the definition): for
+    K = start_steps / 2, start_steps / 4, ..., end_steps the trainer's model is trained for `iters_per_stage` steps as a
+    K-step student of the 2K-step `teacher`, then its parameters are copied INTO the teacher (copy_: no tensor is
+    replaced, so packed-weight caches refresh and nothing is reallocated) -- the student's EMA instead when the trainer
+    keeps one and from_ema=True -- and K halves.  guidance applies to the first stage only: from the second stage on the
+    teacher is a distilled student, which needs no null row.  batches: an iterator of trainer.step() batches (at least
+    stages x iters_per_stage of them).  start_steps = end_steps 2^m with m >= 1 and start_steps <= T, else ValueError.
+    -> [(K, mean loss of the stage as a 0-d device tensor)]; no host sync.  Distillation stays set (at the last K) on
+    return: model.set_distill(None) goes back to the plain objective."""
+    model = trainer.module
+    for name, v in (("start_steps", start_steps), ("end_steps", end_steps), ("iters_per_stage", iters_per_stage)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be a positive integer, got {v!r}")
+    ratio = start_steps // end_steps
+    if start_steps % end_steps or ratio < 2 or ratio & (ratio - 1):
+        raise ValueError(f"start_steps must be end_steps times a power of two (at least 2): got {start_steps} and {end_steps}")
+    if start_steps > model.num_timesteps:
+        raise ValueError(f"start_steps must be at most T = {model.num_timesteps}, got {start_steps}")
+    if from_ema and getattr(trainer.opt, "ema_decay", None) is None:
+        raise ValueError("from_ema=True needs a Trainer that keeps a weight EMA (ema_decay=...)")
+    batches = iter(batches)
+    student = dict(model.named_parameters())
+    out, K = [], start_steps // 2
+    while K >= end_steps:
+        model.set_distill(teacher, steps=K, guidance=guidance)
+        total = None
+        for _ in range(iters_per_stage):
+            loss = trainer.step(next(batches))
+            total = loss if total is None else total + loss
+        out.append((K, total / iters_per_stage))
+        with torch.no_grad():
+            for name, p in teacher.named_parameters():
+                src = student[name]
+                p.copy_(trainer.opt._ema_of(src) if from_ema else src)
+        guidance = None
+        K //= 2
+    return out
 
 
 # ---- eval reduction -----------------------------------------------------------------------------

@@ -78,6 +78,7 @@ _CALL_KIND = {"vf_wino44_pack_weights": "pack", "vf_wino44_pack_weights_multi": 
               "vf_compose_eps": "diffusion", "vf_sample_stat": "diffusion", "vf_abs_quantile": "diffusion",
               "vf_p_sample_tail_eps": "diffusion", "vf_p_sample_tail_eps_rng": "diffusion",
               "vf_sampler_step_eps": "diffusion", "vf_sampler_step_eps_rng": "diffusion",
+              "vf_distill_begin": "diffusion", "vf_distill_target": "diffusion",
               "vf_grad_sumsq_multi": "adam", "vf_grad_norm_finish": "adam", "vf_adam_multi_ex": "adam",
               "vf_adam_multi_ex_dev": "adam", "vf_adam_set_scalars_ex": "adam", "vf_swap_multi": "adam", "vf_grad_accum_multi": "adam"}
 

@@ -356,7 +356,7 @@ def compose_mse_loss(unet_out, target_noise, off, B, weighting):
 
 # ---- loss options (csrc/loss_weight.h): penalty x noise-level weight, per-sample loss, loss-by-level histogram ----
 PENALTIES = {"mse": 0, "l1": 1, "huber": 2}
-WEIGHT_KINDS = {None: 0, "none": 0, "min_snr": 1, "p2": 2}
+WEIGHT_KINDS = {None: 0, "none": 0, "min_snr": 1, "p2": 2, "trunc_snr": 3}
 
 
 class _ComposeLossOptFn(torch.autograd.Function):
@@ -417,9 +417,15 @@ def loss_weights_pred_host(level, prediction="eps", weight_kind=None, a=0.0, b=0
     CPU tensor of the same length.  No GPU."""
     check_prediction(prediction)
     if weight_kind not in WEIGHT_KINDS:
-        raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2'")
+        raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2', 'trunc_snr'")
     lv = torch.as_tensor(level, dtype=torch.float32).detach().cpu().reshape(-1).contiguous()
     out = torch.empty_like(lv)
+    if weight_kind == "trunc_snr":             # a mirror of its own: the two older ones keep refusing codes above p2
+        rc = _lib.load().vf_loss_weights_trunc_snr_host(ctypes.c_void_p(lv.data_ptr()), lv.numel(),
+                                                        PREDICTIONS[prediction], ctypes.c_void_p(out.data_ptr()))
+        if rc != 0:
+            raise _lib.VFHipError(f"vf_loss_weights_trunc_snr_host failed with {rc}")
+        return out
     rc = _lib.load().vf_loss_weights_pred_host(ctypes.c_void_p(lv.data_ptr()), lv.numel(), PREDICTIONS[prediction],
                                                WEIGHT_KINDS[weight_kind], float(a), float(b),
                                                ctypes.c_void_p(out.data_ptr()))
@@ -478,8 +484,8 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
                  hist=None, sample_scale=None, want_weight=False, prediction="eps", y_0=None):
     """compose_mse_loss with options: -> (loss, sample_loss).  d = compose(unet_out) - target;
     penalty "mse" d^2 | "l1" |d| | "huber" (F.huber_loss with `delta`);  sample_loss[b] = mean_i rho(d_bi) (B,), detached;
-    weight_kind None | "min_snr" (w = min(1, a (1 - g) / g)) | "p2" (w = (a + g / (1 - g))^-b) of g = level[b], the
-    sample's gamma (device float32 (B,));  loss = sum_b w_b sample_loss[b] / B, differentiable in unet_out.
+    weight_kind None | "min_snr" (w = min(1, a (1 - g) / g)) | "p2" (w = (a + g / (1 - g))^-b) | "trunc_snr"
+    (w = max(1, (1 - g) / g)) of g = level[b], the sample's gamma (device float32 (B,));  loss = sum_b w_b sample_loss[b] / B, differentiable in unet_out.
     hist = (bin_sum float32 [K], bin_cnt int32 [K]) device accumulators: bin min(K - 1, int(g K)) receives the
     UNWEIGHTED sample_loss[b] and a count; they persist across calls (the caller zeroes them).
     sample_scale (device float32 (B,), default None: the launches above, untouched): a per-sample factor on w_b -- the
@@ -493,7 +499,7 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
     if penalty not in PENALTIES:
         raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
     if weight_kind not in WEIGHT_KINDS:
-        raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2'")
+        raise ValueError(f"unknown loss weighting {weight_kind!r}: one of None, 'min_snr', 'p2', 'trunc_snr'")
     check_prediction(prediction)
     if prediction != "eps" and y_0 is None:
         raise ValueError(f"prediction {prediction!r} forms its target from the noise and y_0: y_0= is required")
@@ -774,6 +780,98 @@ def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_
     _call(f"vf_sampler_step{eps}{rng}", *src, _ptr(y), *noise, *idx, *(_ptr(tab) for tab in tabs), _ptr(y0_prev),
           _ptr(y_next), *sizes, _stream())
     return y_next, wts
+
+
+# ---- progressive distillation (csrc/diffusion.hip holds the definition) ----
+def _check_i64(name, t, n):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous() or t.numel() != n:
+        raise _lib.VFHipError(f"{name} must be a contiguous device int64 tensor of {n} elements")
+
+
+def distill_step_host(seed, ids, K):
+    """The host mirror of the seeded draw of a distillation sample's student step: ids (any integer tensor / sequence)
+    -> int64 CPU tensor, i = mulhi32(word 0 of the sample's training-scalars call, K) in [0, K).  No GPU."""
+    K = int(K)
+    ids = torch.as_tensor(ids).detach().cpu().reshape(-1).to(torch.int64).contiguous()
+    out = torch.empty_like(ids)
+    rc = _lib.load().vf_distill_step_host(_seed(seed), ctypes.c_void_p(ids.data_ptr()), K,
+                                          ctypes.c_void_p(out.data_ptr()), ids.numel())
+    if rc != 0:
+        raise ValueError(f"the student's step count must be in [1, 2^27], got {K}")
+    return out
+
+
+def distill_begin(y_0, noise, tau_s, gammas, seed=None, ids=None, i=None):
+    """The head of a distillation sample batch, one launch: -> (i, k1, k0 int64 (B,), level_s (B,), z_t like y_0).
+    i = the student step of each sample: `i` (device int64 (B,), clamped to [0, K)) when given, else the seeded draw
+    mulhi32(word 0, K) of samples `ids` (ops.sample_ids); k1 = 2 i + 1 and k0 = 2 i index the teacher's 2K-step tables;
+    level_s = gammas[tau_s[i]], tau_s the student's K model timesteps (device int64 (K,));
+    z_t = sqrt(level_s) y_0 + sqrt(1 - level_s) noise."""
+    y_0, noise = _c(y_0), _c(noise)
+    _check(y_0, noise, gammas)
+    if y_0.dim() != 4 or y_0.shape[1] != 3 or noise.shape != y_0.shape:
+        raise ValueError(f"distill_begin takes y_0 and noise of one (B, 3, H, W) shape, got {tuple(y_0.shape)} and "
+                         f"{tuple(noise.shape)}")
+    B = y_0.shape[0]
+    n = y_0[0].numel()
+    if n % 4:
+        raise ValueError(f"H W must be a multiple of 4, got {tuple(y_0.shape)}")
+    K = tau_s.numel()
+    _check_i64("tau_s", tau_s, K)
+    if K < 1 or K > gammas.numel():
+        raise ValueError(f"tau_s holds the student's K model timesteps, 1 <= K <= T: got {K} for T = {gammas.numel()}")
+    if (i is None) == (seed is None):
+        raise ValueError("distill_begin takes either i= or seed= (with ids=)")
+    if i is None:
+        ids = sample_ids(y_0.device, B, ids)
+        _check_ids(ids, B)
+        src = (_seed(seed), ctypes.c_void_p(ids.data_ptr()), None)
+    else:
+        i = _c(i.reshape(-1))
+        _check_i64("i", i, B)
+        src = (0, None, ctypes.c_void_p(i.data_ptr()))
+    idx = torch.empty(3, B, device=y_0.device, dtype=torch.int64)
+    level_s = torch.empty(B, device=y_0.device, dtype=torch.float32)
+    z_t = torch.empty_like(y_0)
+    _call("vf_distill_begin", *src, ctypes.c_void_p(tau_s.data_ptr()), _ptr(gammas), K, _ptr(y_0), _ptr(noise),
+          ctypes.c_void_p(idx[0].data_ptr()), ctypes.c_void_p(idx[1].data_ptr()), ctypes.c_void_p(idx[2].data_ptr()),
+          _ptr(level_s), _ptr(z_t), B, n, _stream())
+    return idx[0], idx[1], idx[2], level_s, z_t
+
+
+def distill_target(unet_out, off, y, x1, z_t, level_s, i, k0, tables, w1, w2, B, weighting, guidance=None, S=None):
+    """The second teacher step's tail and the student's target, one launch: -> (x_tilde, eps_tilde), both like y.
+    unet_out: the teacher's output at y = z' (S rows, or S + B with guidance: the null rows last); x1: the history buffer
+    the first teacher step (sampler_step(y0_prev=x1)) wrote; z_t, level_s, i, k0: distill_begin's; tables: the teacher's
+    fp32 device tables a, b (2K,); w1, w2: fp32 device (K,) (schedule.distill_tables).
+    x2 = clamp(a[k0] y - b[k0] out2, -1, 1), x_tilde = clamp(w1[i] x1 + w2[i] x2, -1, 1),
+    eps_tilde = (z_t - sqrt(level_s) x_tilde) / sqrt(1 - level_s).  guidance (device fp32 (B,)) with S=: as sampler_step."""
+    _check(unet_out, y, x1, z_t, level_s, tables["a"], tables["b"], w1, w2)
+    if unet_out.dim() != 4 or y.dim() != 4 or y.shape[0] != B or y.shape[1] != 3 or x1.shape != y.shape or \
+            z_t.shape != y.shape or unet_out.shape[-2:] != y.shape[-2:]:
+        raise ValueError(f"distill_target takes y, x1 and z_t of one ({B}, 3, H, W) shape and unet_out (rows, C, H, W), got "
+                         f"{tuple(y.shape)}, {tuple(x1.shape)}, {tuple(z_t.shape)} and {tuple(unet_out.shape)}")
+    if guidance is not None:
+        _check_guidance(guidance, unet_out, B, S)
+    elif S is not None and unet_out.shape[0] != int(S):
+        raise ValueError(f"unet_out has {unet_out.shape[0]} rows for S = {int(S)} views")
+    _, Cout, H, W = unet_out.shape
+    if (H * W) % 4 or Cout < (6 if weighting else 3):
+        raise ValueError(f"distill_target needs H W % 4 == 0 and {6 if weighting else 3} output channels, got "
+                         f"{tuple(unet_out.shape)}")
+    K = w1.numel()
+    if w2.numel() != K or tables["a"].numel() != 2 * K or tables["b"].numel() != 2 * K or level_s.numel() != B:
+        raise ValueError("distill_target needs w1, w2 of K entries, teacher tables of 2K entries and one level per sample")
+    _check_i64("i", i, B)
+    _check_i64("k0", k0, B)
+    if off.dtype != torch.int32 or off.numel() != B + 1:
+        raise ValueError(f"off must be the int32 offsets table of {B} samples (ops.view_offsets)")
+    x_t, e_t = torch.empty_like(y), torch.empty_like(y)
+    _call("vf_distill_target", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), _ptr(x1), _ptr(z_t),
+          _ptr(level_s), ctypes.c_void_p(i.data_ptr()), ctypes.c_void_p(k0.data_ptr()), _ptr(tables["a"]),
+          _ptr(tables["b"]), _ptr(w1), _ptr(w2), _ptr(x_t), _ptr(e_t), B, Cout, H * W, int(weighting), _ptr(guidance),
+          _stream())
+    return x_t, e_t
 
 
 def psnr(generated, target):

@@ -179,3 +179,26 @@ def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps"):
         out["c0"][k] = g[k] * (1.0 + 1.0 / (2.0 * r))
         out["c1"][k] = -g[k] / (2.0 * r) + 0.0          # (+ 0.0: no negative zero in the table)
     return out
+
+
+# ---- progressive distillation: the grids and the target weights of a K-step student of a 2K-step teacher ------------
+def distill_tables(betas, K, teacher_prediction="eps"):
+    """float64 betas (T,), K student steps -> {tau_s (K,), tau_t (2K,) int64; w1, w2 float64 (K,); teacher, student: the two
+    sampler_tables dicts} (csrc/diffusion.hip holds the definition).  tau_s / tau_t = sample_timesteps(T, K / 2K), so
+    tau_t[1::2] == tau_s; teacher = sampler_tables(betas, tau_t, "ddim", 0, teacher_prediction), student = the same at
+    tau_s for "eps" (only its cy, c0 take part).  w1[i] = cy_T[2i] c0_T[2i+1] / c0_S[i], w2 = 1 - w1: the student's target
+    is x~ = w1 x1 + w2 x2 of the teacher's two clamped predictions, a convex combination (0 <= w1 <= 1, w1[0] = 0), and
+    cy_S z + c0_S x~ is then the teacher's two-step result.  ValueError for K < 1 or 2K > T."""
+    betas = np.asarray(betas, dtype=np.float64)
+    T = int(betas.shape[0])
+    if isinstance(K, (bool, float, np.floating)) or not isinstance(K, (int, np.integer)):
+        raise ValueError(f"the student's step count must be an integer, got {K!r}")
+    K = int(K)
+    if K < 1 or 2 * K > T:
+        raise ValueError(f"a K-step student needs a 2K-step teacher on the T = {T} schedule: 1 <= K <= {T // 2}, got {K}")
+    tau_s, tau_t = sample_timesteps(T, K), sample_timesteps(T, 2 * K)
+    assert (tau_t[1::2] == tau_s).all()
+    teacher = sampler_tables(betas, tau_t, "ddim", 0.0, teacher_prediction)
+    student = sampler_tables(betas, tau_s, "ddim", 0.0, "x0")     # (a, b unused: "x0" has them finite on every schedule)
+    w1 = teacher["cy"][0::2] * teacher["c0"][1::2] / student["c0"]
+    return dict(tau_s=tau_s, tau_t=tau_t, w1=w1, w2=1.0 - w1, teacher=teacher, student=student)

@@ -129,6 +129,9 @@ def split_batch(batch, extra, accum_steps):
     return [({k: cut(v, m) for k, v in batch.items()}, {k: cut(v, m) for k, v in extra.items()}) for m in range(A)]
 
 
+DISTILL_INPUTS = ("distill_z", "distill_level", "distill_eps", "distill_x0")     # ViewFusion.distill_targets
+
+
 class _StepGraph:
     """One captured training iteration (forward, backward, Adam) for one batch geometry -- or, with accum_steps > 1, one
     captured micro-batch (forward, backward, the accumulate launch)."""
@@ -212,7 +215,19 @@ class Trainer:
     step see an updated proposal: equality with the undivided batch is NOT claimed then (each micro-batch is still
     unbiased on its own).  Single process, GPU model only: world > 1 or a CPU model with a level sampler raises ValueError
     (the statistics would be rank-local and the ranks' proposals would drift apart; a reduction of them is not built).
-    Checkpoints: drivers.save_checkpoint(..., level_sampler=model.level_sampler.state_dict())."""
+    Checkpoints: drivers.save_checkpoint(..., level_sampler=model.level_sampler.state_dict()).
+
+    Progressive distillation (`model.set_distill(teacher, steps=K)`, csrc/diffusion.hip; default None: nothing above
+    changes) is the model's too, and every call of it drops the captured steps.  The teacher phase -- the draw of the
+    student step, the teacher's two no-grad forwards and the two distillation kernels (ViewFusion.distill_targets) -- runs
+    launch by launch in front of every step, and with accum_steps > 1 in front of every micro-batch (the draws are
+    functions of the sample id, so a micro-batch targets what its samples target in the undivided batch); the student's
+    step then takes z_t, its level, eps~ and x~ as injected inputs, which are graph inputs like t / u / noise.  A captured
+    step therefore holds the student's launches only -- the capture's GroupNorm / convolution accounting and the primed
+    tables are the student's, as before -- and replay equals eager bit for bit.  The optimizer holds the student's
+    parameters only; the teacher never changes.  `model.last_distill` = (i, x~) of the last (micro-)batch.  Capturing
+    the teacher phase as a graph of its own is not built (profiles/distill.md prices it).  GPU model only; a multi-rank
+    run is not refused (the teacher phase has no collective) and not claimed."""
     GRAPH_AFTER = 2
     GRAPH_MAX = 96
     AGREE_EVERY = 64            # multi-rank agreement: the failure flag is read at least this often (see _agree)
@@ -431,9 +446,9 @@ class Trainer:
         from . import ops
         if not self.use_graph or ops.st.KERNEL_LOG is not None or (self.arena is not None and self.arena.flat is None):
             return None
-        # injected draws are graph inputs, and so are the sample ids of the seeded draws; the seed is a constant of the
-        # captured launches, so it is part of the key; nothing else is
-        if any(k not in ("t", "u", "noise", "seed", "sample_ids") for k in extra):
+        # injected draws are graph inputs, and so are the sample ids of the seeded draws and the teacher phase's outputs of a
+        # distillation step; the seed is a constant of the captured launches, so it is part of the key; nothing else is
+        if any(k not in ("t", "u", "noise", "seed", "sample_ids") + DISTILL_INPUTS for k in extra):
             return None
         seed = extra.get("seed")
         extra = {k: v for k, v in extra.items() if k != "seed" and v is not None}
@@ -641,6 +656,13 @@ class Trainer:
                 self._drop_graphs()
             self._loss_key = loss_key
             self._check_level_sampler()
+        if getattr(self.module, "_distill", None) is not None and "distill_z" not in extra:
+            # progressive distillation: the teacher phase of this (micro-)batch, no-grad and launch by launch, in front of
+            # the student's step, which takes its four outputs as injected inputs (graph inputs of a captured step) --
+            # so a capture holds the student's launches alone, and its accounting is the default step's
+            draws = {k: extra[k] for k in ("t", "noise", "seed", "sample_ids") if extra.get(k) is not None}
+            tgt = self.module.distill_targets(batch["y_cond"], batch["view_count"], batch["angle"], batch["y_0"], **draws)
+            extra = {**{k: v for k, v in extra.items() if k not in ("t", "u", "noise")}, **tgt}
         key, vc = self._graph_key(batch, extra) or (None, None)
         if key is not None and accum is None and self._graph_epoch is not None and \
                 self.opt.graph_epoch != self._graph_epoch:      # (a micro-batch graph addresses no Adam state)

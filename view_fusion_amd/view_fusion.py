@@ -40,6 +40,11 @@ multiplies the sample's loss by the importance weight that keeps the objective u
 three channels mean: the noise, v = sqrt(g) noise - sqrt(1 - g) y_0, or y_0 itself.  Training forms the target inside
 the loss kernels; sampling hands every reverse-step tail the (a, b) pair of y0_hat = a y - b out that belongs to the
 prediction, so generate() and everything built on it need no new argument.  csrc/diffusion.hip holds the definition.
+
+`set_distill(teacher, steps=K)` (default None: every launch and every bit as before) turns the training forward into one
+step of progressive distillation (Salimans & Ho): the target is what the frozen `teacher` -- another ViewFusion, held
+outside the module tree -- reaches in two deterministic DDIM steps of its 2K-step chain, and the model learns to get
+there in one step of its own K-step chain.  csrc/diffusion.hip holds the definition; drivers.progressive_distill halves K.
 """
 import torch
 from torch import nn
@@ -70,14 +75,21 @@ class ViewFusion(nn.Module):
         # what the network predicts (set_prediction): a plain attribute too; the (a, b) tables of v / x0, made on demand
         self.prediction = "eps"
         self._pred_tabs = None
+        # progressive distillation (set_distill): the settings -- the teacher among them, which is NOT a submodule -- and
+        # the last training forward's (i, x~): plain attributes too
+        object.__setattr__(self, "_distill", None)
+        self._distill_gen = 0
+        self.last_distill = None
 
     # -- training objective -------------------------------------------------------------------
     def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
         """The training objective of forward(): loss = mean_b w_b mean_i rho(noise_hat - noise)  (csrc/loss_weight.h).
 
         penalty: "mse" (d^2), "l1" (|d|) or "huber" (F.huber_loss with `delta`).
-        weighting: None (w = 1), "min_snr" (w = min(SNR, snr_gamma) / SNR, Hang et al.) or "p2" (w = (p2_k + SNR)^-p2_gamma,
-        Choi et al.), with SNR = gamma / (1 - gamma) of the sample's own continuous level.  No renormalisation by sum w.
+        weighting: None (w = 1), "min_snr" (w = min(SNR, snr_gamma) / SNR, Hang et al.), "p2" (w = (p2_k + SNR)^-p2_gamma,
+        Choi et al.) or "trunc_snr" (w = max(SNR, 1) / SNR: the truncated-SNR weight max(SNR, 1) on the x-space error of
+        Salimans & Ho, which keeps a signal at low SNR for a distilled eps-student), with SNR = gamma / (1 - gamma) of the
+        sample's own level.  No renormalisation by sum w.
         The defaults ARE the reference's loss, and with them forward() runs exactly the launches it ran before.  Anything
         else runs the loss-option kernels (the same launch count) and forward() then also leaves `last_sample_loss`
         (B,), the unweighted per-sample loss, and `last_level` (B,): detached device tensors, valid until the next
@@ -86,7 +98,7 @@ class ViewFusion(nn.Module):
         if penalty not in PENALTIES:
             raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
         if weighting not in WEIGHT_KINDS:
-            raise ValueError(f"unknown loss weighting {weighting!r}: one of None, 'min_snr', 'p2'")
+            raise ValueError(f"unknown loss weighting {weighting!r}: one of None, 'min_snr', 'p2', 'trunc_snr'")
         delta, snr_gamma, p2_k, p2_gamma = float(delta), float(snr_gamma), float(p2_k), float(p2_gamma)
         if not delta > 0:
             raise ValueError(f"delta must be positive, got {delta}")
@@ -173,13 +185,139 @@ class ViewFusion(nn.Module):
         self._pred_tabs = None
         self._plan = None
 
+    def set_distill(self, teacher=None, steps=None, guidance=None, threshold=None, guidance_rescale=None):
+        """Progressive distillation (Salimans & Ho; csrc/diffusion.hip holds the definition).  set_distill(None), the default:
+        off -- every launch and every bit as before.
+
+        teacher: another ViewFusion on the same device with the same noise schedule (betas and T), image channels and
+        `relative` configuration; its `prediction` and `weighting_inference` are its own.  steps = K: the model becomes a
+        K-step student of the teacher's 2K-step deterministic DDIM chain, 1 <= K <= T // 2.  In training mode forward()
+        then draws a student step i in [0, K) per sample (seeded: mulhi32(word 0, K), the word that gives t otherwise;
+        unseeded: torch.randint(0, K) where t is drawn; an injected t= is read as i), forms z_t at the level
+        gammas[tau_S[i]] its own sample_steps=K sampler will use, runs the teacher's steps 2i+1 and 2i from there under
+        no_grad, and takes the existing objective -- set_loss penalties and weights, loss_bins, last_sample_loss, last_level
+        -- with noise := eps~ and y_0 := x~, the target that makes one student step land where the teacher's two do.
+        guidance (a scale, or one per sample): the teacher's steps are guided (one null row per sample), so the student
+        needs no null row at sampling time.  threshold / guidance_rescale of the teacher are not built: ValueError.
+        The teacher is held outside the module tree: state_dict(), parameters(), modules(), the optimizer, DDP and
+        functional_call never see it; it is put into eval mode, runs the UNet's inference path and its parameters get no
+        gradient.  `last_distill` = (i, x~) of the last distillation forward (device tensors, no sync).
+        Refused with ValueError: a level sampler, conditioning dropout p > 0 and, when forward() runs, a CPU
+        model (the settings can be made on one, like a level sampler's).  A Trainer drops its captured steps when this is
+        called and runs the teacher phase in front of every (micro-)step."""
+        self._distill_gen += 1
+        self.last_distill = None
+        if teacher is None:
+            if steps is not None or guidance is not None:
+                raise ValueError("set_distill(None) turns distillation off: steps= / guidance= need a teacher")
+            object.__setattr__(self, "_distill", None)
+            return
+        if threshold is not None or guidance_rescale is not None:
+            raise ValueError("a thresholded or rescaled teacher is not built: the teacher's two steps use the static clamp")
+        if not isinstance(teacher, ViewFusion) or teacher is self:
+            raise ValueError("the teacher must be another ViewFusion model")
+        if getattr(self, "betas64", None) is None or getattr(teacher, "betas64", None) is None:
+            raise ValueError("set_distill needs the noise schedule of both models: call set_new_noise_schedule first")
+        import numpy as np
+        if teacher.num_timesteps != self.num_timesteps or not np.array_equal(teacher.betas64, self.betas64):
+            raise ValueError("the teacher must have the student's noise schedule (the same betas, the same T)")
+        if self._in_channels(teacher.denoise_fn) != self._in_channels(self.denoise_fn):
+            raise ValueError("the teacher must take the student's input: the same image channels and `relative` "
+                             f"configuration ({self._in_channels(teacher.denoise_fn)} input channels against "
+                             f"{self._in_channels(self.denoise_fn)})")
+        if isinstance(steps, bool) or not isinstance(steps, int):
+            raise ValueError(f"steps must be an integer, got {steps!r}")
+        tabs = _schedule.distill_tables(self.betas64, steps, teacher.prediction)      # ValueError for K < 1, 2K > T
+        if guidance is not None and not torch.is_tensor(guidance) and not isinstance(guidance, (list, tuple)):
+            import math
+            guidance = float(guidance)
+            if not math.isfinite(guidance) or guidance < 0:
+                raise ValueError(f"a guidance scale must be finite and >= 0, got {guidance}")
+        if self._level_spec is not None:
+            raise ValueError("distillation with a level sampler is not built: the student step is drawn uniformly "
+                             "(set_level_sampler(None) first)")
+        if self._cond_drop_p > 0:
+            raise ValueError("distillation with conditioning dropout is not built: a distilled student is not "
+                             "w-conditioned (set_cond_dropout(0) first)")
+        dev = self.gammas.device
+        if teacher.gammas.device != dev:
+            raise ValueError(f"the teacher must live on the student's device ({teacher.gammas.device} against {dev})")
+        teacher.eval()
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32, device=dev)              # noqa: E731
+        plan = {k: f32(v) for k, v in tabs["teacher"].items()}
+        tau_t = torch.tensor(tabs["tau_t"], dtype=torch.int64, device=dev)
+        object.__setattr__(self, "_distill", dict(
+            teacher=teacher, steps=int(steps), guidance=guidance, prediction=teacher.prediction, plan=plan,
+            level_t=self.gammas[tau_t].contiguous(), tau_s=torch.tensor(tabs["tau_s"], dtype=torch.int64, device=dev),
+            w1=f32(tabs["w1"]), w2=f32(tabs["w2"])))
+
+    @staticmethod
+    def _in_channels(net):
+        for m in net.modules():
+            if isinstance(m, nn.Conv2d):
+                return m.in_channels
+        return None
+
+    @torch.no_grad()
+    def distill_targets(self, y_cond, view_count, angle, y_0, noise=None, t=None, seed=None, sample_ids=None):
+        """The teacher phase of a distillation step (steps 1 - 5 of the definition in csrc/diffusion.hip), under no_grad:
+        -> dict(distill_z = z_t, distill_level = gammas[tau_S[i]] (B,), distill_eps = eps~, distill_x0 = x~), the four
+        inputs forward() takes in place of running the phase itself (a Trainer runs it in front of its captured step).
+        Launches: [noise draw] begin, stack (conditioning half once), the teacher UNet, sampler_step (history buffer),
+        level gather + re-stack of the target half, the teacher UNet, distill_target.  Sets `last_distill` = (i, x~)."""
+        from . import ops
+        d = self._distill
+        if d is None:
+            raise ValueError("distill_targets needs set_distill(teacher, steps=K)")
+        teacher = d["teacher"]
+        if teacher.prediction != d["prediction"]:
+            raise ValueError("the teacher's prediction changed since set_distill: call set_distill again")
+        if self._level_spec is not None or self._cond_drop_p > 0:
+            raise ValueError("distillation with a level sampler or conditioning dropout is not built (DESIGN 8)")
+        if self.gammas.device.type != "cuda" or teacher.gammas.device != self.gammas.device:
+            raise ValueError("distillation runs on the GPU only (its target is formed by HIP kernels), with the teacher "
+                             "on the student's device: move both models there and call set_distill again")
+        if teacher.training:
+            teacher.eval()
+        b, dev = y_0.shape[0], y_0.device
+        y_0 = y_0.contiguous()
+        ids = None
+        if seed is not None and (t is None or noise is None):
+            ids = ops.sample_ids(dev, b, sample_ids)
+        if seed is not None and noise is None:
+            noise = ops.randn_ids(seed, ids, ops.diffusion.RNG_TRAIN_NOISE, 0, tuple(y_0.shape[1:]))
+        if t is None and seed is None:            # the reference's draw order: the step where t is drawn, then the noise
+            t = torch.randint(0, d["steps"], (b,), device=dev)
+        if noise is None:
+            noise = torch.randn_like(y_0)
+        if t is None:
+            i, k1, k0, level, z_t = ops.distill_begin(y_0, noise, d["tau_s"], self.gammas, seed=seed, ids=ids)
+        else:
+            i, k1, k0, level, z_t = ops.distill_begin(y_0, noise, d["tau_s"], self.gammas, i=t.to(torch.int64))
+        gs = None if d["guidance"] is None else ops.guidance_scales(dev, b, d["guidance"])
+        guided = gs is not None
+        off, S, max_v = ops.view_offsets(view_count, dev)
+        w_on = bool(teacher.weighting_inference)
+        y_cond, angle = y_cond.contiguous(), angle.contiguous()
+        y, x1 = z_t.clone(), torch.empty_like(z_t)                 # the teacher's chain moves y in place; x1: its history
+        x, out = teacher._denoise(y, y_cond, angle, k1, off, S, levels=d["level_t"], null_rows=guided)
+        ops.sampler_step(out, off, y, None, k1, d["plan"], b, max_v, w_on, y0_prev=x1, want_weights=False, inplace=True,
+                         guidance=gs, S=S)
+        _, out = teacher._denoise(y, y_cond, angle, k0, off, S, x=x, copy_cond=False, levels=d["level_t"],
+                                  null_rows=guided)
+        x_t, eps_t = ops.distill_target(out, off, y, x1, z_t, level, i, k0, d["plan"], d["w1"], d["w2"], b, w_on,
+                                        guidance=gs, S=S)
+        self.last_distill = (i, x_t)
+        return dict(distill_z=z_t, distill_level=level, distill_eps=eps_t, distill_x0=x_t)
+
     def loss_key(self):
         """What a captured training step depends on besides its inputs: the objective, the attached histogram, the
-        conditioning-dropout probability, the level sampler (every set_level_sampler call counts) and the prediction."""
+        conditioning-dropout probability, the level sampler (every set_level_sampler call counts), the prediction and the
+        distillation settings (every set_distill call counts)."""
         h = self.loss_hist
         return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
                 None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p,
-                self._level_gen, self.prediction)
+                self._level_gen, self.prediction, self._distill_gen)
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -432,7 +570,8 @@ class ViewFusion(nn.Module):
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
                 z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0,
-                guidance=None, cond_drop=None, threshold=None, threshold_max=None, guidance_rescale=None):
+                guidance=None, cond_drop=None, threshold=None, threshold_max=None, guidance_rescale=None, distill_z=None,
+                distill_level=None, distill_eps=None, distill_x0=None):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
             return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
                                  sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta,
@@ -442,6 +581,23 @@ class ViewFusion(nn.Module):
         b = y_0.shape[0]
         dev = y_0.device
         level = None
+        if distill_z is not None or (self._distill is not None and self.training):
+            # progressive distillation (set_distill): the teacher phase -- or its four outputs, injected -- then the
+            # student's ordinary stacking of z_t at its level, the UNet and the ordinary objective on (eps~, x~)
+            tgt = dict(distill_z=distill_z, distill_level=distill_level, distill_eps=distill_eps, distill_x0=distill_x0)
+            if distill_z is None:
+                if cond_drop is not None or u is not None:
+                    raise ValueError("a distillation step takes no cond_drop= / u=: its level is gammas[tau_S[i]]")
+                tgt = self.distill_targets(y_cond, view_count, angle, y_0, noise=noise, t=t, seed=seed,
+                                           sample_ids=sample_ids)
+            elif any(v is None for v in tgt.values()):
+                raise ValueError("distill_z / distill_level / distill_eps / distill_x0 (distill_targets) come together")
+            level = tgt["distill_level"].reshape(-1)
+            off, S, _ = ops.view_offsets(view_count, dev)
+            self.last_cond_drop = None
+            x, level_s, angle_s = ops.stack_views(y_cond, tgt["distill_z"].contiguous(), None, level, angle, off, S)
+            out = self.denoise_fn(x, angle_s, level_s)
+            return self._objective(out, tgt["distill_eps"], tgt["distill_x0"], level, off, b)
         # conditioning dropout (set_cond_dropout): an injected mask wins; else drawn in training mode when p > 0
         drop_p = self._cond_drop_p if (cond_drop is None and self.training) else 0.0
         drop = cond_drop
@@ -490,6 +646,12 @@ class ViewFusion(nn.Module):
         x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S,
                                               drop=drop)
         out = self.denoise_fn(x, angle_s, level_s)
+        return self._objective(out, noise, y_0, level, off, b, smp, iw, t)
+
+    def _objective(self, out, noise, y_0, level, off, b, smp=None, iw=None, t=None):
+        """The training loss of the composed output against (noise, y_0) at `level`: the reference's MSE, or the
+        loss-option kernels (set_loss, loss_hist, a level sampler, a prediction other than "eps")."""
+        from . import ops
         self.last_t, self.last_importance_weight = (None, None) if smp is None else (t, iw)
         if self._loss is None and self.loss_hist is None and smp is None and self.prediction == "eps":
             return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
