@@ -528,7 +528,10 @@ def test_cat_free_decoder_ops(dev, C1, C2, H, Cout, S):
 
 
 def test_conv_large_batch_split_k(dev):
-    """S large enough that wgrad runs many pixel tiles per slice; odd S for the 8x8 two-image tiles."""
+    """Stride-1 3x3 layers at large S: S (H/2) (W/2) >= 256 at every shape here, so the weight gradient is the Winograd
+    F(4x4) kernel's (vf_wino_wgrad: many chunks per slice; odd S on the 8x8 map, one chunk per view) -- NOT the direct
+    kernel's, whose multi-tile slices and two-image 8x8 tiles tests/test_gpu_wgrad_plan.py runs.  The kernel log confirms
+    the entry."""
     from view_fusion_amd import ops
     for (Cin, Cout, H, S) in [(64, 64, 64, 40), (320, 320, 8, 97), (192, 192, 16, 96)]:
         layer = torch.nn.Conv2d(Cin, Cout, 3, padding=1)
@@ -538,7 +541,14 @@ def test_conv_large_batch_split_k(dev):
         wgc = layer.weight.grad.clone(); layer.zero_grad()
         layer = layer.to(dev)
         xg = x.to(dev).requires_grad_(True)
-        yg = ops.conv2d(xg, layer); yg.backward(gy.to(dev))
+        ops.st.KERNEL_LOG = []
+        try:
+            yg = ops.conv2d(xg, layer); yg.backward(gy.to(dev))
+            torch.cuda.synchronize()
+            wgrad = [e[5] for e in ops.st.KERNEL_LOG if e[0] == "conv_wgrad"]
+        finally:
+            ops.st.KERNEL_LOG = None
+        assert wgrad == (["vf_wino_wgrad_main", "vf_wino44_reduce_multi"] if ops.st.WRED_DEFER else ["vf_wino_wgrad"]), wgrad
         assert rel(yg, yc) < 2e-5 and rel(xg.grad, xc.grad) < 2e-5
         assert rel(layer.weight.grad, wgc) < 1e-4
 
