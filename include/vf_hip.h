@@ -63,7 +63,8 @@ int vf_conv_pack_weights(const float* w_oihw, float* w_fwd, float* w_bwd /*or NU
 int vf_conv_pack_weights_multi(const void* desc, int nlayers, long total_blocks, void* stream);
 /* mode 0 stride-1 | 1 stride-2 (x is 2Hx2W) | 2 nearest-x2 upsampled x (x is H/2xW/2) |
  * 4 sub-pixel dgrad of mode 1: x = dY (HxW), y = dX (2Hx2W), every
- * output parity gets its own taps (no zeros multiplied; w_packed = the dgrad pack; no epilogue operands).
+ * output parity gets its own taps (no zeros multiplied; w_packed = the dgrad pack; no epilogue operands but the
+ * residual, which has dX's layout).  Mode 4 never splits K: it ignores ws / ws_floats.
  * H,W = OUTPUT size (mode 4: the dY size), any size (mode 2: both even).  The shapes the specialised kernels are
  * compiled for (square power of two in [8,128]; mode 1 / 4 up to 64, mode 2 from 16) run them (conv.hip); every other
  * geometry runs the general runtime-H,W kernels (conv_any.hip) from the same packed weights.  The same holds for
@@ -115,6 +116,18 @@ long vf_conv_small_pack_floats(int Cout, int Cin);
 int vf_conv_small_pack(const float* w_oihw, float* w_packed, int Cout, int Cin, void* stream);
 /* split-K workspace the call above wants at this shape (0 when the natural grid fills the chip) */
 long vf_conv_fwd_ws_floats(int S, int Cin, int Cout, int H, int W, int KS);
+/* Host-only query (touches no device, launches nothing): the plan vf_conv_fwd takes for these arguments -- also
+ * vf_conv_fwd_gn (gn_groups > 0, else 0), vf_conv1x1_cat_fwd (0 < C1 < Cin, else 0 or Cin) and vf_conv1x1_cat_dgrad
+ * (0 < C1o < Cout, else 0 or Cout); has_ws: a workspace of ws_floats floats is passed.  The launchers execute the
+ * function that answers.  out[8] = { route: 0 conv_mfma_kernel, 1 conv1x1_kernel<1>, 2 conv1x1_kernel<2>,
+ * 3 conv_any_kernel;  npt: 64-pixel units per workgroup tile;  nblk: workgroups per K split;  ks: K splits after the
+ * clamp by the workspace (the launch has nblk * ks workgroups and writes ks slabs of S*Cout*H*W floats);  safe: the
+ * instantiation with unconditional loads;  what follows the conv: 0 nothing, 1 the split-K reduce, 2 the reduce that also
+ * evaluates the GroupNorm, 3 a GroupNorm launch (ks = 1), 4 the split-K reduce and then a GroupNorm launch (group above
+ * 8192 float4);  NV, NT: the variant of 2, else 0 }.  Mode 4 ignores the workspace: ks = 1 whatever is passed.
+ * Returns hipErrorInvalidValue for arguments the entries refuse. */
+int vf_conv_fwd_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, int C1, int C1o, int gn_groups, int has_ws,
+                     long ws_floats, int* out /*[8]*/);
 /* 1x1 conv on the channel concatenation [x1 (C1 channels, multiple of 64) | x2] (residual conv of the decoder
  * blocks, unet.py:134,238): forward, dgrad into two tensors, wgrad */
 int vf_conv1x1_cat_fwd(const float* x1, const float* x2, int C1, const float* w_packed, const float* bias, float* y,

@@ -11,6 +11,10 @@ int vfi_conv_any_fwd(const float* x, const float* x2, int C1, const float* w_pac
                      const float* view_bias, const float* residual, float* y, float* y2, int C1o, float* ws, long ws_floats,
                      int S, int Cin, int Cout, int H, int W, int KS, int mode, hipStream_t st);
 long vfi_conv_any_fwd_ws_floats(int S, int Cin, int Cout, int H, int W, int KS);
+// the plan of that launch, host only: out = {npt (64-pixel units per tile), nblk (workgroups per K split), ks (K splits
+// after the workspace clamp)}
+void vfi_conv_any_fwd_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, bool split_out, bool has_ws,
+                           long ws_floats, int out[3]);
 // Weight gradient at any H x W (output size), modes 0 / 1 / 2.  desc9 != null: the slab sum is left to the caller's
 // deferred vf_wino44_reduce_multi launch (desc9 receives the row, *nblocks its workgroup count).
 int vfi_conv_any_wgrad(const float* x, const float* x2, int C1, const float* dy, float* dw, float* ws, long ws_floats, int S,

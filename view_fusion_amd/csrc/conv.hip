@@ -956,10 +956,17 @@ __global__ __launch_bounds__(NT) void conv_splitk_reduce_gn_kernel(const float4*
     }
 }
 
-// launches the fused reduce + GroupNorm for a (view, group) of n4g float4; false if the group is too large
-inline bool launch_reduce_gn(const ConvArgs& a, int ks, size_t n4_total, int HW, hipStream_t st) {
+// (NV, NT) of the fused reduce + GroupNorm for a (view, group) of n4g float4; false if the group is too large
+inline bool reduce_gn_variant(long n4g, int* nv, int* nt) {
+    static const int table[6][3] = {{256, 1, 256}, {512, 2, 256}, {1024, 4, 256}, {2048, 8, 256}, {4096, 8, 512}, {8192, 8, 1024}};
+    for (const auto& r : table)
+        if (n4g <= r[0]) { *nv = r[1]; *nt = r[2]; return true; }
+    return false;
+}
+
+// launches the fused reduce + GroupNorm variant (nv, nt) that reduce_gn_variant chose
+inline void launch_reduce_gn(const ConvArgs& a, int ks, size_t n4_total, int HW, int nv, int nt, hipStream_t st) {
     const int cpg = a.Cout / a.gn_groups;
-    const long n4g = (long)cpg * HW / 4;
     int hw4sh = 0;
     while ((1 << hw4sh) < HW / 4) ++hw4sh;
     const dim3 grid(a.S * a.gn_groups);
@@ -969,16 +976,15 @@ inline bool launch_reduce_gn(const ConvArgs& a, int ks, size_t n4_total, int HW,
         hipLaunchKernelGGL((conv_splitk_reduce_gn_kernel<NV, NT>), grid, dim3(NT), 0, st, (const float4*)a.ws, a.bias, \
                            a.vbias, (const float4*)a.res, y4, a.gn_gamma, a.gn_beta, (float4*)a.gn_out, ks, n4_total, \
                            hw4sh, a.Cout, cpg, a.gn_eps, a.gn_silu);                                            \
-        return true;                                                                                            \
+        return;                                                                                                 \
     }
-    if (n4g <= 256) VF_RGN(1, 256)
-    if (n4g <= 512) VF_RGN(2, 256)
-    if (n4g <= 1024) VF_RGN(4, 256)
-    if (n4g <= 2048) VF_RGN(8, 256)
-    if (n4g <= 4096) VF_RGN(8, 512)
-    if (n4g <= 8192) VF_RGN(8, 1024)
+    if (nv == 1 && nt == 256) VF_RGN(1, 256)
+    if (nv == 2 && nt == 256) VF_RGN(2, 256)
+    if (nv == 4 && nt == 256) VF_RGN(4, 256)
+    if (nv == 8 && nt == 256) VF_RGN(8, 256)
+    if (nv == 8 && nt == 512) VF_RGN(8, 512)
+    if (nv == 8 && nt == 1024) VF_RGN(8, 1024)
 #undef VF_RGN
-    return false;
 }
 
 extern "C" int vf_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int S,
@@ -997,39 +1003,46 @@ inline int choose_ksplit(int nblk, int nchunks) {
     return k < 1 ? 1 : k;
 }
 
-template <int KS, int LOGW, int MODE, int NPT, int NCO = 1>
-int conv_blocks(const ConvArgs& a) {
-    using G = Geo<KS, LOGW, MODE, 64 * NPT>;
-    const int ntiles = G::IM > 1 ? (a.S + G::IM - 1) / G::IM : a.S * G::TPI;
-    return ntiles * ((a.CoutP / TCO + NCO - 1) / NCO);
+// The plan of one forward / dgrad launch: every decision the launchers of this file, conv1x1.hip and conv_any.hip take on
+// the host, made in ONE place (conv_fwd_plan below) that the launchers execute and vf_conv_fwd_plan reports.
+enum { ROUTE_MFMA = 0, ROUTE_1X1_64 = 1, ROUTE_1X1_128 = 2, ROUTE_ANY = 3 };
+// what follows the conv launch: nothing | the plain split-K reduce | the reduce that also normalises (variant NV, NT) |
+// a GroupNorm launch (the conv wrote y itself: ks = 1) | the plain reduce, then a GroupNorm launch (group too large)
+enum { RED_NONE = 0, RED_PLAIN = 1, RED_GN = 2, RED_GN_LAUNCH = 3, RED_PLAIN_GN_LAUNCH = 4 };
+struct ConvFwdPlan {
+    int route, npt, nblk, ks, safe, reduce, nv, nt;
+};
+
+// workgroups of a launch with 64*npt-pixel tiles: whole image rows, or several whole images per tile (Geo::IM)
+inline int conv_blocks(int S, int CoutP, int HW, int npt) {
+    const int tpix = 64 * npt;
+    const int ntiles = HW >= tpix ? S * (HW / tpix) : (S + tpix / HW - 1) / (tpix / HW);
+    return ntiles * (CoutP / TCO);
 }
 
+// (1x1 convs: a 64*NCO-channel workgroup tile -- NCO = 2, 3 instantiations of conv_mfma_kernel -- was measured:
+// 5-20 % faster on a few 16x16 / 8x8 shapes, 10-100 % slower wherever the grid stops filling the chip, net worse;
+// only NCO = 1 is compiled.)
 template <int KS, int LOGW, int MODE, int NPT, int NCO = 1>
-int launch_conv_npt(ConvArgs a, hipStream_t st, long ws_floats) {
+int launch_conv_npt(ConvArgs a, hipStream_t st, const ConvFwdPlan& p) {
     constexpr int HW = 1 << (2 * LOGW);
-    const int nblk = conv_blocks<KS, LOGW, MODE, NPT, NCO>(a);
+    const int nblk = p.nblk, ks = p.ks;
     const size_t out_floats = (size_t)a.S * a.Cout * HW;
-    int ks = choose_ksplit(nblk, a.CinP / (KS == 3 ? 8 : 32));
-    if (a.ws == nullptr) ks = 1;
-    while (ks > 1 && (size_t)ks * out_floats > (size_t)ws_floats) --ks;
     a.ksplit = ks;
-    using G = Geo<KS, LOGW, MODE, 64 * NPT>;
-    // every patch element exists (see load_patch4): whole 32-channel chunks from either source, whole view groups
-    const bool safe = KS == 1 && a.Cin % 32 == 0 && (!a.x2 || a.C1 % 32 == 0) && (G::IM == 1 || a.S % G::IM == 0);
-    if (KS == 1 && safe)
+    if (KS == 1 && p.safe)
         hipLaunchKernelGGL((conv_mfma_kernel<KS, LOGW, MODE, NPT, NCO, KS == 1>), dim3(nblk * ks), dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((conv_mfma_kernel<KS, LOGW, MODE, NPT, NCO, false>), dim3(nblk * ks), dim3(256), 0, st, a);
-    bool gn_done = false;
     if (ks > 1) {
         const size_t n4 = out_floats / 4;
-        if (a.gn_out) gn_done = launch_reduce_gn(a, ks, n4, HW, st);
-        if (!gn_done)
+        if (p.reduce == RED_GN)
+            launch_reduce_gn(a, ks, n4, HW, p.nv, p.nt, st);
+        else
             hipLaunchKernelGGL(conv_splitk_reduce_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st,
                                (const float4*)a.ws, a.bias, a.vbias, (const float4*)a.res, (float4*)a.y, ks, n4, HW / 4,
                                a.Cout);
     }
-    if (a.gn_out && !gn_done)         // the conv wrote y itself (no split-K here): plain GroupNorm launch behind it
+    if (p.reduce == RED_GN_LAUNCH || p.reduce == RED_PLAIN_GN_LAUNCH)     // y is complete: plain GroupNorm launch behind it
         return vf_gn_fwd(a.y, a.gn_gamma, a.gn_beta, a.gn_out, a.gn_stats, a.gn_stats + (size_t)a.S * a.gn_groups, a.S,
                          a.Cout, HW, a.gn_groups, a.gn_eps, a.gn_silu, (void*)st);
     VF_RETURN_LAST_ERROR();
@@ -1049,31 +1062,12 @@ inline int npt_override() {
     return v;
 }
 
-// 1x1 convs.  (A 64*NCO-channel workgroup tile -- NCO = 2, 3 instantiations of conv_mfma_kernel -- was measured:
-// 5-20 % faster on a few 16x16 / 8x8 shapes, 10-100 % slower wherever the grid stops filling the chip, net worse;
-// only NCO = 1 is compiled.)
-template <int LOGW, int NPT>
-int launch_conv_1x1(const ConvArgs& a, hipStream_t st, long ws_floats) {
-    return launch_conv_npt<1, LOGW, 0, NPT, 1>(a, st, ws_floats);
-}
-
 template <int KS, int LOGW, int MODE>
-int launch_conv(const ConvArgs& a, hipStream_t st, long ws_floats) {
-    constexpr bool ok1 = LOGW <= 4;                       // 64-pixel tiles
-    if constexpr (KS == 1) {
-        if constexpr (ok1) {
-            const int force = npt_override();
-            if (force == 1 || (force == 0 && conv_blocks<1, LOGW, 0, 2>(a) < CONV_MIN_WGS))
-                return launch_conv_1x1<LOGW, 1>(a, st, ws_floats);
-        }
-        return launch_conv_1x1<LOGW, 2>(a, st, ws_floats);
+int launch_conv(const ConvArgs& a, hipStream_t st, const ConvFwdPlan& p) {
+    if constexpr (LOGW <= 4) {                            // 64-pixel tiles are compiled for maps up to 16 x 16
+        if (p.npt == 1) return launch_conv_npt<KS, LOGW, MODE, 1>(a, st, p);
     }
-    if constexpr (ok1) {
-        const int force = npt_override();
-        if (force == 1 || (force == 0 && conv_blocks<KS, LOGW, MODE, 2>(a) < CONV_MIN_WGS))
-            return launch_conv_npt<KS, LOGW, MODE, 1>(a, st, ws_floats);
-    }
-    return launch_conv_npt<KS, LOGW, MODE, 2>(a, st, ws_floats);
+    return launch_conv_npt<KS, LOGW, MODE, 2>(a, st, p);
 }
 
 template <int KS, int LOGW, int MODE>
@@ -1134,6 +1128,75 @@ inline bool square_pow2(int H, int W) {
     return H == W && lw >= 3 && lw <= 7;
 }
 
+// argument rules of the forward entries (cat: the input is a concatenation [x | x2], split: the output is [y | y2])
+inline bool conv_fwd_args_ok(int Cin, int Cout, int KS, int mode, bool cat, int C1, bool split, int C1o, bool gn,
+                             int gn_groups) {
+    if (KS != 1 && KS != 3) return false;
+    if (KS == 1 && mode != 0) return false;
+    if ((cat || split) && KS != 1) return false;
+    if (cat && (C1 <= 0 || C1 >= Cin || C1 % 32 != 0)) return false;          // chunk-aligned split
+    if (split && (C1o <= 0 || C1o >= Cout || C1o % TCO != 0)) return false;   // tile-aligned split
+    if (gn && (gn_groups <= 0 || Cout % gn_groups != 0 || split || mode == 4)) return false;
+    return true;
+}
+
+// the 1x1 kernel's view of a launch (pointers are filled in by the caller; the predicates only ask whether x2 / y2 exist)
+inline C11Args conv1x1_shape(int S, int Cin, int Cout, int H, int W, int C1, int C1o) {
+    C11Args c{};
+    c.S = S; c.Cin = Cin; c.Cout = Cout; c.C1 = C1; c.C1o = C1o; c.HW = H * W; c.hwsh = 2 * ilog2_exact(W);
+    c.npx = S * H * W;
+    c.nct = round_up(Cout, TCO) / TCO;
+    return c;
+}
+
+// Every host-side decision of a forward / dgrad launch (arguments already checked by conv_fwd_args_ok).
+inline ConvFwdPlan conv_fwd_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, bool cat, int C1, bool split,
+                                 int C1o, bool gn, int gn_groups, bool has_ws, long ws_floats) {
+    ConvFwdPlan p{ROUTE_MFMA, 2, 0, 1, 0, RED_NONE, 0, 0};
+    if (!fwd_specialised(KS, H, W, mode)) {               // any other geometry: the general kernel (conv_any.hip), the
+        int q[3];                                         // GroupNorm of vf_conv_fwd_gn as its own launch
+        vfi_conv_any_fwd_plan(S, Cin, Cout, H, W, KS, mode, split, has_ws, ws_floats, q);
+        p.route = ROUTE_ANY; p.npt = q[0]; p.nblk = q[1]; p.ks = q[2];
+        p.reduce = p.ks > 1 ? (gn ? RED_PLAIN_GN_LAUNCH : RED_PLAIN) : (gn ? RED_GN_LAUNCH : RED_NONE);
+        return p;
+    }
+    if (KS == 1 && !gn) {          // training-size grids: the dedicated 1x1 kernel (conv1x1.hip)
+        static const float present = 0.f;
+        C11Args c = conv1x1_shape(S, Cin, Cout, H, W, C1, C1o);
+        c.x2 = cat ? &present : nullptr;
+        c.y2 = split ? const_cast<float*>(&present) : nullptr;
+        static const bool off = getenv("VF_CONV1X1_OLD") != nullptr;       // (tuning aid: the generic kernel)
+        if (!off && vfi_conv1x1_supported(c)) {
+            int halves;
+            p.nblk = (int)vfi_conv1x1_grid(c, &halves);
+            p.route = halves == 2 ? ROUTE_1X1_128 : ROUTE_1X1_64;
+            return p;
+        }
+    }
+    const int HW = H * W, CK = KS == 3 ? 8 : 32;
+    const int CoutP = round_up(Cout, TCO), CinP = round_up(Cin, CK);
+    const int force = npt_override();
+    p.npt = (HW <= 256 && (force == 1 || (force == 0 && conv_blocks(S, CoutP, HW, 2) < CONV_MIN_WGS))) ? 1 : 2;
+    p.nblk = conv_blocks(S, CoutP, HW, p.npt);
+    int ks = choose_ksplit(p.nblk, CinP / CK);
+    // no workspace; a split output (the split-K reduce writes one destination); mode 4 (its epilogue writes the four
+    // output parities of dX itself and has no partial-sum form: it ignores the workspace)
+    if (!has_ws || split || mode == 4) ks = 1;
+    const size_t out_floats = (size_t)S * Cout * HW;
+    while (ks > 1 && (size_t)ks * out_floats > (size_t)ws_floats) --ks;
+    p.ks = ks;
+    // every patch element exists (see load_patch4): whole 32-channel chunks from either source, whole view groups
+    const int im = HW >= 64 * p.npt ? 1 : 64 * p.npt / HW;
+    p.safe = KS == 1 && Cin % 32 == 0 && (!cat || C1 % 32 == 0) && (im == 1 || S % im == 0);
+    if (ks > 1) {
+        p.reduce = RED_PLAIN;
+        if (gn) p.reduce = reduce_gn_variant((long)(Cout / gn_groups) * HW / 4, &p.nv, &p.nt) ? RED_GN : RED_PLAIN_GN_LAUNCH;
+    } else if (gn) {
+        p.reduce = RED_GN_LAUNCH;
+    }
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1173,7 +1236,8 @@ int vf_conv_pack_weights_multi(const void* desc, int nlayers, long total_blocks,
 // mode 0: x is [S][Cin][H][W]; 1: stride 2, x is [S][Cin][2H][2W]; 2: x is [S][Cin][H/2][W/2]
 // nearest-upsampled on the fly; 4: x = dY [S][Cin][H][W] of a stride-2 conv, y = dX [S][Cout][2H][2W] (w_packed =
 // the dgrad pack, no epilogue operands).
-// ws / ws_floats: optional split-K workspace (see vf_conv_fwd_ws_floats); NULL disables split-K.
+// ws / ws_floats: optional split-K workspace (see vf_conv_fwd_ws_floats); NULL disables split-K.  Mode 4 ignores it: its
+// epilogue stores the four output parities of dX itself, there is no partial-sum form of it.
 struct GnFuse {
     const float* gamma;
     const float* beta;
@@ -1189,13 +1253,11 @@ static int conv_fwd_impl(const float* x, const float* x2, int C1, const float* w
                          const GnFuse* gn = nullptr) {
     if (S <= 0) return 0;
     const int lw = ilog2_exact(W);
-    if (KS != 1 && KS != 3) return (int)hipErrorInvalidValue;
-    if (KS == 1 && mode != 0) return (int)hipErrorInvalidValue;
-    if ((x2 || y2) && KS != 1) return (int)hipErrorInvalidValue;
-    if (x2 && (C1 <= 0 || C1 >= Cin || C1 % 32 != 0)) return (int)hipErrorInvalidValue;     // chunk-aligned split
-    if (y2 && (C1o <= 0 || C1o >= Cout || C1o % TCO != 0)) return (int)hipErrorInvalidValue; // tile-aligned split
-    if (gn && (gn->groups <= 0 || Cout % gn->groups != 0 || y2 || mode == 4)) return (int)hipErrorInvalidValue;
-    if (!fwd_specialised(KS, H, W, mode)) {
+    if (!conv_fwd_args_ok(Cin, Cout, KS, mode, x2 != nullptr, C1, y2 != nullptr, C1o, gn != nullptr, gn ? gn->groups : 0))
+        return (int)hipErrorInvalidValue;
+    const ConvFwdPlan p = conv_fwd_plan(S, Cin, Cout, H, W, KS, mode, x2 != nullptr, C1, y2 != nullptr, C1o, gn != nullptr,
+                                        gn ? gn->groups : 0, ws != nullptr, ws_floats);
+    if (p.route == ROUTE_ANY) {
         // any other geometry: the general kernel (conv_any.hip); the GroupNorm of vf_conv_fwd_gn as its own launch
         const int e = vfi_conv_any_fwd(x, x2, C1, w_packed, bias, view_bias, residual, y, y2, C1o, ws, ws_floats, S, Cin, Cout,
                                        H, W, KS, mode, (hipStream_t)stream);
@@ -1217,16 +1279,13 @@ static int conv_fwd_impl(const float* x, const float* x2, int C1, const float* w
         a.gn_groups = gn->groups; a.gn_silu = gn->silu; a.gn_store_y = gn->store_y; a.gn_eps = gn->eps;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (KS == 1 && !gn) {          // training-size grids: the dedicated 1x1 kernel (conv1x1.hip)
-        C11Args c;
+    if (p.route == ROUTE_1X1_64 || p.route == ROUTE_1X1_128) {
+        C11Args c = conv1x1_shape(S, Cin, Cout, H, W, C1, C1o);
         c.x = x; c.x2 = x2; c.w = w_packed; c.bias = bias; c.vbias = view_bias; c.res = residual; c.y = y; c.y2 = y2;
-        c.S = S; c.Cin = Cin; c.Cout = Cout; c.C1 = C1; c.C1o = C1o; c.HW = H * W; c.hwsh = 2 * lw; c.npx = S * H * W;
-        c.nct = a.CoutP / TCO;
-        static const bool off = getenv("VF_CONV1X1_OLD") != nullptr;       // (tuning aid: the generic kernel)
-        if (!off && vfi_conv1x1_supported(c)) return vfi_conv1x1_launch(c, st);
+        return vfi_conv1x1_launch(c, st);
     }
 #define VF_CASE(KS_, LW_, M_) \
-    if (KS == KS_ && lw == LW_ && mode == M_) return launch_conv<KS_, LW_, M_>(a, st, ws_floats);
+    if (KS == KS_ && lw == LW_ && mode == M_) return launch_conv<KS_, LW_, M_>(a, st, p);
     VF_CASE(3, 3, 0) VF_CASE(3, 4, 0) VF_CASE(3, 5, 0) VF_CASE(3, 6, 0) VF_CASE(3, 7, 0)
     VF_CASE(3, 3, 1) VF_CASE(3, 4, 1) VF_CASE(3, 5, 1) VF_CASE(3, 6, 1)
     VF_CASE(3, 4, 2) VF_CASE(3, 5, 2) VF_CASE(3, 6, 2) VF_CASE(3, 7, 2)
@@ -1282,6 +1341,26 @@ long vf_conv_fwd_ws_floats(int S, int Cin, int Cout, int H, int W, int KS) {
     const int nch = round_up(Cin, KS == 3 ? 8 : 32) / (KS == 3 ? 8 : 32);
     const int ks = choose_ksplit((int)nblk_min, nch);
     return ks > 1 ? (long)ks * S * Cout * H * W : 0;
+}
+
+// The plan vf_conv_fwd / vf_conv_fwd_gn (gn_groups > 0) / vf_conv1x1_cat_fwd (0 < C1 < Cin) / vf_conv1x1_cat_dgrad
+// (0 < C1o < Cout) take for these arguments: host only, touches no device, launches nothing.  The launchers run the very
+// function that fills `out` = {route (0 conv_mfma_kernel, 1 conv1x1_kernel<1>, 2 conv1x1_kernel<2>, 3 conv_any_kernel),
+// npt (64-pixel units per tile), nblk (workgroups per K split), ks (K splits after the workspace clamp), safe
+// (unconditional loads), what follows the conv (0 nothing, 1 split-K reduce, 2 reduce + GroupNorm in one launch, 3 a
+// GroupNorm launch, 4 split-K reduce then a GroupNorm launch), NV, NT (the reduce + GroupNorm variant, else 0)}.
+int vf_conv_fwd_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, int C1, int C1o, int gn_groups, int has_ws,
+                     long ws_floats, int* out) {
+    if (!out || S <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0) return (int)hipErrorInvalidValue;
+    const bool cat = C1 > 0 && C1 < Cin, split = C1o > 0 && C1o < Cout, gn = gn_groups > 0;
+    if (!conv_fwd_args_ok(Cin, Cout, KS, mode, cat, C1, split, C1o, gn, gn_groups)) return (int)hipErrorInvalidValue;
+    if (mode != 0 && mode != 1 && mode != 2 && mode != 4) return (int)hipErrorInvalidValue;
+    if (!fwd_specialised(KS, H, W, mode) && mode == 2 && ((H & 1) || (W & 1))) return (int)hipErrorInvalidValue;
+    const ConvFwdPlan p = conv_fwd_plan(S, Cin, Cout, H, W, KS, mode, cat, C1, split, C1o, gn, gn_groups, has_ws != 0,
+                                        ws_floats);
+    const int v[8] = {p.route, p.npt, p.nblk, p.ks, p.safe, p.reduce, p.nv, p.nt};
+    memcpy(out, v, sizeof v);
+    return 0;
 }
 
 // Workspace floats needed by vf_conv_wgrad for the preferred split (a smaller workspace is

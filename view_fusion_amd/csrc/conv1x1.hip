@@ -184,8 +184,10 @@ __global__ __launch_bounds__(256 * NCW, 4) void conv1x1_kernel(C11Args a) {
         if (a.res) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
+                // (a 32-channel block that lies wholly past Cout -- Cout % 64 <= 32 -- has a NEGATIVE dco: it steps back from
+                // ob to channel Cout - 1; clamping it to 0 would read past the last view's end)
                 const int dco = min((r & 3) + 8 * (r >> 2), a.Cout - 1 - cob - cb * 32);
-                add[r] = a.res[ob + (size_t)max(dco, 0) * a.HW];
+                add[r] = a.res[(ptrdiff_t)ob + (ptrdiff_t)dco * a.HW];
             }
         }
         if (a.bias) {
@@ -256,10 +258,17 @@ int vfi_conv1x1_halves(const C11Args& a) {
     return 0;
 }
 
-int vfi_conv1x1_launch(const C11Args& a, hipStream_t st) {
-    const int halves = vfi_conv1x1_halves(a) == 1 ? 1 : 2;
+// the launch of a supported shape: *halves = 64-channel halves per workgroup (1 | 2); returns the workgroup count
+unsigned vfi_conv1x1_grid(const C11Args& a, int* halves) {
+    *halves = vfi_conv1x1_halves(a) == 1 ? 1 : 2;
     const unsigned ptiles = (unsigned)((a.npx + 127) / 128);
-    if (halves == 2) hipLaunchKernelGGL(conv1x1_kernel<2>, dim3(ptiles * (unsigned)((a.nct + 1) / 2)), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL(conv1x1_kernel<1>, dim3(ptiles * (unsigned)a.nct), dim3(256), 0, st, a);
+    return ptiles * (unsigned)(*halves == 2 ? (a.nct + 1) / 2 : a.nct);
+}
+
+int vfi_conv1x1_launch(const C11Args& a, hipStream_t st) {
+    int halves;
+    const unsigned nblk = vfi_conv1x1_grid(a, &halves);
+    if (halves == 2) hipLaunchKernelGGL(conv1x1_kernel<2>, dim3(nblk), dim3(512), 0, st, a);
+    else hipLaunchKernelGGL(conv1x1_kernel<1>, dim3(nblk), dim3(256), 0, st, a);
     VF_RETURN_LAST_ERROR();
 }

@@ -424,6 +424,18 @@ long vfi_conv_any_fwd_ws_floats(int S, int Cin, int Cout, int H, int W, int KS) 
     return p.ks > 1 ? (long)p.ks * S * Cout * H * W : 0;
 }
 
+// The launch plan of vfi_conv_any_fwd, host only: out = {npt, nblk, ks after the workspace clamp}.  split_out: the output is
+// split over two tensors (the reduce writes one destination); mode 4 ignores the workspace.
+void vfi_conv_any_fwd_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, bool split_out, bool has_ws,
+                           long ws_floats, int out[3]) {
+    const FwdPlan p = fwd_plan(S, Cin, Cout, H, W, KS);
+    const size_t out_floats = (size_t)S * Cout * H * W;
+    int ks = p.ks;
+    if (!has_ws || split_out || mode == 4) ks = 1;
+    while (ks > 1 && (size_t)ks * out_floats > (size_t)ws_floats) --ks;
+    out[0] = p.npt; out[1] = p.nblk; out[2] = ks;
+}
+
 int vfi_conv_any_fwd(const float* x, const float* x2, int C1, const float* w_packed, const float* bias,
                      const float* view_bias, const float* residual, float* y, float* y2, int C1o, float* ws, long ws_floats,
                      int S, int Cin, int Cout, int H, int W, int KS, int mode, hipStream_t st) {
@@ -441,11 +453,11 @@ int vfi_conv_any_fwd(const float* x, const float* x2, int C1, const float* w_pac
     a.SH = mode == 1 ? 2 * H : (mode == 2 ? H / 2 : H);
     a.SW = mode == 1 ? 2 * W : (mode == 2 ? W / 2 : W);
     a.npix = S * H * W;
-    const FwdPlan p = fwd_plan(S, Cin, Cout, H, W, KS);
     const size_t out_floats = (size_t)S * Cout * H * W;
-    int ks = p.ks;
-    if (!ws || y2 || mode == 4) ks = 1;                  // (the reduce writes one destination; mode 4 has no workspace)
-    while (ks > 1 && (size_t)ks * out_floats > (size_t)ws_floats) --ks;
+    int plan[3];
+    vfi_conv_any_fwd_plan(S, Cin, Cout, H, W, KS, mode, y2 != nullptr, ws != nullptr, ws_floats, plan);
+    const FwdPlan p{plan[0], plan[1], plan[2]};
+    const int ks = p.ks;
     a.ksplit = ks;
     a.ws = ws;
 #define VF_ANY(KS_, M_) \
