@@ -1,6 +1,6 @@
 """Loss-aware noise-level sampling on the GPU (ops.draw_level / level_stats / compose_loss(sample_scale=),
-ViewFusion.set_level_sampler, train.Trainer; draw_level_kernel, level_stats_kernel and compose_loss_finish_scaled_kernel of
-csrc/diffusion.hip, specification in csrc/level_sampler.h), against tests/level_sampler_ref.py:
+ViewFusion.set_level_sampler, train.Trainer; draw_level_kernel, level_stats_kernel and compose_loss_finish_kernel's scale
+of csrc/diffusion.hip, specification in csrc/level_sampler.h), against tests/level_sampler_ref.py:
 
   1. the draw kernel, bitwise in t / u / iw, seeded and from words, B = 1000, skewed tables at (T, K) = (20, 4), (2000, 64);
   2. the statistics + table kernel: B = 70 samples (more than the 64 threads of the finish kernel it follows), K = 100

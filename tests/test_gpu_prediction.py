@@ -1,5 +1,5 @@
 """v- and x0-prediction on the GPU (ViewFusion.set_prediction, ops.compose_loss(prediction=, y_0=); the
-compose_loss_pred_fwd / _finish_pred / _pred_bwd kernels of csrc/diffusion.hip; definition at the head of that file,
+compose_loss_fwd / _finish / _bwd kernels of csrc/diffusion.hip under PRED = v | x0; definition at the head of that file,
 weights in csrc/loss_weight.h) against the float64 restatement tests/prediction_ref.py.
 
   1. loss and d unet_out against float64: "v" and "x0" x every penalty x every weighting, softmax and mean, at the shapes

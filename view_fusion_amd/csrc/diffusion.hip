@@ -13,10 +13,20 @@
 //   composition     compose4 (softmax over the views, or the mean), guide4, write_weights (the softmax weights handed
 //                   back by the tails; compose_fwd_kernel and compose_eps_kernel keep that loop written out, for the
 //                   same reason).
-//   training loss   compose_fwd / loss_finish / compose_mse_bwd: the MSE pair of the benchmarked step; further down their
-//                   siblings compose_loss_fwd / _finish / _bwd<PEN> with a penalty (mse / l1 / huber), a per-sample
-//                   noise-level weight (min-SNR, P2), the per-sample loss and a loss-by-level histogram -- same launch
-//                   count, no atomics; loss_weight.h holds the specification.
+//   training loss   compose_fwd / loss_finish / compose_mse_bwd: the MSE pair of the benchmarked step.  It stands apart from
+//                   the family below on purpose: with the chain-rule block of compose_mse_bwd_kernel in a __device__
+//                   function shared with the family, that kernel's code changes (SGPR 47 -> 45, s_add_u32 / s_addc_u32
+//                   4 -> 3: scalar address arithmetic associated differently; profiles/loss_templates.md), and the three
+//                   kernels of the benchmarked step keep their code.
+//   the loss family pred_target4, compose_loss_fwd_kernel<PEN, PRED> -> compose_loss_finish_kernel, and
+//                   compose_loss_bwd_kernel<PEN, PRED>: every other objective.  PEN: the penalty (mse / l1 / huber);
+//                   PRED: what channels 0..2 mean -- eps (the target handed over ready-made), v, x0 (the target formed in
+//                   registers from noise, y_0 and level); nine instantiations of each.  The finish kernel takes the
+//                   prediction's native noise-level weight (none / min-SNR / P2 / truncated SNR) at run time, an optional
+//                   per-sample scale (the importance weight of a level-sampler draw), and writes the per-sample loss and an
+//                   optional loss-by-level histogram.  Same launch count as the MSE pair, no atomics; loss_weight.h holds
+//                   the specification.  The tails have no such switch: another parameterisation is another (a, b) table
+//                   pair.
 //   step arithmetic y0_hat, y0_hat_as, posterior_update, multistep_base / _add: how each product and sum of a reverse
 //                   step is rounded, and why it is written operation by operation; EpsBound / EpsBuffer: what a tail on
 //                   the eps buffer knows about its sample.
@@ -28,18 +38,17 @@
 //                   per-sample id) instead of loaded.  Six instantiations of each.  In front of them the two noise sources
 //                   (load_z, draw_z) and the common prologue (tail_sample, tail_eps).
 //   draws, metrics  draw_train, randn_ids, philox_ids (rng.h), gather_level, psnr.
-//   level sampling  compose_loss_finish_scaled_kernel, draw_level_kernel, level_stats_kernel: importance-sampled timesteps
-//                   from a proposal table the loss statistics rebuild on the device (level_sampler.h).
+//   level sampling  draw_level_kernel, level_stats_kernel: importance-sampled timesteps from a proposal table the loss
+//                   statistics rebuild on the device (level_sampler.h); the draw's weight is the loss family's scale.
 //   three launches  compose_eps_kernel<CFG, FUSED_TAIL> -> sample_stat_kernel (abs_select, quantile_lerp; the same
 //                   selection on a plain buffer: abs_quantile_kernel) -> an EPS tail: the thresholded / rescaled step.
-//   prediction      pred_target4, compose_loss_pred_fwd / _finish_pred / _pred_bwd<PEN, PRED>: the loss-option kernels for
-//                   v- and x0-prediction, the target formed in registers from noise, y_0 and level (same launch count).
-//                   The tails have no sibling: another parameterisation is another (a, b) table pair.
 //   distillation    distill_begin_kernel (the draw of i, z_t) and distill_target_kernel<CFG> (the second teacher step's tail:
 //                   x2, x~, eps~), siblings of draw_train / stack_views and of sampler_step_kernel.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
-//                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.
+//                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The five
+//                   vf_compose_loss_* entries likewise forward to loss_fwd / loss_bwd; loss_kernels turns the run-time
+//                   (penalty, pred) into the instantiation.
 // With every option off a path runs the launches and the bits it ran before the option existed.
 //
 // Classifier-free guidance (Ho & Salimans, "Classifier-Free Diffusion Guidance").  This comment is the ONE written
@@ -87,7 +96,8 @@
 //
 // Prediction: what channels 0..2 of the network mean (Salimans & Ho, "Progressive Distillation", v; Hang et al., Min-SNR,
 // the weights).  This comment is the ONE written definition (the weights: loss_weight.h); tests/prediction_ref.py
-// restates it.  Opt-in: "eps" runs the launches and the bits of before.
+// restates it.  One switch (PRED) of the loss family: "eps" is handed its target ready-made and computes the bits it
+// computed before the switch existed.
 //   g = the level the network is conditioned on: the sample's continuous `level` in training, gammas[t] / gammas[tau[k]]
 //   in sampling.  y_t = sqrt(g) y_0 + sqrt(1 - g) noise as before.  `out` = the composition over the sample's views of
 //   channels 0..2 (softmax of channels 3..5, or the mean), unchanged: the weights sum to 1 and everything below is affine
@@ -735,12 +745,34 @@ __global__ __launch_bounds__(256) void psnr_kernel(const float* __restrict__ a, 
     if (threadIdx.x == 0) out[blockIdx.x] = 20.0f * log10f(1.0f / sqrtf(s / (float)n));
 }
 
-// ---- loss options: penalty x noise-level weight, per-sample loss, loss-by-level histogram (loss_weight.h) ----
-// compose_fwd_kernel's sibling: the same noise_hat and the same (b, chunk) partial sums, of rho(noise_hat - target).
-template <int PEN>
+// ---- the loss family: penalty x prediction x noise-level weight, per-sample loss and scale, loss-by-level histogram
+// (loss_weight.h, level_sampler.h; the head of this file holds the table of targets) ----
+// The training target of one element:
+//   eps the ready-made target handed over as `noise` (y_0 and level are not read);
+//   v   sa noise - sb y_0 with sa = sqrtf(g_b), sb = sqrtf(1 - g_b), formed in registers from the noise and y_0 the step
+//       already holds: sb y_0 is rounded, the rest is one fused multiply-add, written out so that the forward and the
+//       backward kernel form the very same bits;
+//   x0  y_0 itself (the noise is not read).
+template <int PRED>
+__device__ __forceinline__ float4 pred_target4(const float* __restrict__ noise, const float* __restrict__ y_0, size_t o,
+                                               float sa, float sb) {
+    if (PRED == VF_PRED_EPS) return *reinterpret_cast<const float4*>(noise + o);
+    const float4 y = *reinterpret_cast<const float4*>(y_0 + o);
+    if (PRED == VF_PRED_X0) return y;
+    const float4 n = *reinterpret_cast<const float4*>(noise + o);
+    return make_float4(__builtin_fmaf(sa, n.x, -mul_rn(sb, y.x)), __builtin_fmaf(sa, n.y, -mul_rn(sb, y.y)),
+                       __builtin_fmaf(sa, n.z, -mul_rn(sb, y.z)), __builtin_fmaf(sa, n.w, -mul_rn(sb, y.w)));
+}
+
+// compose_fwd_kernel with a penalty and a prediction: the same composition and the same (b, chunk) partial sums, of
+// rho(noise_hat - target).  noise_hat receives the composed output in the network's own parameterisation (what the
+// backward kernel reads back).
+template <int PEN, int PRED>
 __global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __restrict__ out,
                                                                const int* __restrict__ off,
-                                                               const float* __restrict__ target,
+                                                               const float* __restrict__ noise,
+                                                               const float* __restrict__ y_0,
+                                                               const float* __restrict__ level,
                                                                float* __restrict__ noise_hat,
                                                                float* __restrict__ loss_part, int Cout, int HW,
                                                                int weighting, float delta) {
@@ -748,13 +780,18 @@ __global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __re
     const int b = blockIdx.y;
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
+    float sa = 0.f, sb = 0.f;
+    if (PRED != VF_PRED_EPS) {
+        const float g = level[b];
+        sa = sqrtf(g), sb = sqrtf(1.0f - g);
+    }
     float acc = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
         *reinterpret_cast<float4*>(noise_hat + o) = nh;
-        const float4 t = *reinterpret_cast<const float4*>(target + o);
+        const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
         acc += (vf_loss_rho<PEN>(nh.x - t.x, delta) + vf_loss_rho<PEN>(nh.y - t.y, delta)) +
                (vf_loss_rho<PEN>(nh.z - t.z, delta) + vf_loss_rho<PEN>(nh.w - t.w, delta));
     }
@@ -762,22 +799,32 @@ __global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __re
     if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
-// One workgroup.  Per sample (one thread each): s_b = its `ch` partials in index order / n, w_b = the weight of its
-// level; then loss = sum_b w_b s_b / B in index order (one thread); then, with a histogram attached, one thread per bin
-// walks the samples in index order and adds the UNWEIGHTED s_b of its own bin into the persistent accumulators.  Every
-// address is written by exactly one thread: no atomics, the same bits on every run.
+// One workgroup.  Per sample (one thread each): s_b = its `ch` partials in index order / n, w_b = the native weight of
+// its level for the prediction (vf_loss_weight_pred; pred 0 is vf_loss_weight); then loss = sum_b sample_w[b] s_b / B in
+// index order (one thread); then, with a histogram attached, one thread per bin walks the samples in index order and adds
+// the UNWEIGHTED s_b of its own bin into the persistent accumulators.  scale (nullable; the importance weight of a
+// level-sampler draw): with it sample_w holds 2 B floats -- w_s scale[s], what the loss and the backward kernel use, then
+// w_s alone, what level_stats_kernel reads; without, B floats.  Every address is written by exactly one thread: no
+// atomics, the same bits on every run.
 __global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __restrict__ part,
                                                                  const float* __restrict__ level,
+                                                                 const float* __restrict__ scale,
                                                                  float* __restrict__ sample_loss,
                                                                  float* __restrict__ sample_w, float* __restrict__ loss,
                                                                  float* __restrict__ bin_sum, int* __restrict__ bin_cnt,
                                                                  int B, int ch, int K, float inv_n, int kind, float a,
-                                                                 float b) {
+                                                                 float b, int pred) {
     for (int s = threadIdx.x; s < B; s += 64) {
         float acc = 0.f;
         for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
         sample_loss[s] = acc * inv_n;
-        sample_w[s] = vf_loss_weight(kind, a, b, level[s]);
+        const float w = vf_loss_weight_pred(pred, kind, a, b, level[s]);
+        if (scale != nullptr) {
+            sample_w[s] = w * scale[s];
+            sample_w[B + s] = w;
+        } else {
+            sample_w[s] = w;
+        }
     }
     __syncthreads();                        // (also makes the workgroup's global stores above visible to it)
     if (threadIdx.x == 0) {
@@ -802,12 +849,15 @@ __global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __
     }
 }
 
-// compose_mse_bwd_kernel's sibling: g = gloss w_b rho'(noise_hat - target) / (n B), then the same softmax / mean
-// chain rule (d eps_v = w_v g;  d logit_v = w_v (eps_v - nh) g;  mean ablation: d eps_v = g / count, logits zero).
-template <int PEN>
+// compose_mse_bwd_kernel with a penalty and a prediction: the forward kernel's target formed again, g = gloss
+// sample_w[b] rho'(noise_hat - target) / (n B), then the same softmax / mean chain rule (d eps_v = w_v g;
+// d logit_v = w_v (eps_v - nh) g;  mean ablation: d eps_v = g / count, logits zero).
+template <int PEN, int PRED>
 __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __restrict__ out,
                                                                const int* __restrict__ off,
-                                                               const float* __restrict__ target,
+                                                               const float* __restrict__ noise,
+                                                               const float* __restrict__ y_0,
+                                                               const float* __restrict__ level,
                                                                const float* __restrict__ noise_hat,
                                                                const float* __restrict__ gloss,
                                                                const float* __restrict__ sample_w,
@@ -817,12 +867,17 @@ __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __re
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
     const float gs = gloss[0] * sample_w[b] * inv_nb;
+    float sa = 0.f, sb = 0.f;
+    if (PRED != VF_PRED_EPS) {
+        const float lv = level[b];
+        sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    }
     const size_t vs = (size_t)Cout * HW;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
         const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
-        const float4 t = *reinterpret_cast<const float4*>(target + o);
+        const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
         const float4 g = make_float4(gs * vf_loss_drho<PEN>(nh.x - t.x, delta), gs * vf_loss_drho<PEN>(nh.y - t.y, delta),
                                      gs * vf_loss_drho<PEN>(nh.z - t.z, delta), gs * vf_loss_drho<PEN>(nh.w - t.w, delta));
         if (!weighting) {
@@ -854,49 +909,6 @@ __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __re
 }
 
 // ---- loss-aware noise-level sampling (level_sampler.h holds the specification) ----
-// compose_loss_finish_kernel with a per-sample scale (the importance weight of the draw): sample_w[s] = w_s scale[s] is
-// what the loss and the backward kernel use, sample_w[B + s] = w_s alone is what level_stats_kernel reads; sample_loss
-// and the histogram stay unweighted.  A sibling written out, not a shared body: the kernel above keeps its code.
-__global__ __launch_bounds__(64) void compose_loss_finish_scaled_kernel(const float* __restrict__ part,
-                                                                        const float* __restrict__ level,
-                                                                        const float* __restrict__ scale,
-                                                                        float* __restrict__ sample_loss,
-                                                                        float* __restrict__ sample_w,
-                                                                        float* __restrict__ loss,
-                                                                        float* __restrict__ bin_sum,
-                                                                        int* __restrict__ bin_cnt, int B, int ch, int K,
-                                                                        float inv_n, int kind, float a, float b) {
-    for (int s = threadIdx.x; s < B; s += 64) {
-        float acc = 0.f;
-        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
-        sample_loss[s] = acc * inv_n;
-        const float w = vf_loss_weight(kind, a, b, level[s]);
-        sample_w[s] = w * scale[s];
-        sample_w[B + s] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float acc = 0.f;
-        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
-        *loss = acc / (float)B;
-    }
-    if (bin_sum == nullptr) return;
-    for (int k = threadIdx.x; k < K; k += 64) {
-        float sum = 0.f;
-        int cnt = 0;
-        for (int s = 0; s < B; ++s) {
-            int bin = (int)(level[s] * (float)K);
-            bin = bin > K - 1 ? K - 1 : bin;
-            if (bin == k) {
-                sum += sample_loss[s];
-                ++cnt;
-            }
-        }
-        bin_sum[k] += sum;
-        bin_cnt[k] += cnt;
-    }
-}
-
 // draw_train_kernel's sibling: t from the proposal table (c [K + 1], iw [K], *ready in device memory) instead of the
 // uniform map, and the draw's importance weight.  The word is word 0 of the sample's training-scalars call (ids != null)
 // or words[b] (the unseeded path: int64 values in [0, 2^32)); u / level (seeded only, both optional) as draw_train_kernel.
@@ -1248,185 +1260,6 @@ int sampler_step(const float* unet_out, const int* off, const float* eps, const 
     VF_RETURN_LAST_ERROR();
 }
 
-// ---- prediction: v- and x0-prediction losses (the head of this file; loss_weight.h holds the weights) ----
-// The training target of one element, formed in registers from the noise and y_0 the step already holds:
-//   v   sa noise - sb y_0 with sa = sqrtf(g_b), sb = sqrtf(1 - g_b): sb y_0 is rounded, the rest is one fused multiply-add,
-//       written out so that the forward and the backward kernel form the very same bits;
-//   x0  y_0 itself (the noise is not read).
-template <int PRED>
-__device__ __forceinline__ float4 pred_target4(const float* __restrict__ noise, const float* __restrict__ y_0, size_t o,
-                                               float sa, float sb) {
-    const float4 y = *reinterpret_cast<const float4*>(y_0 + o);
-    if (PRED == VF_PRED_X0) return y;
-    const float4 n = *reinterpret_cast<const float4*>(noise + o);
-    return make_float4(__builtin_fmaf(sa, n.x, -mul_rn(sb, y.x)), __builtin_fmaf(sa, n.y, -mul_rn(sb, y.y)),
-                       __builtin_fmaf(sa, n.z, -mul_rn(sb, y.z)), __builtin_fmaf(sa, n.w, -mul_rn(sb, y.w)));
-}
-
-// compose_loss_fwd_kernel's sibling: noise, y_0 and level in place of a ready-made target.  noise_hat receives the
-// composed output in the network's own parameterisation (what the backward kernel reads back).
-template <int PEN, int PRED>
-__global__ __launch_bounds__(256) void compose_loss_pred_fwd_kernel(const float* __restrict__ out,
-                                                                    const int* __restrict__ off,
-                                                                    const float* __restrict__ noise,
-                                                                    const float* __restrict__ y_0,
-                                                                    const float* __restrict__ level,
-                                                                    float* __restrict__ noise_hat,
-                                                                    float* __restrict__ loss_part, int Cout, int HW,
-                                                                    int weighting, float delta) {
-    __shared__ float red[4];
-    const int b = blockIdx.y;
-    const int v0 = off[b], v1 = off[b + 1];
-    const int n4 = 3 * HW / 4;
-    const float g = level[b];
-    const float sa = sqrtf(g), sb = sqrtf(1.0f - g);
-    float acc = 0.f;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
-        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
-        *reinterpret_cast<float4*>(noise_hat + o) = nh;
-        const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
-        acc += (vf_loss_rho<PEN>(nh.x - t.x, delta) + vf_loss_rho<PEN>(nh.y - t.y, delta)) +
-               (vf_loss_rho<PEN>(nh.z - t.z, delta) + vf_loss_rho<PEN>(nh.w - t.w, delta));
-    }
-    acc = block_sum<256>(acc, red);
-    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
-}
-
-// compose_loss_finish_kernel / _scaled_kernel with the native weight of the prediction (vf_loss_weight_pred).  scale
-// (nullable): with it sample_w holds 2 B floats, w_s scale[s] then w_s alone, as the scaled kernel writes them; without,
-// B floats.  One workgroup, every address written by one thread, sums in index order.
-__global__ __launch_bounds__(64) void compose_loss_finish_pred_kernel(const float* __restrict__ part,
-                                                                      const float* __restrict__ level,
-                                                                      const float* __restrict__ scale,
-                                                                      float* __restrict__ sample_loss,
-                                                                      float* __restrict__ sample_w,
-                                                                      float* __restrict__ loss,
-                                                                      float* __restrict__ bin_sum,
-                                                                      int* __restrict__ bin_cnt, int B, int ch, int K,
-                                                                      float inv_n, int kind, float a, float b, int pred) {
-    for (int s = threadIdx.x; s < B; s += 64) {
-        float acc = 0.f;
-        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
-        sample_loss[s] = acc * inv_n;
-        const float w = vf_loss_weight_pred(pred, kind, a, b, level[s]);
-        if (scale != nullptr) {
-            sample_w[s] = w * scale[s];
-            sample_w[B + s] = w;
-        } else {
-            sample_w[s] = w;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float acc = 0.f;
-        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
-        *loss = acc / (float)B;
-    }
-    if (bin_sum == nullptr) return;
-    for (int k = threadIdx.x; k < K; k += 64) {
-        float sum = 0.f;
-        int cnt = 0;
-        for (int s = 0; s < B; ++s) {
-            int bin = (int)(level[s] * (float)K);
-            bin = bin > K - 1 ? K - 1 : bin;
-            if (bin == k) {
-                sum += sample_loss[s];
-                ++cnt;
-            }
-        }
-        bin_sum[k] += sum;
-        bin_cnt[k] += cnt;
-    }
-}
-
-// compose_loss_bwd_kernel's sibling: the same target as the forward kernel, formed again, then the same chain rule.
-template <int PEN, int PRED>
-__global__ __launch_bounds__(256) void compose_loss_pred_bwd_kernel(const float* __restrict__ out,
-                                                                    const int* __restrict__ off,
-                                                                    const float* __restrict__ noise,
-                                                                    const float* __restrict__ y_0,
-                                                                    const float* __restrict__ level,
-                                                                    const float* __restrict__ noise_hat,
-                                                                    const float* __restrict__ gloss,
-                                                                    const float* __restrict__ sample_w,
-                                                                    float* __restrict__ dout, int Cout, int HW,
-                                                                    int weighting, float inv_nb, float delta) {
-    const int b = blockIdx.y;
-    const int v0 = off[b], v1 = off[b + 1];
-    const int n4 = 3 * HW / 4;
-    const float gs = gloss[0] * sample_w[b] * inv_nb;
-    const float lv = level[b];
-    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
-    const size_t vs = (size_t)Cout * HW;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
-        const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
-        const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
-        const float4 g = make_float4(gs * vf_loss_drho<PEN>(nh.x - t.x, delta), gs * vf_loss_drho<PEN>(nh.y - t.y, delta),
-                                     gs * vf_loss_drho<PEN>(nh.z - t.z, delta), gs * vf_loss_drho<PEN>(nh.w - t.w, delta));
-        if (!weighting) {
-            const float inv = 1.0f / (float)(v1 - v0);
-            const float4 d = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
-            for (int v = v0; v < v1; ++v) {
-                *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)c * HW + p) = d;
-                if (Cout > 3)
-                    *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)(3 + c) * HW + p) =
-                        make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-            continue;
-        }
-        float4 mx, inv;
-        (void)compose4(out, Cout, HW, v0, v1, c, p, 1, &mx, &inv);
-        for (int v = v0; v < v1; ++v) {
-            const float* ep = out + (size_t)v * vs + (size_t)c * HW + p;
-            const float4 e = *reinterpret_cast<const float4*>(ep);
-            const float4 l = *reinterpret_cast<const float4*>(ep + (size_t)3 * HW);
-            const float4 w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
-                                         expf(l.w - mx.w) * inv.w);
-            float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
-            *reinterpret_cast<float4*>(dp) = make_float4(w.x * g.x, w.y * g.y, w.z * g.z, w.w * g.w);
-            *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
-                make_float4(w.x * (e.x - nh.x) * g.x, w.y * (e.y - nh.y) * g.y, w.z * (e.z - nh.z) * g.z,
-                            w.w * (e.w - nh.w) * g.w);
-        }
-    }
-}
-
-template <int PRED>
-void launch_pred_fwd(dim3 grid, hipStream_t st, int penalty, const float* out, const int* off, const float* noise,
-                     const float* y_0, const float* level, float* noise_hat, float* loss_part, int Cout, int HW,
-                     int weighting, float delta) {
-    const dim3 block(256);
-    if (penalty == VF_LOSS_L1)
-        hipLaunchKernelGGL((compose_loss_pred_fwd_kernel<VF_LOSS_L1, PRED>), grid, block, 0, st, out, off, noise, y_0, level,
-                           noise_hat, loss_part, Cout, HW, weighting, delta);
-    else if (penalty == VF_LOSS_HUBER)
-        hipLaunchKernelGGL((compose_loss_pred_fwd_kernel<VF_LOSS_HUBER, PRED>), grid, block, 0, st, out, off, noise, y_0,
-                           level, noise_hat, loss_part, Cout, HW, weighting, delta);
-    else
-        hipLaunchKernelGGL((compose_loss_pred_fwd_kernel<VF_LOSS_MSE, PRED>), grid, block, 0, st, out, off, noise, y_0,
-                           level, noise_hat, loss_part, Cout, HW, weighting, delta);
-}
-
-template <int PRED>
-void launch_pred_bwd(dim3 grid, hipStream_t st, int penalty, const float* out, const int* off, const float* noise,
-                     const float* y_0, const float* level, const float* noise_hat, const float* gloss,
-                     const float* sample_w, float* dout, int Cout, int HW, int weighting, float inv_nb, float delta) {
-    const dim3 block(256);
-    if (penalty == VF_LOSS_L1)
-        hipLaunchKernelGGL((compose_loss_pred_bwd_kernel<VF_LOSS_L1, PRED>), grid, block, 0, st, out, off, noise, y_0, level,
-                           noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
-    else if (penalty == VF_LOSS_HUBER)
-        hipLaunchKernelGGL((compose_loss_pred_bwd_kernel<VF_LOSS_HUBER, PRED>), grid, block, 0, st, out, off, noise, y_0,
-                           level, noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
-    else
-        hipLaunchKernelGGL((compose_loss_pred_bwd_kernel<VF_LOSS_MSE, PRED>), grid, block, 0, st, out, off, noise, y_0,
-                           level, noise_hat, gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
-}
-
 // ---- progressive distillation (the head of this file) ----
 // The student step of sample b, its two teacher steps and its level, and z_t.  grid (chunks, B); i_in (int64 [B] | null):
 // an injected i, clamped to 0..K-1; else i = mulhi32(word 0 of the training-scalars call, K).  z_t is stack_views_kernel's
@@ -1510,6 +1343,28 @@ __global__ __launch_bounds__(256) void distill_target_kernel(
     }
 }
 
+// ---- the loss family: the run-time (penalty, pred) -> the kernel pair (the launchers stand with the entry points) ----
+struct LossKernels {
+    decltype(&compose_loss_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) fwd;
+    decltype(&compose_loss_bwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) bwd;
+};
+
+template <int PRED>
+LossKernels loss_kernels_of(int penalty) {
+    if (penalty == VF_LOSS_L1)
+        return {compose_loss_fwd_kernel<VF_LOSS_L1, PRED>, compose_loss_bwd_kernel<VF_LOSS_L1, PRED>};
+    if (penalty == VF_LOSS_HUBER)
+        return {compose_loss_fwd_kernel<VF_LOSS_HUBER, PRED>, compose_loss_bwd_kernel<VF_LOSS_HUBER, PRED>};
+    return {compose_loss_fwd_kernel<VF_LOSS_MSE, PRED>, compose_loss_bwd_kernel<VF_LOSS_MSE, PRED>};
+}
+
+// the run-time (penalty, pred) -> the instantiation: the one place that names the nine of each
+LossKernels loss_kernels(int penalty, int pred) {
+    if (pred == VF_PRED_V) return loss_kernels_of<VF_PRED_V>(penalty);
+    if (pred == VF_PRED_X0) return loss_kernels_of<VF_PRED_X0>(penalty);
+    return loss_kernels_of<VF_PRED_EPS>(penalty);
+}
+
 }  // namespace
 
 extern "C" {
@@ -1567,93 +1422,107 @@ int vf_compose_mse_bwd(const float* unet_out, const int* off, const float* targe
     VF_RETURN_LAST_ERROR();
 }
 
-// ---- loss options (loss_weight.h): vf_compose_fwd with a target / vf_compose_mse_bwd with a penalty, a per-sample
-// weight of `level`, the per-sample loss and an optional histogram.  Two launches forward, one backward, as those. ----
-static inline bool loss_args_ok(int B, int Cout, int HW, int weighting, int penalty, float delta) {
+// ---- the loss family (loss_weight.h): vf_compose_fwd with a target / vf_compose_mse_bwd with a penalty, a prediction, a
+// per-sample weight of `level` (times a per-sample scale), the per-sample loss and an optional histogram.  Two launches
+// forward, one backward, as those.  Five entry points in front of one forward and one backward launcher:
+//   vf_compose_loss_fwd          eps, the target ready-made;
+//   vf_compose_loss_fwd_scaled   + scale (DEVICE float [B], the importance weight of level_sampler.h): sample_w then holds
+//                                2 B floats, w_b scale_b (what the loss and the backward use) and then w_b alone;
+//                                scale == NULL is vf_compose_loss_fwd itself;
+//   vf_compose_loss_bwd          eps;
+//   vf_compose_loss_pred_fwd / _pred_bwd   pred 1 (v) | 2 (x0), fed noise, y_0 and level instead of a target; scale
+//                                (nullable) as above; noise may be NULL for x0; pred 0 (eps) is refused: its path is the
+//                                entries above.
+// What an entry refuses is what it always refused, which is not the same for every entry.  All: B <= 0 returns 0 without a
+// launch; HW & 3, Cout < 3, weighting with Cout < 6, an unknown penalty, huber with delta <= 0; a null sample_w.  The three
+// forward entries: an unknown weight_kind, bin_sum without bin_cnt or the reverse, bins with K < 1, a null level, noise_hat,
+// loss_part, sample_loss or loss.  The eps forward entries: a null target.  The pred entries: pred other than 1 | 2, a null
+// y_0, a null noise for v; vf_compose_loss_pred_bwd alone also a null level, noise_hat, gloss or dout --
+// vf_compose_loss_bwd looks at no pointer but sample_w. ----
+static inline bool loss_args_ok(int Cout, int HW, int weighting, int penalty, float delta) {
     if ((HW & 3) || Cout < 3 || (weighting && Cout < 6)) return false;
     if (penalty < VF_LOSS_MSE || penalty > VF_LOSS_HUBER) return false;
     return penalty != VF_LOSS_HUBER || delta > 0.0f;
+}
+
+static inline bool pred_args_ok(int pred, const float* noise, const float* y_0) {
+    return (pred == VF_PRED_V || pred == VF_PRED_X0) && y_0 && (pred == VF_PRED_X0 || noise);
+}
+
+// noise: the ready-made target for pred 0 (y_0 is then not read).
+static int loss_fwd(int pred, const float* unet_out, const int* off, const float* noise, const float* y_0,
+                    const float* level, const float* scale, float* noise_hat, float* loss_part, float* sample_loss,
+                    float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B, int Cout, int HW, int weighting,
+                    int penalty, float delta, int weight_kind, float a, float b, int K, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
+    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
+    if (!level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss) return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = chunks_for(3 * HW / 4);
+    hipLaunchKernelGGL(loss_kernels(penalty, pred).fwd, dim3(ch, B), dim3(256), 0, st, unet_out, off, noise, y_0, level,
+                       noise_hat, loss_part, Cout, HW, weighting, delta);
+    hipLaunchKernelGGL(compose_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
+                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b, pred);
+    VF_RETURN_LAST_ERROR();
+}
+
+static int loss_bwd(int pred, const float* unet_out, const int* off, const float* noise, const float* y_0,
+                    const float* level, const float* noise_hat, const float* gloss, const float* sample_w, float* dout,
+                    int B, int Cout, int HW, int weighting, int penalty, float delta, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(Cout, HW, weighting, penalty, delta) || !sample_w) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(loss_kernels(penalty, pred).bwd, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout, Cout, HW,
+                       weighting, 1.0f / ((float)B * 3.0f * (float)HW), delta);
+    VF_RETURN_LAST_ERROR();
 }
 
 int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* target, const float* level,
                         float* noise_hat, float* loss_part, float* sample_loss, float* sample_w, float* loss,
                         float* bin_sum, int* bin_cnt, int B, int Cout, int HW, int weighting, int penalty, float delta,
                         int weight_kind, float a, float b, int K, void* stream) {
-    if (B <= 0) return 0;
-    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
-    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
-    if (!target || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
-        return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = chunks_for(3 * HW / 4);
-    const dim3 grid(ch, B), block(256);
-    if (penalty == VF_LOSS_L1)
-        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_L1>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           loss_part, Cout, HW, weighting, delta);
-    else if (penalty == VF_LOSS_HUBER)
-        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_HUBER>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           loss_part, Cout, HW, weighting, delta);
-    else
-        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           loss_part, Cout, HW, weighting, delta);
-    hipLaunchKernelGGL(compose_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_part, level, sample_loss, sample_w,
-                       loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b);
-    VF_RETURN_LAST_ERROR();
+    if (B > 0 && !target) return (int)hipErrorInvalidValue;
+    return loss_fwd(VF_PRED_EPS, unet_out, off, target, nullptr, level, nullptr, noise_hat, loss_part, sample_loss,
+                    sample_w, loss, bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream);
 }
 
-int vf_compose_loss_bwd(const float* unet_out, const int* off, const float* target, const float* noise_hat,
-                        const float* gloss, const float* sample_w, float* dout, int B, int Cout, int HW, int weighting,
-                        int penalty, float delta, void* stream) {
-    if (B <= 0) return 0;
-    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta) || !sample_w) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(chunks_for(3 * HW / 4), B), block(256);
-    const float inv_nb = 1.0f / ((float)B * 3.0f * (float)HW);
-    if (penalty == VF_LOSS_L1)
-        hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_L1>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
-    else if (penalty == VF_LOSS_HUBER)
-        hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_HUBER>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
-    else
-        hipLaunchKernelGGL(compose_loss_bwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           gloss, sample_w, dout, Cout, HW, weighting, inv_nb, delta);
-    VF_RETURN_LAST_ERROR();
-}
-
-// vf_compose_loss_fwd with a per-sample scale (DEVICE float [B], the importance weight of level_sampler.h): sample_w then
-// holds 2 B floats, w_b scale_b (what the loss and vf_compose_loss_bwd use) and then w_b alone.  scale == NULL is
-// vf_compose_loss_fwd itself.
 int vf_compose_loss_fwd_scaled(const float* unet_out, const int* off, const float* target, const float* level,
                                const float* scale, float* noise_hat, float* loss_part, float* sample_loss,
                                float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B, int Cout, int HW,
                                int weighting, int penalty, float delta, int weight_kind, float a, float b, int K,
                                void* stream) {
-    if (scale == nullptr)
-        return vf_compose_loss_fwd(unet_out, off, target, level, noise_hat, loss_part, sample_loss, sample_w, loss,
-                                   bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream);
-    if (B <= 0) return 0;
-    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
-    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
-    if (!target || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
+    if (B > 0 && !target) return (int)hipErrorInvalidValue;
+    return loss_fwd(VF_PRED_EPS, unet_out, off, target, nullptr, level, scale, noise_hat, loss_part, sample_loss, sample_w,
+                    loss, bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream);
+}
+
+int vf_compose_loss_bwd(const float* unet_out, const int* off, const float* target, const float* noise_hat,
+                        const float* gloss, const float* sample_w, float* dout, int B, int Cout, int HW, int weighting,
+                        int penalty, float delta, void* stream) {
+    return loss_bwd(VF_PRED_EPS, unet_out, off, target, nullptr, nullptr, noise_hat, gloss, sample_w, dout, B, Cout, HW,
+                    weighting, penalty, delta, stream);
+}
+
+int vf_compose_loss_pred_fwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                             const float* level, const float* scale, float* noise_hat, float* loss_part,
+                             float* sample_loss, float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B,
+                             int Cout, int HW, int weighting, int penalty, float delta, int weight_kind, float a, float b,
+                             int K, int pred, void* stream) {
+    if (B > 0 && !pred_args_ok(pred, noise, y_0)) return (int)hipErrorInvalidValue;
+    return loss_fwd(pred, unet_out, off, noise, y_0, level, scale, noise_hat, loss_part, sample_loss, sample_w, loss,
+                    bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream);
+}
+
+int vf_compose_loss_pred_bwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                             const float* level, const float* noise_hat, const float* gloss, const float* sample_w,
+                             float* dout, int B, int Cout, int HW, int weighting, int penalty, float delta, int pred,
+                             void* stream) {
+    if (B > 0 && (!pred_args_ok(pred, noise, y_0) || !level || !noise_hat || !gloss || !dout))
         return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = chunks_for(3 * HW / 4);
-    const dim3 grid(ch, B), block(256);
-    if (penalty == VF_LOSS_L1)
-        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_L1>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           loss_part, Cout, HW, weighting, delta);
-    else if (penalty == VF_LOSS_HUBER)
-        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_HUBER>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           loss_part, Cout, HW, weighting, delta);
-    else
-        hipLaunchKernelGGL(compose_loss_fwd_kernel<VF_LOSS_MSE>, grid, block, 0, st, unet_out, off, target, noise_hat,
-                           loss_part, Cout, HW, weighting, delta);
-    hipLaunchKernelGGL(compose_loss_finish_scaled_kernel, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
-                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b);
-    VF_RETURN_LAST_ERROR();
+    return loss_bwd(pred, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout, B, Cout, HW, weighting,
+                    penalty, delta, stream);
 }
 
 // ---- loss-aware noise-level sampling (level_sampler.h) ----
@@ -1716,54 +1585,6 @@ int vf_loss_weights_host(const float* level, int B, int kind, float a, float b, 
     if (B < 0 || kind < VF_LOSS_W_NONE || kind > VF_LOSS_W_P2) return (int)hipErrorInvalidValue;
     for (int s = 0; s < B; ++s) out[s] = vf_loss_weight(kind, a, b, level[s]);
     return 0;
-}
-
-// ---- prediction (the head of this file): vf_compose_loss_fwd(_scaled) / vf_compose_loss_bwd for pred 1 (v) | 2 (x0),
-// fed noise, y_0 and level instead of a target.  scale (nullable) as in vf_compose_loss_fwd_scaled.  noise may be NULL
-// for x0.  pred 0 (eps) is refused: its path is the entry points above. ----
-int vf_compose_loss_pred_fwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
-                             const float* level, const float* scale, float* noise_hat, float* loss_part,
-                             float* sample_loss, float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B,
-                             int Cout, int HW, int weighting, int penalty, float delta, int weight_kind, float a, float b,
-                             int K, int pred, void* stream) {
-    if (B <= 0) return 0;
-    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
-    if (pred != VF_PRED_V && pred != VF_PRED_X0) return (int)hipErrorInvalidValue;
-    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
-    if (!y_0 || (pred == VF_PRED_V && !noise) || !level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss)
-        return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = chunks_for(3 * HW / 4);
-    if (pred == VF_PRED_V)
-        launch_pred_fwd<VF_PRED_V>(dim3(ch, B), st, penalty, unet_out, off, noise, y_0, level, noise_hat, loss_part, Cout,
-                                   HW, weighting, delta);
-    else
-        launch_pred_fwd<VF_PRED_X0>(dim3(ch, B), st, penalty, unet_out, off, noise, y_0, level, noise_hat, loss_part, Cout,
-                                    HW, weighting, delta);
-    hipLaunchKernelGGL(compose_loss_finish_pred_kernel, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
-                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b, pred);
-    VF_RETURN_LAST_ERROR();
-}
-
-int vf_compose_loss_pred_bwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
-                             const float* level, const float* noise_hat, const float* gloss, const float* sample_w,
-                             float* dout, int B, int Cout, int HW, int weighting, int penalty, float delta, int pred,
-                             void* stream) {
-    if (B <= 0) return 0;
-    if (!loss_args_ok(B, Cout, HW, weighting, penalty, delta) || !sample_w) return (int)hipErrorInvalidValue;
-    if (pred != VF_PRED_V && pred != VF_PRED_X0) return (int)hipErrorInvalidValue;
-    if (!y_0 || (pred == VF_PRED_V && !noise) || !level || !noise_hat || !gloss || !dout) return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(chunks_for(3 * HW / 4), B);
-    const float inv_nb = 1.0f / ((float)B * 3.0f * (float)HW);
-    if (pred == VF_PRED_V)
-        launch_pred_bwd<VF_PRED_V>(grid, st, penalty, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout,
-                                   Cout, HW, weighting, inv_nb, delta);
-    else
-        launch_pred_bwd<VF_PRED_X0>(grid, st, penalty, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout,
-                                    Cout, HW, weighting, inv_nb, delta);
-    VF_RETURN_LAST_ERROR();
 }
 
 // Host mirror: vf_loss_weight_pred itself on the CPU (pred 0 | 1 | 2).  HOST pointers, no stream.

@@ -51,7 +51,7 @@ from .diffusion import (  # noqa: F401
     sample_ids, sampler_step, ssim, stack_views, view_offsets, cond_drop_threshold, draw_cond_drop, guidance_scales,
     abs_quantile, quantile_position, threshold_scratch, threshold_settings,
     LevelSampler, check_level_sampler, draw_level, level_draw_host, level_stats, level_table_host,
-    PREDICTIONS, _ComposeLossPredFn, check_prediction, loss_weights_pred_host,
+    PREDICTIONS, check_prediction, loss_weights_pred_host,
     distill_begin, distill_step_host, distill_target
 )
 from .lpips import (  # noqa: F401

@@ -360,52 +360,61 @@ WEIGHT_KINDS = {None: 0, "none": 0, "min_snr": 1, "p2": 2, "trunc_snr": 3}
 
 
 class _ComposeLossOptFn(torch.autograd.Function):
-    """_ComposeLossFn with a penalty, a per-sample weight of the noise level and the per-sample loss as a second
-    (non-differentiable) output: the same two launches forward and one backward."""
+    """_ComposeLossFn with a penalty, a prediction, a per-sample weight of the noise level (times a per-sample scale) and
+    the per-sample loss as a second (non-differentiable) output: the same two launches forward and one backward.
+    pred 0 (eps): `target` is the ready-made target; pred 1 (v) | 2 (x0): it is the noise, and the kernels form the target
+    from it, y_0 and level themselves -- no target buffer."""
 
     @staticmethod
-    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, scale=None):
-        _check(out, target, level, bin_sum, scale)
+    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, scale=None,
+                pred=0, y_0=None):
+        _check(out, target, y_0, level, bin_sum, scale)
         S, Cout, H, W = out.shape
         if level.numel() != B:
             raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
+        if pred and (tuple(y_0.shape) != (B, 3, H, W) or tuple(target.shape) != (B, 3, H, W)):
+            raise ValueError(f"compose_loss needs noise and y_0 of shape {(B, 3, H, W)}, got {tuple(target.shape)} and "
+                             f"{tuple(y_0.shape)}")
         K = 0
         if bin_sum is not None:
             K = bin_sum.numel()
             if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
                 raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
+        if scale is not None and scale.numel() != B:
+            raise ValueError(f"compose_loss needs one scale per sample: {scale.numel()} for a batch of {B}")
         nh = torch.empty(B, 3, H, W, device=out.device, dtype=torch.float32)
-        if scale is None:
-            buf = torch.empty(B * 66 + 1, device=out.device, dtype=torch.float32)   # partials | sample_loss | sample_w | loss
-            sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * 66:]
-            _call("vf_compose_loss_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(level), _ptr(nh),
-                  _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
-                  None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
-                  delta, kind, a, b, K, _stream())
-            weight = sample_w
-        else:                     # partials | sample_loss | w scale | w | loss  (csrc/level_sampler.h)
-            if scale.numel() != B:
-                raise ValueError(f"compose_loss needs one scale per sample: {scale.numel()} for a batch of {B}")
-            buf = torch.empty(B * 67 + 1, device=out.device, dtype=torch.float32)
-            sample_loss, sample_w, weight, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * 66:B * 67], buf[B * 67:]
-            _call("vf_compose_loss_fwd_scaled", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(level),
-                  _ptr(scale), _ptr(nh), _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
-                  None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
-                  delta, kind, a, b, K, _stream())
-        ctx.save_for_backward(out, target, nh, off, sample_w)
-        ctx.B, ctx.weighting, ctx.penalty, ctx.delta = B, int(weighting), penalty, delta
+        nw = 1 if scale is None else 2           # partials | sample_loss | w (scale) | [w] | loss  (csrc/level_sampler.h)
+        buf = torch.empty(B * (65 + nw) + 1, device=out.device, dtype=torch.float32)
+        sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * (65 + nw):]
+        weight = sample_w if scale is None else buf[B * 66:B * 67]
+        # one entry point per path (the kernel log names them): each takes what its path has, in this order
+        if pred:
+            entry, front, back = "vf_compose_loss_pred_fwd", (_ptr(target), _ptr(y_0), _ptr(level), _ptr(scale)), (pred,)
+        elif scale is not None:
+            entry, front, back = "vf_compose_loss_fwd_scaled", (_ptr(target), _ptr(level), _ptr(scale)), ()
+        else:
+            entry, front, back = "vf_compose_loss_fwd", (_ptr(target), _ptr(level)), ()
+        _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, _ptr(nh), _ptr(buf), _ptr(sample_loss),
+              _ptr(sample_w), _ptr(loss), _ptr(bin_sum), None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()),
+              B, Cout, H * W, int(weighting), penalty, delta, kind, a, b, K, *back, _stream())
+        ctx.save_for_backward(out, target, y_0, level, nh, off, sample_w)
+        ctx.B, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred = B, int(weighting), penalty, delta, pred
         ctx.mark_non_differentiable(sample_loss, weight)
         return loss.reshape(()), sample_loss, weight
 
     @staticmethod
     def backward(ctx, gloss, _gsample, _gweight):
-        out, target, nh, off, sample_w = ctx.saved_tensors
+        out, target, y_0, level, nh, off, sample_w = ctx.saved_tensors
         S, Cout, H, W = out.shape
         gloss = _c(gloss.reshape(1).float())
         dout = torch.empty_like(out)
-        _call("vf_compose_loss_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(nh), _ptr(gloss),
-              _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, _stream())
-        return (dout,) + (None,) * 13
+        if ctx.pred:
+            entry, front, back = "vf_compose_loss_pred_bwd", (_ptr(target), _ptr(y_0), _ptr(level)), (ctx.pred,)
+        else:
+            entry, front, back = "vf_compose_loss_bwd", (_ptr(target),), ()
+        _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, _ptr(nh), _ptr(gloss), _ptr(sample_w), _ptr(dout),
+              ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, *back, _stream())
+        return (dout,) + (None,) * 15
 
 
 # ---- prediction (csrc/diffusion.hip holds the definition): what channels 0..2 of the network mean ----
@@ -434,52 +443,6 @@ def loss_weights_pred_host(level, prediction="eps", weight_kind=None, a=0.0, b=0
     return out
 
 
-class _ComposeLossPredFn(torch.autograd.Function):
-    """_ComposeLossOptFn for v- / x0-prediction: the kernels take noise, y_0 and level and form the target themselves --
-    the same two launches forward and one backward, no target buffer."""
-
-    @staticmethod
-    def forward(ctx, out, noise, y_0, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, scale, pred):
-        _check(out, noise, y_0, level, bin_sum, scale)
-        S, Cout, H, W = out.shape
-        if level.numel() != B:
-            raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
-        if tuple(y_0.shape) != (B, 3, H, W) or tuple(noise.shape) != (B, 3, H, W):
-            raise ValueError(f"compose_loss needs noise and y_0 of shape {(B, 3, H, W)}, got {tuple(noise.shape)} and "
-                             f"{tuple(y_0.shape)}")
-        K = 0
-        if bin_sum is not None:
-            K = bin_sum.numel()
-            if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
-                raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
-        if scale is not None and scale.numel() != B:
-            raise ValueError(f"compose_loss needs one scale per sample: {scale.numel()} for a batch of {B}")
-        nh = torch.empty(B, 3, H, W, device=out.device, dtype=torch.float32)
-        nw = 1 if scale is None else 2           # partials | sample_loss | w (scale) | [w] | loss
-        buf = torch.empty(B * (65 + nw) + 1, device=out.device, dtype=torch.float32)
-        sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * (65 + nw):]
-        weight = sample_w if scale is None else buf[B * 66:B * 67]
-        _call("vf_compose_loss_pred_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(noise), _ptr(y_0), _ptr(level),
-              _ptr(scale), _ptr(nh), _ptr(buf), _ptr(sample_loss), _ptr(sample_w), _ptr(loss), _ptr(bin_sum),
-              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
-              delta, kind, a, b, K, pred, _stream())
-        ctx.save_for_backward(out, noise, y_0, level, nh, off, sample_w)
-        ctx.B, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred = B, int(weighting), penalty, delta, pred
-        ctx.mark_non_differentiable(sample_loss, weight)
-        return loss.reshape(()), sample_loss, weight
-
-    @staticmethod
-    def backward(ctx, gloss, _gsample, _gweight):
-        out, noise, y_0, level, nh, off, sample_w = ctx.saved_tensors
-        S, Cout, H, W = out.shape
-        gloss = _c(gloss.reshape(1).float())
-        dout = torch.empty_like(out)
-        _call("vf_compose_loss_pred_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(noise), _ptr(y_0), _ptr(level),
-              _ptr(nh), _ptr(gloss), _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty,
-              ctx.delta, ctx.pred, _stream())
-        return (dout,) + (None,) * 15
-
-
 def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delta=1.0, weight_kind=None, a=0.0, b=0.0,
                  hist=None, sample_scale=None, want_weight=False, prediction="eps", y_0=None):
     """compose_mse_loss with options: -> (loss, sample_loss).  d = compose(unet_out) - target;
@@ -489,12 +452,12 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
     hist = (bin_sum float32 [K], bin_cnt int32 [K]) device accumulators: bin min(K - 1, int(g K)) receives the
     UNWEIGHTED sample_loss[b] and a count; they persist across calls (the caller zeroes them).
     sample_scale (device float32 (B,), default None: the launches above, untouched): a per-sample factor on w_b -- the
-    importance weight of a non-uniform timestep draw (draw_level); loss = sum_b w_b scale_b sample_loss[b] / B through a
-    sibling of the finish kernel, sample_loss and the histogram stay unweighted.
+    importance weight of a non-uniform timestep draw (draw_level); loss = sum_b w_b scale_b sample_loss[b] / B, sample_loss
+    and the histogram stay unweighted.
     want_weight=True: -> (loss, sample_loss, w) with w (B,) the noise-level weight ALONE (what level_stats reads).
     prediction "eps" (the default: everything above, launch for launch) | "v" | "x0" (csrc/diffusion.hip holds the
     definition): `target` is then the NOISE and y_0 (B, 3, H, W) is required; d = compose(unet_out) - the prediction's
-    own target (v: sqrt(g) noise - sqrt(1 - g) y_0; x0: y_0), formed inside sibling kernels from noise, y_0 and level --
+    own target (v: sqrt(g) noise - sqrt(1 - g) y_0; x0: y_0), formed inside the loss kernels from noise, y_0 and level --
     no target buffer, the same launch count -- and w the prediction's native weight (csrc/loss_weight.h)."""
     if penalty not in PENALTIES:
         raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
@@ -508,14 +471,10 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
     bin_sum, bin_cnt = hist if hist is not None else (None, None)
     if sample_scale is not None:
         sample_scale = _c(sample_scale.reshape(-1))
-    if prediction != "eps":
-        loss, sample_loss, weight = _ComposeLossPredFn.apply(
-            unet_out, _c(target), _c(y_0), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty], float(delta),
-            WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, sample_scale, PREDICTIONS[prediction])
-        return (loss, sample_loss, weight) if want_weight else (loss, sample_loss)
     loss, sample_loss, weight = _ComposeLossOptFn.apply(
         unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty], float(delta),
-        WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, sample_scale)
+        WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, sample_scale, PREDICTIONS[prediction],
+        None if y_0 is None else _c(y_0))
     return (loss, sample_loss, weight) if want_weight else (loss, sample_loss)
 
 
