@@ -29,6 +29,20 @@ int vf_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, f
  * the conv bias / embedding bias added in front of this GroupNorm (unet.py:160-177); only filled where
  * vf_gn_bwd_emits_rowsum() says so. */
 int vf_gn_bwd_emits_rowsum(int C, int HW, int groups);
+/* The plan vf_gn_cat_fwd / vf_gn_cat_bwd (vf_gn_fwd / vf_gn_bwd: cat = 0) take for these arguments: host only, touches no
+ * device, launches nothing; the launchers run the function that fills it.  cat: the input is the concatenation
+ * [C1 | C - C1]; has_addend / has_addend2 / has_dx2: which optional pointers the backward gets (the forward's fields do
+ * not depend on them).  out[12] = {
+ *   [0] forward route: 0 rejected (hipErrorInvalidValue), 1 gn_fwd_kernel<NV, NT>, 2 gn_any_fwd_kernel;
+ *   [1] [2] the forward's NV, NT (route 1, else 0);
+ *   [3] backward route: 0 rejected, 1 gn_bwd_fused_kernel<NV, 256, 16>, 2 gn_bwd_fused_kernel<NV, NT, 64>,
+ *       3 gn_bwd_rows_kernel + gn_bwd_dx_kernel (+ add_inplace_kernel per addend), 4 gn_any_bwd_kernel;
+ *   [4] [5] [6] the backward's NV, NT, SEG and [7] its dynamic LDS bytes (routes 1, 2, else 0);
+ *   [8] chunks, the second grid dimension of gn_bwd_dx_kernel, and [9] add_inplace_kernel launches (route 3, else 0);
+ *   [10] dx_rowsum is written where one is passed (= vf_gn_bwd_emits_rowsum for a plain input);
+ *   [11] channels per group (0 where groups does not divide C) }.
+ * Returns hipErrorInvalidValue only for out == NULL: a refused call is a plan with route 0. */
+int vf_gn_plan(int C, int HW, int groups, int cat, int C1, int has_addend, int has_addend2, int has_dx2, int* out /*[12]*/);
 int vf_gn_bwd(const float* x, const float* gamma, const float* beta, const float* mean, const float* rstd,
               const float* dy, const float* addend, float* dx, float* dgamma_part, float* dbeta_part,
               float* dx_rowsum, int S, int C, int HW, int groups, int silu, void* stream);

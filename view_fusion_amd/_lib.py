@@ -29,6 +29,7 @@ _U64 = ctypes.c_uint64       # the seed of the counter-based draws (csrc/rng.h)
 SIGNATURES = {
     "vf_gn_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "vf_gn_bwd_emits_rowsum": [_I, _I, _I],
+    "vf_gn_plan": [_I, _I, _I, _I, _I, _I, _I, _I, _P],
     "vf_gn_cat_fwd": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
     "vf_gn_cat_bwd": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "vf_conv1x1_cat_fwd": [_P, _P, _I, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _P],

@@ -9,6 +9,7 @@
 // Layout: NCHW fp32, a group is cpg*H*W contiguous floats.
 #include "common.h"
 #include "any_geom.h"
+#include <cstring>
 
 namespace {
 
@@ -532,6 +533,85 @@ int launch_gn_fwd(const float* x, const float* x2, int C1, const float* gamma, c
     VF_RETURN_LAST_ERROR();
 }
 
+// The plan of one GroupNorm forward and of the backward behind it: every decision vf_gn_cat_fwd / vf_gn_cat_bwd take on the
+// host (validity included), made in ONE place (gn_plan below) that the launchers execute and vf_gn_plan reports.
+enum { GN_REJECTED = 0, GN_FWD_REG = 1, GN_FWD_ANY = 2 };        // gn_fwd_kernel<NV, NT> | gn_any_fwd_kernel
+// gn_bwd_fused_kernel<NV, 256, 16> | gn_bwd_fused_kernel<NV, NT, 64> | gn_bwd_rows_kernel + gn_bwd_dx_kernel (+ add_inplace_kernel
+// per addend) | gn_any_bwd_kernel
+enum { GN_BWD_FUSED16 = 1, GN_BWD_FUSED64 = 2, GN_BWD_TWO = 3, GN_BWD_ANY = 4 };
+struct GnPlan {
+    int fwd, fnv, fnt;                               // forward route and its instantiation (0, 0 off the register kernel)
+    int bwd, bnv, bnt, seg, lds;                     // backward route, instantiation, dynamic LDS bytes (fused routes only)
+    int chunks, adds;                                // two-kernel path: gridDim.y of the dx kernel, add_inplace launches
+    int rowsum;                                      // the backward writes dx_rowsum (where one is passed)
+    int cpg;
+};
+
+// cat: the input is the never materialised concatenation [C1 | C - C1]; has_addend / has_addend2 / has_dx2: which of the
+// backward's optional pointers are passed (they do not touch the forward's fields).
+inline GnPlan gn_plan(int C, int HW, int groups, bool cat, int C1, bool has_addend, bool has_addend2, bool has_dx2) {
+    GnPlan p = {};
+    if (groups <= 0 || C % groups != 0) return p;
+    const int cpg = C / groups;
+    p.cpg = cpg;
+    // HW: a power of two >= 4 (square power-of-two maps; the kernels index channels by shifts); any other HW, or a group
+    // too large for the register-resident forward, takes the general kernels (norm_any.hip; plain input only, any HW >= 1)
+    const bool pow2 = HW >= 4 && !(HW & (HW - 1));
+    const long n4 = (long)cpg * HW / 4;              // float4 per (view, group)
+    const bool cat_ok = !cat || (C1 > 0 && C1 < C);
+    if (!pow2 || n4 > 32768) {
+        p.fwd = (cat || HW < 1) ? GN_REJECTED : GN_FWD_ANY;
+    } else if (cat_ok) {
+        static const int tab[11][3] = {{64, 1, 64},     {256, 1, 256},   {512, 2, 256},    {1024, 4, 256},
+                                       {2048, 8, 256},  {3072, 12, 256}, {4096, 16, 256},  {6144, 12, 512},
+                                       {8192, 16, 512}, {16384, 16, 1024}, {32768, 32, 1024}};
+        for (int i = 0; i < 11; ++i)
+            if (n4 <= tab[i][0]) {
+                p.fwd = GN_FWD_REG, p.fnv = tab[i][1], p.fnt = tab[i][2];
+                break;
+            }
+    }
+    if (!pow2) {                                     // general HW: plain input, no dx_rowsum
+        p.bwd = (cat || HW < 1) ? GN_REJECTED : GN_BWD_ANY;
+        return p;
+    }
+    const bool fused16 = HW == 64 && n4 <= 1024;     // 8x8 maps: 16-lane channel segments
+    const bool fused64 = HW >= 256 && n4 <= 8192;
+    // cat inputs: single-pass kernels only, both dx, both addends or none
+    if (cat && (!cat_ok || !has_dx2 || (has_addend && !has_addend2) || !(fused16 || fused64))) return p;
+    if (fused16) {
+        p.bwd = GN_BWD_FUSED16, p.bnv = n4 <= 256 ? 1 : n4 <= 512 ? 2 : 4, p.bnt = 256, p.seg = 16;
+    } else if (fused64) {
+        static const int tab[7][3] = {{256, 1, 256},  {512, 2, 256},   {1024, 4, 256}, {2048, 8, 256},
+                                      {4096, 8, 512}, {6144, 12, 512}, {8192, 8, 1024}};
+        for (int i = 0; i < 7; ++i)
+            if (n4 <= tab[i][0]) {
+                p.bnv = tab[i][1], p.bnt = tab[i][2];
+                break;
+            }
+        p.bwd = GN_BWD_FUSED64, p.seg = 64;
+    } else {
+        p.bwd = GN_BWD_TWO;
+        const long chunks = (n4 + 1023) / 1024;      // >= 4 float4 per thread
+        p.chunks = chunks < 1 ? 1 : (int)chunks;
+        p.adds = (has_addend ? 1 : 0) + (has_addend2 ? 1 : 0);
+        return p;
+    }
+    p.lds = (p.bnt / 64) * cpg * 3 * 4;              // part[NWV][cpg][3]
+    p.rowsum = 1;
+    return p;
+}
+
+template <int NV, int NT, int SEG>
+int launch_gn_bwd_fused(const GnPlan& p, const float* x, const float* x2, int C1, const float* dy, const float* gamma,
+                        const float* beta, const float* mean, const float* rstd, const float* addend, const float* addend2,
+                        float* dx, float* dx2, float* dgamma_part, float* dbeta_part, float* dx_rowsum, int S, int C, int HW,
+                        int groups, int silu, hipStream_t st) {
+    hipLaunchKernelGGL((gn_bwd_fused_kernel<NV, NT, SEG>), dim3(S * groups), dim3(NT), p.lds, st, x, x2, C1, dy, gamma, beta,
+                       mean, rstd, addend, addend2, dx, dx2, dgamma_part, dbeta_part, dx_rowsum, C, HW, p.cpg, silu);
+    VF_RETURN_LAST_ERROR();
+}
+
 }  // namespace
 
 extern "C" {
@@ -540,27 +620,23 @@ int vf_gn_cat_fwd(const float* x, const float* x2, int C1, const float* gamma, c
                   float* rstd, int S, int C, int HW, int groups, float eps, int silu, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (S <= 0) return 0;
-    // HW: a power of two >= 4 (square power-of-two maps; the kernels index channels by shifts); any other HW, or a group
-    // too large for the register-resident kernels, takes the general kernel (norm_any.hip; plain input only)
-    if (groups <= 0 || C % groups != 0 || (x2 && (C1 <= 0 || C1 >= C))) return (int)hipErrorInvalidValue;
-    const int cpg = C / groups;
-    const long n4 = (long)cpg * HW / 4;
-    if (HW < 4 || (HW & (HW - 1)) || n4 > 32768) {
-        if (x2) return (int)hipErrorInvalidValue;
-        return vfi_gn_any_fwd(x, gamma, beta, y, mean, rstd, S, C, HW, groups, eps, silu, st);
-    }
-#define VF_GN(NV, NT) return launch_gn_fwd<NV, NT>(x, x2, C1, gamma, beta, y, mean, rstd, S, C, HW, cpg, eps, silu, st)
-    if (n4 <= 64) VF_GN(1, 64);
-    if (n4 <= 256) VF_GN(1, 256);
-    if (n4 <= 512) VF_GN(2, 256);
-    if (n4 <= 1024) VF_GN(4, 256);
-    if (n4 <= 2048) VF_GN(8, 256);
-    if (n4 <= 3072) VF_GN(12, 256);
-    if (n4 <= 4096) VF_GN(16, 256);
-    if (n4 <= 6144) VF_GN(12, 512);
-    if (n4 <= 8192) VF_GN(16, 512);
-    if (n4 <= 16384) VF_GN(16, 1024);
-    if (n4 <= 32768) VF_GN(32, 1024);
+    const GnPlan p = gn_plan(C, HW, groups, x2 != nullptr, C1, false, false, true);
+    if (p.fwd == GN_FWD_ANY) return vfi_gn_any_fwd(x, gamma, beta, y, mean, rstd, S, C, HW, groups, eps, silu, st);
+    if (p.fwd != GN_FWD_REG) return (int)hipErrorInvalidValue;
+#define VF_GN(NV, NT)                                                                                                    \
+    if (p.fnv == NV && p.fnt == NT)                                                                                      \
+    return launch_gn_fwd<NV, NT>(x, x2, C1, gamma, beta, y, mean, rstd, S, C, HW, p.cpg, eps, silu, st)
+    VF_GN(1, 64);
+    VF_GN(1, 256);
+    VF_GN(2, 256);
+    VF_GN(4, 256);
+    VF_GN(8, 256);
+    VF_GN(12, 256);
+    VF_GN(16, 256);
+    VF_GN(12, 512);
+    VF_GN(16, 512);
+    VF_GN(16, 1024);
+    VF_GN(32, 1024);
 #undef VF_GN
     return (int)hipErrorInvalidValue;
 }
@@ -570,11 +646,24 @@ int vf_gn_fwd(const float* x, const float* gamma, const float* beta, float* y, f
     return vf_gn_cat_fwd(x, nullptr, C, gamma, beta, y, mean, rstd, S, C, HW, groups, eps, silu, stream);
 }
 
-// 1 when vf_gn_bwd fills `dx_rowsum` at this shape (the single-pass kernel; the two-kernel path does not)
+// The plan vf_gn_cat_fwd and vf_gn_cat_bwd (vf_gn_fwd / vf_gn_bwd: cat = 0) take for these arguments: host only, touches
+// no device, launches nothing.  The launchers run the very function that fills `out` = {forward route (0 rejected, 1
+// gn_fwd_kernel<NV, NT>, 2 gn_any_fwd_kernel), NV, NT, backward route (0 rejected, 1 gn_bwd_fused_kernel<NV, 256, 16>, 2
+// gn_bwd_fused_kernel<NV, NT, 64>, 3 gn_bwd_rows_kernel + gn_bwd_dx_kernel, 4 gn_any_bwd_kernel), NV, NT, SEG, dynamic
+// LDS bytes, chunks (gridDim.y of gn_bwd_dx_kernel), add_inplace_kernel launches, dx_rowsum written (where passed),
+// channels per group}; fields a route does not use are 0.  has_addend / has_addend2 / has_dx2: the backward's optional
+// pointers.  Returns hipErrorInvalidValue only for out == NULL: a rejected shape is a plan (route 0), not an error.
+int vf_gn_plan(int C, int HW, int groups, int cat, int C1, int has_addend, int has_addend2, int has_dx2, int* out) {
+    if (!out) return (int)hipErrorInvalidValue;
+    const GnPlan p = gn_plan(C, HW, groups, cat != 0, C1, has_addend != 0, has_addend2 != 0, has_dx2 != 0);
+    const int v[12] = {p.fwd, p.fnv, p.fnt, p.bwd, p.bnv, p.bnt, p.seg, p.lds, p.chunks, p.adds, p.rowsum, p.cpg};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+
+// 1 when vf_gn_bwd fills `dx_rowsum` at this shape (the single-pass kernels; the two-kernel path and the general kernel do not)
 int vf_gn_bwd_emits_rowsum(int C, int HW, int groups) {
-    if (groups <= 0 || C % groups != 0 || HW < 4 || (HW & (HW - 1))) return 0;
-    const long n4g = (long)(C / groups) * HW / 4;
-    return ((HW >= 256 && n4g <= 8192) || (HW == 64 && n4g <= 1024)) ? 1 : 0;
+    return gn_plan(C, HW, groups, false, C, false, false, false).rowsum;
 }
 
 int vf_gn_cat_bwd(const float* x, const float* x2, int C1, const float* gamma, const float* beta, const float* mean,
@@ -583,53 +672,34 @@ int vf_gn_cat_bwd(const float* x, const float* x2, int C1, const float* gamma, c
                   void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (S <= 0) return 0;
-    if (groups <= 0 || C % groups != 0) return (int)hipErrorInvalidValue;
-    if (HW < 4 || (HW & (HW - 1))) {                     // general HW: norm_any.hip (plain input, no dx_rowsum)
-        if (x2) return (int)hipErrorInvalidValue;
+    const GnPlan p = gn_plan(C, HW, groups, x2 != nullptr, C1, addend != nullptr, addend2 != nullptr, dx2 != nullptr);
+    if (p.bwd == GN_REJECTED) return (int)hipErrorInvalidValue;
+    if (p.bwd == GN_BWD_ANY)
         return vfi_gn_any_bwd(x, gamma, beta, mean, rstd, dy, addend, addend2, dx, dgamma_part, dbeta_part, S, C, HW, groups,
                               silu, st);
-    }
-    if (x2 && (C1 <= 0 || C1 >= C || !dx2 || (addend && !addend2) || !vf_gn_bwd_emits_rowsum(C, HW, groups)))
-        return (int)hipErrorInvalidValue;                // cat inputs: single-pass kernels only
-    const int cpg = C / groups;
-    const int rows = S * C;
-    const long n4g = (long)cpg * HW / 4;
-    if (HW == 64 && n4g <= 1024) {       // 8x8 maps: 16-lane channel segments
-#define VF_GNB16(NV)                                                                                       \
-    {                                                                                                      \
-        hipLaunchKernelGGL((gn_bwd_fused_kernel<NV, 256, 16>), dim3(S * groups), dim3(256), 4 * cpg * 3 * 4, st, x, x2, C1, dy, \
-                           gamma, beta, mean, rstd, addend, addend2, dx, dx2, dgamma_part, dbeta_part, dx_rowsum, C, HW, cpg, silu); \
-        VF_RETURN_LAST_ERROR();                                                                            \
-    }
-        if (n4g <= 256) VF_GNB16(1)
-        if (n4g <= 512) VF_GNB16(2)
-        VF_GNB16(4)
-#undef VF_GNB16
-    }
-    if (HW >= 256 && n4g <= 8192) {
-#define VF_GNB(NV, NT)                                                                                     \
-    {                                                                                                      \
-        hipLaunchKernelGGL((gn_bwd_fused_kernel<NV, NT>), dim3(S * groups), dim3(NT), (NT / 64) * cpg * 3 * 4, st, \
-                           x, x2, C1, dy, gamma, beta, mean, rstd, addend, addend2, dx, dx2, dgamma_part, dbeta_part, \
-                           dx_rowsum, C, HW, cpg, silu);                                                   \
-        VF_RETURN_LAST_ERROR();                                                                            \
-    }
-        if (n4g <= 256) VF_GNB(1, 256)
-        if (n4g <= 512) VF_GNB(2, 256)
-        if (n4g <= 1024) VF_GNB(4, 256)
-        if (n4g <= 2048) VF_GNB(8, 256)
-        if (n4g <= 4096) VF_GNB(8, 512)
-        if (n4g <= 6144) VF_GNB(12, 512)
-        VF_GNB(8, 1024)
+    if (p.bwd == GN_BWD_FUSED16 || p.bwd == GN_BWD_FUSED64) {
+#define VF_GNB(NV, NT, SEG)                                                                                              \
+    if (p.bnv == NV && p.bnt == NT && p.seg == SEG)                                                                      \
+    return launch_gn_bwd_fused<NV, NT, SEG>(p, x, x2, C1, dy, gamma, beta, mean, rstd, addend, addend2, dx, dx2,          \
+                                            dgamma_part, dbeta_part, dx_rowsum, S, C, HW, groups, silu, st)
+        VF_GNB(1, 256, 16);
+        VF_GNB(2, 256, 16);
+        VF_GNB(4, 256, 16);
+        VF_GNB(1, 256, 64);
+        VF_GNB(2, 256, 64);
+        VF_GNB(4, 256, 64);
+        VF_GNB(8, 256, 64);
+        VF_GNB(8, 512, 64);
+        VF_GNB(12, 512, 64);
+        VF_GNB(8, 1024, 64);
 #undef VF_GNB
+        return (int)hipErrorInvalidValue;
     }
+    const int rows = S * C;
     hipLaunchKernelGGL(gn_bwd_rows_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, dy, gamma, beta, mean, rstd,
-                       dbeta_part, dgamma_part, rows, C, HW, cpg, silu);
-    const int n4 = cpg * HW / 4;
-    int chunks = (n4 + 1023) / 1024;  // >= 4 float4 per thread
-    if (chunks < 1) chunks = 1;
-    hipLaunchKernelGGL(gn_bwd_dx_kernel, dim3(S * groups, chunks), dim3(256), 0, st, x, dy, gamma, beta, mean,
-                       rstd, dbeta_part, dgamma_part, dx, C, HW, cpg, silu);
+                       dbeta_part, dgamma_part, rows, C, HW, p.cpg, silu);
+    hipLaunchKernelGGL(gn_bwd_dx_kernel, dim3(S * groups, p.chunks), dim3(256), 0, st, x, dy, gamma, beta, mean,
+                       rstd, dbeta_part, dgamma_part, dx, C, HW, p.cpg, silu);
     const size_t t4 = (size_t)S * C * HW / 4;
     if (addend)
         hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((t4 + 255) / 256)), dim3(256), 0, st, (float4*)dx,
