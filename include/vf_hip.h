@@ -272,6 +272,24 @@ int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, cons
                        float* dqkv, int S, int C, int L, void* stream);
 int vf_softmax_fwd(const float* x, float* y, int rows, int cols, void* stream);
 int vf_softmax_bwd(const float* y, const float* dy, float* dx, int rows, int cols, void* stream);
+/* The launch plans of this family, host only (nothing is launched); the launchers execute the functions that answer.
+ * vf_bgemm_plan: out[7] = {launches (0: batch, M or N <= 0), variant (0 bgemm_kernel, 1..4 bgemm_v2_kernel<A_KC, B_KC> =
+ *   <1,1> <1,0> <0,1> <0,0>), grid x, y, z, xcd_batches (whole groups of eight batch items dealt one per XCD), refused};
+ *   refused = the failed terms of the fast kernels' predicate as bits: 1 A has no unit stride, 2 B has none, 4 sCn != 1,
+ *   8 K % 4, 16 sAb % 4, 32 sBb % 4, 64 sAm % 4 (A k-contiguous), 128 sAk % 4 and 256 M % 4 (A m-contiguous), 512 sBn % 4
+ *   (B k-contiguous), 1024 sBk % 4 and 2048 N % 4 (B n-contiguous), 4096 A | B not 16-byte aligned.  A and B count by their
+ *   alignment alone.
+ * vf_softmax_plan: out[2] = {MAXV of softmax_fwd_kernel / softmax_bwd_kernel (1, 4, 16, 64; 0 above 4096 columns:
+ *   refused), workgroups}.
+ * vf_attention_bwd_plan: what the backward of the attention core runs (ops/attention.py), use_dscore / use_dvdk being its
+ *   two switches: out[6] = {route (1 dscore + dvdk, 2 dscore + the dV and dK products, 3 four products + softmax backward
+ *   on the materialised scores, 0 nothing: a size <= 0 or L > 4096), workgroups of vf_attention_dscore, of
+ *   vf_attention_dvdk, the vf_bgemm products as bits (1 dP, 2 dV, 4 dQ, 8 dK), rows and columns of vf_softmax_bwd}.
+ * Each returns hipErrorInvalidValue only for out == NULL. */
+int vf_bgemm_plan(const void* A, const void* B, int batch, int M, int N, int K, long sAb, long sAm, long sAk, long sBb,
+                  long sBk, long sBn, long sCn, int* out /*[7]*/);
+int vf_softmax_plan(int rows, int cols, int* out /*[2]*/);
+int vf_attention_bwd_plan(int S, int C, int L, int use_dscore, int use_dvdk, int* out /*[6]*/);
 
 /* ---- small elementwise : PositionalEncoding unet.py:142-157, Swish :180-182, torch.cat :134 ---- */
 int vf_sincos_embed(const float* level /*[S]*/, const float* angle /*[S]*/, float* out /*[S][dim]*/, int S, int dim,

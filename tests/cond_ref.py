@@ -20,7 +20,10 @@ EPS = 1e-5            # nn.GroupNorm's eps everywhere in the UNet
 # test_winograd_fixup_evaluates_the_groupnorm, test_conv_small_groupnorm_without_a_launch, test_compose_loss_and_stack,
 # test_p_sample_tail; DESIGN 5 "kernels rel 2e-5").
 TOL = {"gn_fwd": 1e-5, "gn_bwd": 2e-5, "attn_fwd": 2e-5, "attn_bwd": 5e-5, "conv_gn": 2e-5, "small_h": 2e-6,
-       "small_y": 5e-6, "compose": 1e-5, "compose_loss": 1e-6}
+       "small_y": 5e-6, "compose": 1e-5, "compose_loss": 1e-6, "softmax": 9e-7}
+
+# "softmax" (vf_softmax_fwd / _bwd alone, no stated tolerance): four times the largest stock fp32 error over
+# attn_plan_ref.softmax_cases(), rounded up to one digit (2.04e-7 -> 9e-7; tests/test_attn_plan_host.py recomputes it).
 
 # The grid (ISSUE: fp32 CPU e <= 7.2e-5 for GroupNorm at ratio 100, 1.1e-3 at ratio 1000 -- not used; attention scale 14:
 # e <= 6.9e-5).  Compose logit scales chosen the same way: e (measured on the CPU, test_cond_host) stays below 1e-6 up to

@@ -171,9 +171,9 @@ ATTN_KERNEL_CODE = {1: "q16", 2: "q32", 3: "split", 4: "128-query"}       # vf_a
 
 def _attn_launches(C, L):
     """The C-ABI entries of a training call of ops.attention (forward, then backward)."""
-    if L == 256:
+    if L == 256 and C % 32 == 0:
         return ["vf_attention_fwd", "vf_attention_dscore"] + (["vf_attention_dvdk"] if C % 64 == 0 else ["vf_bgemm"] * 2)
-    if L == 64:
+    if L == 64 and C % 32 == 0:          # (C % 32 != 0 sends the fused maps to the generic path too)
         return ["vf_attention_fwd", "vf_bgemm", "vf_softmax_bwd", "vf_bgemm", "vf_bgemm", "vf_bgemm"]
     return ["vf_bgemm", "vf_softmax_fwd", "vf_bgemm", "vf_bgemm", "vf_softmax_bwd", "vf_bgemm", "vf_bgemm", "vf_bgemm"]
 

@@ -578,9 +578,11 @@ def test_attention_fwd_bwd(dev, C, H, S):
     """S <= 16 at L=256 (C a multiple of 64) runs the 16-query kernel of round 5 (the sampler's); every other L=256 call the
     32-query kernel (round 5: 8 S workgroups, whole groups of eight views placed per XCD + a plain-order remainder -- S = 17,
     53, 56; C = 32 is its shortest channel loop) or, where 2 S workgroups fill the chip better (S = 100), the 128-query
-    kernel; L=64 the key-split kernel.  All write the probabilities for the backward pass here.  Backward at L=256: one
-    launch of the 32-query kernel in its second role (dS from dP = dO^T V and P in registers, then dQ = K dS^T) + the dV and dK
-    batched products; at L=64 four batched products + the softmax backward."""
+    kernel.  Both L=64 shapes here (S = 3, C = 320 and 64: multiples of 64) take the 16-query kernel as well -- the L=64
+    key-split kernel (S > 16 or C % 64 != 0) runs in tests/test_gpu_attn_plan.py.  All write the probabilities for the backward
+    pass here.  Backward at L=256: one launch of the 32-query kernel in its second role (dS from dP = dO^T V and P in registers,
+    then dQ = K dS^T) + one launch for dV and dK where C is a multiple of 64 (192, 64), the two batched products otherwise
+    (96, 32); at L=64 four batched products + the softmax backward."""
     from view_fusion_amd import ops
     L = H * H
     qkv, gy = rnd(S, 3 * C, H, H, seed=1) * 2, rnd(S, C, H, H, seed=2)
@@ -598,8 +600,9 @@ def test_attention_fwd_bwd(dev, C, H, S):
 @pytest.mark.parametrize("C,H,S", [(192, 16, 2), (320, 8, 2), (32, 32, 2), (192, 16, 12), (192, 16, 40), (192, 16, 60), (320, 8, 40),
                                    (320, 16, 16), (192, 16, 1), (96, 16, 5), (192, 16, 96), (192, 16, 128), (64, 16, 150)])
 def test_attention_inference_path(dev, C, H, S):
-    """no-grad call: fused kernels without the probability write (L=64/256, both view-count regimes) / generic
-    path (L=1024)."""
+    """no-grad call: fused kernels without the probability write (L=64: the 16-query kernel at S = 2, the key-split kernel at
+    S = 40; L=256: the 16-query kernel up to S = 16 where C is a multiple of 64, the 32-query kernel at S = 5 (C = 96), 40, 60,
+    96 and 150, the 128-query kernel at S = 128) / generic path (L=1024)."""
     from view_fusion_amd import ops
     L = H * H
     qkv = rnd(S, 3 * C, H, H, seed=3) * 2

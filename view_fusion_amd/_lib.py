@@ -88,6 +88,9 @@ SIGNATURES = {
     "vf_attn_stream_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vf_softmax_fwd": [_P, _P, _I, _I, _P],
     "vf_softmax_bwd": [_P, _P, _P, _I, _I, _P],
+    "vf_bgemm_plan": [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _P],
+    "vf_softmax_plan": [_I, _I, _P],
+    "vf_attention_bwd_plan": [_I, _I, _I, _I, _I, _P],
     "vf_sincos_embed": [_P, _P, _P, _I, _I, _P],
     "vf_swish_fwd": [_P, _P, _L, _P],
     "vf_swish_bwd": [_P, _P, _P, _L, _P],

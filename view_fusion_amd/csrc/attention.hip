@@ -894,6 +894,13 @@ __global__ __launch_bounds__(256, 5) void attn_bwd_dvdk_kernel(const float* __re
     }
 }
 
+// The shapes the two backward kernels take and their grids: vf_attention_dscore / vf_attention_dvdk launch by these,
+// vf_attention_bwd_plan reports them.
+bool attn_dscore_ok(int C, int L) { return L == 256 && C % 32 == 0 && C >= 32; }
+bool attn_dvdk_ok(int C, int L) { return L == 256 && C % 64 == 0 && C >= 64; }
+int attn_dscore_blocks(int S) { return 8 * S; }                      // attn_fwd_q32_kernel<true>: 8 query blocks per view
+int attn_dvdk_blocks(int S, int C) { return 2 * S * (C / 64) * 2; }  // (product, view) pairs x 64-channel x 128-key tiles
+
 }  // namespace
 
 extern "C" {
@@ -952,8 +959,8 @@ int vf_attention_fwd(const float* qkv, float* out, float* P, int S, int C, int L
 int vf_attention_dscore(const float* qkv, const float* dO, const float* P, float* dS, float* dqkv, int S, int C, int L,
                         void* stream) {
     if (S <= 0) return 0;
-    if (L != 256 || C % 32 != 0 || C < 32) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(attn_fwd_q32_kernel<true>, dim3(8 * S), dim3(256), 0, (hipStream_t)stream, qkv, dqkv,
+    if (!attn_dscore_ok(C, L)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(attn_fwd_q32_kernel<true>, dim3(attn_dscore_blocks(S)), dim3(256), 0, (hipStream_t)stream, qkv, dqkv,
                        const_cast<float*>(P), C, 1.0f / sqrtf((float)C), S, dO, dS);
     VF_RETURN_LAST_ERROR();
 }
@@ -963,10 +970,31 @@ int vf_attention_dscore(const float* qkv, const float* dO, const float* P, float
 int vf_attention_dvdk(const float* qkv, const float* dO, const float* P, const float* dS, float* dqkv, int S, int C, int L,
                       void* stream) {
     if (S <= 0) return 0;
-    if (L != 256 || C % 64 != 0 || C < 64) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(attn_bwd_dvdk_kernel, dim3(2 * S * (C / 64) * 2), dim3(256), 0, (hipStream_t)stream, qkv, dO, P, dS,
+    if (!attn_dvdk_ok(C, L)) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(attn_bwd_dvdk_kernel, dim3(attn_dvdk_blocks(S, C)), dim3(256), 0, (hipStream_t)stream, qkv, dO, P, dS,
                        dqkv, C, 1.0f / sqrtf((float)C), S);
     VF_RETURN_LAST_ERROR();
+}
+
+// Host only, launches nothing: what the backward of the attention core runs at (S, C, L) -- the route ops/attention.py's
+// _AttentionFn.backward takes, with use_dscore / use_dvdk its two switches (VF_ATTN_DSCORE / VF_ATTN_DVDK, both on by
+// default) -> out[6] = {route, workgroups of vf_attention_dscore, workgroups of vf_attention_dvdk, the vf_bgemm products as
+// bits (1 dP, 2 dV, 4 dQ, 8 dK), rows of vf_softmax_bwd, its columns}.  Routes: 1 dscore + dvdk, 2 dscore + the dV and dK
+// products, 3 the four products and the softmax backward on the materialised scores (any L <= 4096), 0 nothing here
+// (S, C or L <= 0, or L > 4096: the softmax kernels refuse, such maps take vf_attn_stream_bwd).  Fields a route does not
+// use are 0.
+int vf_attention_bwd_plan(int S, int C, int L, int use_dscore, int use_dvdk, int* out) {
+    if (!out) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (S <= 0 || C <= 0 || L <= 0 || L > 4096) return 0;
+    const bool dscore = use_dscore && attn_dscore_ok(C, L), dvdk = dscore && use_dvdk && attn_dvdk_ok(C, L);
+    out[0] = dvdk ? 1 : dscore ? 2 : 3;
+    out[1] = dscore ? attn_dscore_blocks(S) : 0;
+    out[2] = dvdk ? attn_dvdk_blocks(S, C) : 0;
+    out[3] = dvdk ? 0 : dscore ? 2 | 8 : 1 | 2 | 4 | 8;
+    out[4] = dscore ? 0 : S * L;
+    out[5] = dscore ? 0 : L;
+    return 0;
 }
 
 }  // extern "C"

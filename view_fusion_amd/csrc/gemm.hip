@@ -386,45 +386,114 @@ __global__ __launch_bounds__(256) void time_affine_bwd_x_sum_kernel(const float*
 
 }  // namespace
 
+namespace {
+
+// The plan of one vf_bgemm call: every decision the launcher takes on the host, made in ONE place (bgemm_plan below) that
+// vf_bgemm executes and vf_bgemm_plan reports.
+enum { BG_SLOW = 0, BG_TT = 1, BG_TF = 2, BG_FT = 3, BG_FF = 4 };      // bgemm_kernel | bgemm_v2_kernel<A_KC, B_KC>
+// why the fast kernels were refused: one bit per term of their predicate (0: a fast kernel runs)
+enum { BG_NO_A_UNIT = 1 << 0, BG_NO_B_UNIT = 1 << 1, BG_SCN = 1 << 2, BG_K4 = 1 << 3, BG_SAB4 = 1 << 4, BG_SBB4 = 1 << 5,
+       BG_SAM4 = 1 << 6, BG_SAK4 = 1 << 7, BG_M4 = 1 << 8, BG_SBN4 = 1 << 9, BG_SBK4 = 1 << 10, BG_N4 = 1 << 11,
+       BG_ALIGN16 = 1 << 12 };
+
+struct BgemmPlan {
+    int launches;         // 0: an empty product (batch, M or N <= 0), nothing runs
+    int variant;          // BG_*
+    int gx, gy, gz;       // grid
+    int xcd_batches;      // GemmArgs::xcd_batches (the fast kernels read it)
+    int refused;          // BG_* bits
+};
+
+BgemmPlan bgemm_plan(const void* A, const void* B, int batch, int M, int N, int K, long sAb, long sAm, long sAk, long sBb,
+                     long sBk, long sBn, long sCn) {
+    BgemmPlan p = {0, BG_SLOW, 0, 0, 0, 0, 0};
+    if (batch <= 0 || M <= 0 || N <= 0) return p;
+    p.launches = 1;
+    p.gx = (N + BN - 1) / BN; p.gy = (M + BM - 1) / BM; p.gz = batch;
+    static const bool xcd = !(getenv("VF_GEMM_XCD") && getenv("VF_GEMM_XCD")[0] == '0');     // (tuning aid)
+    p.xcd_batches = xcd ? batch / 8 : 0;
+    auto mul4 = [](long v) { return (v & 3) == 0; };
+    const bool a_kc = sAk == 1, a_mc = sAm == 1, b_kc = sBk == 1, b_nc = sBn == 1;
+    int r = 0;
+    if (!(a_kc || a_mc)) r |= BG_NO_A_UNIT;
+    if (!(b_kc || b_nc)) r |= BG_NO_B_UNIT;
+    if (sCn != 1) r |= BG_SCN;
+    if (!mul4(K)) r |= BG_K4;
+    if (!mul4(sAb)) r |= BG_SAB4;
+    if (!mul4(sBb)) r |= BG_SBB4;
+    if (a_kc) { if (!mul4(sAm)) r |= BG_SAM4; }
+    else { if (!mul4(sAk)) r |= BG_SAK4; if (!mul4(M)) r |= BG_M4; }
+    if (b_kc) { if (!mul4(sBn)) r |= BG_SBN4; }
+    else { if (!mul4(sBk)) r |= BG_SBK4; if (!mul4(N)) r |= BG_N4; }
+    if (((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15) != 0) r |= BG_ALIGN16;
+    p.refused = r;
+    if (r == 0) p.variant = a_kc ? (b_kc ? BG_TT : BG_TF) : (b_kc ? BG_FT : BG_FF);
+    return p;
+}
+
+// softmax_fwd_kernel<MAXV> / softmax_bwd_kernel<MAXV>: a wave holds a row of at most 64 MAXV columns; 0: refused
+int softmax_maxv(int cols) {
+    return cols <= 64 ? 1 : cols <= 256 ? 4 : cols <= 1024 ? 16 : cols <= 4096 ? 64 : 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int vf_bgemm(const float* A, const float* B, float* C, const float* bias, int batch, int M, int N, int K,
              long sAb, long sAm, long sAk, long sBb, long sBk, long sBn, long sCb, long sCm, long sCn,
              float alpha, float beta, void* stream) {
-    if (batch <= 0 || M <= 0 || N <= 0) return 0;
+    const BgemmPlan p = bgemm_plan(A, B, batch, M, N, K, sAb, sAm, sAk, sBb, sBk, sBn, sCn);
+    if (!p.launches) return 0;
     GemmArgs g;
     g.A = A; g.B = B; g.C = C; g.bias = bias; g.M = M; g.N = N; g.K = K;
     g.sAb = sAb; g.sAm = sAm; g.sAk = sAk; g.sBb = sBb; g.sBk = sBk; g.sBn = sBn;
     g.sCb = sCb; g.sCm = sCm; g.sCn = sCn; g.alpha = alpha; g.beta = beta;
-    const dim3 grid((N + BN - 1) / BN, (M + BM - 1) / BM, batch);
+    g.xcd_batches = p.xcd_batches;
+    const dim3 grid(p.gx, p.gy, p.gz);
     hipStream_t st = (hipStream_t)stream;
-    static const bool xcd = !(getenv("VF_GEMM_XCD") && getenv("VF_GEMM_XCD")[0] == '0');     // (tuning aid)
-    g.xcd_batches = xcd ? batch / 8 : 0;
-    auto mul4 = [](long v) { return (v & 3) == 0; };
-    const bool a_kc = sAk == 1, a_mc = sAm == 1, b_kc = sBk == 1, b_nc = sBn == 1;
-    const bool fast = (a_kc || a_mc) && (b_kc || b_nc) && sCn == 1 && mul4(K) && mul4(sAb) && mul4(sBb) &&
-                      (a_kc ? mul4(sAm) : (mul4(sAk) && mul4(M))) && (b_kc ? mul4(sBn) : (mul4(sBk) && mul4(N))) &&
-                      ((reinterpret_cast<size_t>(A) | reinterpret_cast<size_t>(B)) & 15) == 0;
-    if (fast) {
-        if (a_kc && b_kc) hipLaunchKernelGGL((bgemm_v2_kernel<true, true>), grid, dim3(256), 0, st, g);
-        else if (a_kc) hipLaunchKernelGGL((bgemm_v2_kernel<true, false>), grid, dim3(256), 0, st, g);
-        else if (b_kc) hipLaunchKernelGGL((bgemm_v2_kernel<false, true>), grid, dim3(256), 0, st, g);
-        else hipLaunchKernelGGL((bgemm_v2_kernel<false, false>), grid, dim3(256), 0, st, g);
-        VF_RETURN_LAST_ERROR();
+    switch (p.variant) {
+    case BG_TT: hipLaunchKernelGGL((bgemm_v2_kernel<true, true>), grid, dim3(256), 0, st, g); break;
+    case BG_TF: hipLaunchKernelGGL((bgemm_v2_kernel<true, false>), grid, dim3(256), 0, st, g); break;
+    case BG_FT: hipLaunchKernelGGL((bgemm_v2_kernel<false, true>), grid, dim3(256), 0, st, g); break;
+    case BG_FF: hipLaunchKernelGGL((bgemm_v2_kernel<false, false>), grid, dim3(256), 0, st, g); break;
+    default: hipLaunchKernelGGL(bgemm_kernel, grid, dim3(256), 0, st, g); break;
     }
-    hipLaunchKernelGGL(bgemm_kernel, grid, dim3(256), 0, st, g);
     VF_RETURN_LAST_ERROR();
+}
+
+// Host only, launches nothing: the plan vf_bgemm executes for these arguments (A and B count by their alignment alone) ->
+// out[7] = {launches (0: an empty product), variant (0 bgemm_kernel, 1..4 bgemm_v2_kernel<A_KC, B_KC> = <1,1> <1,0> <0,1>
+// <0,0>), grid x, y, z, xcd_batches, the refused terms of the fast kernels' predicate as bits (0 where one runs)}.
+int vf_bgemm_plan(const void* A, const void* B, int batch, int M, int N, int K, long sAb, long sAm, long sAk, long sBb,
+                  long sBk, long sBn, long sCn, int* out) {
+    if (!out) return (int)hipErrorInvalidValue;
+    const BgemmPlan p = bgemm_plan(A, B, batch, M, N, K, sAb, sAm, sAk, sBb, sBk, sBn, sCn);
+    const int v[7] = {p.launches, p.variant, p.gx, p.gy, p.gz, p.xcd_batches, p.refused};
+    for (int i = 0; i < 7; ++i) out[i] = v[i];
+    return 0;
+}
+
+// Host only: MAXV of the softmax_fwd_kernel / softmax_bwd_kernel instantiation both launchers take at `cols` (1, 4, 16, 64;
+// 0 above 4096 columns: refused) and their grid -> out[2] = {MAXV, workgroups (four rows each; 0 for rows <= 0)}.
+int vf_softmax_plan(int rows, int cols, int* out) {
+    if (!out) return (int)hipErrorInvalidValue;
+    out[0] = softmax_maxv(cols);
+    out[1] = rows > 0 ? (rows + 3) / 4 : 0;
+    return 0;
 }
 
 int vf_softmax_fwd(const float* x, float* y, int rows, int cols, void* stream) {
     if (rows <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((rows + 3) / 4), blk(256);
-    if (cols <= 64) hipLaunchKernelGGL(softmax_fwd_kernel<1>, grid, blk, 0, st, x, y, rows, cols);
-    else if (cols <= 256) hipLaunchKernelGGL(softmax_fwd_kernel<4>, grid, blk, 0, st, x, y, rows, cols);
-    else if (cols <= 1024) hipLaunchKernelGGL(softmax_fwd_kernel<16>, grid, blk, 0, st, x, y, rows, cols);
-    else if (cols <= 4096) hipLaunchKernelGGL(softmax_fwd_kernel<64>, grid, blk, 0, st, x, y, rows, cols);
-    else return (int)hipErrorInvalidValue;
+    switch (softmax_maxv(cols)) {
+    case 1: hipLaunchKernelGGL(softmax_fwd_kernel<1>, grid, blk, 0, st, x, y, rows, cols); break;
+    case 4: hipLaunchKernelGGL(softmax_fwd_kernel<4>, grid, blk, 0, st, x, y, rows, cols); break;
+    case 16: hipLaunchKernelGGL(softmax_fwd_kernel<16>, grid, blk, 0, st, x, y, rows, cols); break;
+    case 64: hipLaunchKernelGGL(softmax_fwd_kernel<64>, grid, blk, 0, st, x, y, rows, cols); break;
+    default: return (int)hipErrorInvalidValue;
+    }
     VF_RETURN_LAST_ERROR();
 }
 
@@ -432,11 +501,13 @@ int vf_softmax_bwd(const float* y, const float* dy, float* dx, int rows, int col
     if (rows <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((rows + 3) / 4), blk(256);
-    if (cols <= 64) hipLaunchKernelGGL(softmax_bwd_kernel<1>, grid, blk, 0, st, y, dy, dx, rows, cols);
-    else if (cols <= 256) hipLaunchKernelGGL(softmax_bwd_kernel<4>, grid, blk, 0, st, y, dy, dx, rows, cols);
-    else if (cols <= 1024) hipLaunchKernelGGL(softmax_bwd_kernel<16>, grid, blk, 0, st, y, dy, dx, rows, cols);
-    else if (cols <= 4096) hipLaunchKernelGGL(softmax_bwd_kernel<64>, grid, blk, 0, st, y, dy, dx, rows, cols);
-    else return (int)hipErrorInvalidValue;
+    switch (softmax_maxv(cols)) {
+    case 1: hipLaunchKernelGGL(softmax_bwd_kernel<1>, grid, blk, 0, st, y, dy, dx, rows, cols); break;
+    case 4: hipLaunchKernelGGL(softmax_bwd_kernel<4>, grid, blk, 0, st, y, dy, dx, rows, cols); break;
+    case 16: hipLaunchKernelGGL(softmax_bwd_kernel<16>, grid, blk, 0, st, y, dy, dx, rows, cols); break;
+    case 64: hipLaunchKernelGGL(softmax_bwd_kernel<64>, grid, blk, 0, st, y, dy, dx, rows, cols); break;
+    default: return (int)hipErrorInvalidValue;
+    }
     VF_RETURN_LAST_ERROR();
 }
 

@@ -44,7 +44,7 @@ from .dense import (  # noqa: F401
     time_affine_all
 )
 from .attention import (  # noqa: F401
-    _AttentionFn, _AttentionStreamFn, _ConcatFn, attention, attention_route, attention_streaming, concat_channels
+    _AttentionFn, _AttentionStreamFn, _ConcatFn, attention, attention_bwd_route, attention_route, attention_streaming, concat_channels
 )
 from .diffusion import (  # noqa: F401
     _ComposeLossFn, _ComposeLossOptFn, compose, compose_loss, compose_mse_loss, draw_train, gather_level, p_sample_tail, philox_ids, psnr, randn_ids,

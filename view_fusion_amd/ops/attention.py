@@ -45,18 +45,17 @@ class _AttentionFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         dS = torch.empty_like(P)
         st._KIND_OVERRIDE = "attn_bwd" if st.KERNEL_LOG is not None else None
-        fused_dq = False
-        if L == 256 and C % 32 == 0 and st.ATTN_DSCORE:
+        fused_dq, fused_dvdk = attention_bwd_route(C, L)
+        if fused_dq:
             # one launch (round 5): dS = P o (dP - rowsum(P o dP)) with dP[i][j] = sum_c dO[c][i] v[c][j] never written,
             # and dQ[c][i] = alpha sum_j k[c][j] dS[i][j] from the dS values still in registers
             _call("vf_attention_dscore", _ptr(qkv), _ptr(dO), _ptr(P), _ptr(dS), _ptr(dqkv), S, C, L, _stream(),
                   flops=4.0 * S * L * L * C)
-            fused_dq = True
         else:
             # dP[i][j] = sum_c dO[c][i] v[c][j]
             _bgemm(dO, qkv, dS, None, S, L, L, C, (C * L, 1, L), (C3 * L, L, 1), (L * L, L, 1), offB=2 * C * L)
             _call("vf_softmax_bwd", _ptr(P), _ptr(dS), _ptr(dS), S * L, L, _stream())
-        if fused_dq and C % 64 == 0 and st.ATTN_DVDK:
+        if fused_dvdk:
             # dV and dK (below) in one launch of a kernel written for these two products (round 5)
             _call("vf_attention_dvdk", _ptr(qkv), _ptr(dO), _ptr(P), _ptr(dS), _ptr(dqkv), S, C, L, _stream(),
                   flops=4.0 * S * L * L * C)
@@ -86,6 +85,15 @@ def attention_route(C, L):
     if L in (64, 256) and C % 32 == 0:
         return "fused"
     return "generic"
+
+
+def attention_bwd_route(C, L):
+    """(dscore, dvdk): whether _AttentionFn.backward runs vf_attention_dscore (dS + dQ in one launch) and
+    vf_attention_dvdk (dV + dK in one launch) at a (C, L) map; every product a kernel does not take is a vf_bgemm call, and
+    without dscore the softmax backward is a launch of its own.  The library states the same route (vf_attention_bwd_plan);
+    tests/test_attn_plan_host.py holds the two together."""
+    dscore = L == 256 and C % 32 == 0 and bool(st.ATTN_DSCORE)
+    return dscore, dscore and C % 64 == 0 and bool(st.ATTN_DVDK)
 
 
 class _AttentionStreamFn(torch.autograd.Function):
