@@ -213,6 +213,17 @@ int vf_wino44_conv_fill_pct(int S, int Cin, int Cout, int H, int W, int* tiles_o
 int vf_wino44_conv_fwd(const float* x, const float* u_packed, const float* bias, const float* view_bias,
                        const float* residual, float* y, float* ws, long ws_floats, int S, int Cin, int Cout, int H,
                        int W, int mode, void* stream);
+/* Host-only query (touches no device, launches nothing): the plan vf_wino_conv_fwd (kind 1) / vf_wino44_conv_fwd
+ * (kind 2; ops.wino_kind's codes) takes for these arguments; has_ws: a workspace of ws_floats floats is passed.  The
+ * launchers execute the function that answers.  out[8] = { T: workgroup tiles of the launch (tile groups x 64-channel
+ * tiles);  nch: 8-channel K chunks;  nfull: tiles [0, nfull) are computed whole;  split: K ranges per tail tile AFTER the
+ * clamp by the workspace (parts that do not fit, or no workspace: nfull = T, split = 1, the plain grid);  per: chunks per
+ * K range (the last may be shorter);  npers: persistent workgroups = min(nfull, 256);  workgroups of the conv launch
+ * = npers + (T - nfull) * split;  workgroups of the fix-up launch, 0: none }.  vf_wino_conv_fwd_gn runs the same conv
+ * launch and chooses its GroupNorm fix-up's grid itself.  Returns hipErrorInvalidValue for S <= 0, out == NULL and a
+ * size / mode the kind does not support. */
+int vf_wino_conv_plan(int kind, int S, int Cin, int Cout, int H, int W, int mode, int has_ws, long ws_floats,
+                      int* out /*[8]*/);
 /* weight gradient of a stride-1 3x3 conv (modes 0 and 2, output H = W in {8,16,32,64}) through the same
  * transform: dU = sum over tiles of (A dY A^T) (B^T d B)^T per Winograd slice, split over tile ranges into `ws`
  * slabs that are summed in a fixed order, then dW = G^T dU G */

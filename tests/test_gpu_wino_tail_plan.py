@@ -64,13 +64,25 @@ def _judge_all(label, names, got, r64, r32, tols):
     assert all(r[4] for r in rows), [(r[0], r[1], r[3]) for r in rows if not r[4]]
 
 
-def _confirm_plan(lib, c):
-    """The library's own host functions give this launch the plan the case list claims."""
+def _confirm_plan(lib, c, ws=None):
+    """The library's own host functions give this launch the plan the case list claims -- vf_wino_conv_plan, the function
+    the launcher executes, included: describe()'s plan with the workspace the launch asks for (ws = None), the plain grid
+    with the (has_ws, floats) a fallback case passes."""
     d = wp.describe(c.kernel, c.S, c.Cin, c.Cout, c.H, c.H)
     tiles = ctypes.c_int(0)
     getattr(lib, ABI[c.kernel][4])(c.S, c.Cin, c.Cout, c.H, c.H, ctypes.byref(tiles))
     need = getattr(lib, ABI[c.kernel][3])(c.S, c.Cin, c.Cout, c.H, c.H)
     assert tiles.value == d["T"] and need == d["parts"] * wp.PART_FLOATS[c.kernel], (wp.case_id(c), d, tiles.value, need)
+    has_ws, nws = (1, need) if ws is None else ws
+    out = (ctypes.c_int * 8)()
+    rc = lib.vf_wino_conv_plan(wp.KIND[c.kernel], c.S, c.Cin, c.Cout, c.H, c.H, {"same": 0, "up2": 2}[c.mode], has_ws, nws,
+                               ctypes.cast(out, ctypes.c_void_p))
+    plan = dict(zip(wp.PLAN_FIELDS, out))
+    assert rc == 0 and plan == wp.launch_plan(c.kernel, c.S, c.Cin, c.Cout, c.H, c.H, has_ws, nws), (wp.case_id(c), rc, plan)
+    if has_ws and nws >= need:
+        assert all(plan[k] == d[k] for k in ("T", "nch", "nfull", "split", "per")), (wp.case_id(c), d, plan)
+    else:
+        assert (plan["T"], plan["nch"], plan["nfull"], plan["split"], plan["fixup_grid"]) == (d["T"], d["nch"], d["T"], 1, 0), plan
     return d, need
 
 
@@ -121,6 +133,7 @@ def _abi_launch(lib, dev, c, t, ws_mode):
     y = torch.full((c.S, c.Cout, c.H, c.H), float("nan"), device=dev)
     ws = torch.full((need + GUARD,), float("nan"), device=dev)
     wsp, nws = {"guard": (_ptr(ws), need), "null": (None, 0), "short": (_ptr(ws), need - 1)}[ws_mode]
+    _confirm_plan(lib, c, (int(wsp is not None), nws))
     rc = f_conv(_ptr(g["x"]), _ptr(uf), _ptr(g["b"]), _ptr(g["vb"]), _ptr(g["res"]), _ptr(y), wsp, nws, c.S, c.Cin, c.Cout,
                 c.H, c.H, m, _stream())
     torch.cuda.synchronize()

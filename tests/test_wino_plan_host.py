@@ -1,5 +1,6 @@
 """The Winograd K-split tail plan on the CPU: tests/wino_plan_ref.py's restatement equals the host functions of
-libvf_hip.so over a grid of shapes, the plan's invariants hold on that grid, every plan class the SMALL / TINY layers reach
+libvf_hip.so over a grid of shapes -- vf_wino_conv_plan, the function the launchers execute, under every workspace, and
+the policy's cycle model that reads it --, the plan's invariants hold on that grid, every plan class the SMALL / TINY layers reach
 (both directions, S = 1 .. 368) is in wino_plan_ref.cases() -- the list tests/test_gpu_wino_tail_plan.py runs -- and the
 comparison rule of those tests rejects two wrong K-splits on the inputs they use."""
 import ctypes
@@ -61,6 +62,88 @@ def test_restatement_equals_the_library_and_the_plan_keeps_its_invariants(lib, k
             assert split == 1, at
         n += 1
     assert n == len(wp.MAPS[kernel]) * len(GRID_S) * len(GRID_CIN) * len(GRID_COUT)
+
+
+def _ask(lib, kernel, S, Cin, Cout, W, mode, has_ws, ws, out=None):
+    """vf_wino_conv_plan -> (rc, dict of PLAN_FIELDS)."""
+    out = (ctypes.c_int * 8)() if out is None else out
+    rc = lib.vf_wino_conv_plan(wp.KIND[kernel], S, Cin, Cout, W, W, mode, has_ws, ws, ctypes.cast(out, ctypes.c_void_p))
+    return rc, dict(zip(wp.PLAN_FIELDS, out))
+
+
+@pytest.mark.parametrize("kernel", wp.KERNELS)
+def test_the_plan_query_equals_the_restatement_under_every_workspace(lib, kernel):
+    """vf_wino_conv_plan -- the function the launchers execute -- field for field, with the workspace at the priced size,
+    one float short of it (the plain grid), at zero and absent; the unclamped plan is the one *_conv_ws_floats prices."""
+    f_ws = getattr(lib, LIB[kernel][0])
+    out = (ctypes.c_int * 8)()
+    n = split = 0
+    for S, Cin, Cout, W in _grid(kernel):
+        d = wp.describe(kernel, S, Cin, Cout, W, W)
+        need = f_ws(S, Cin, Cout, W, W)
+        assert need == d["parts"] * wp.PART_FLOATS[kernel], (kernel, S, Cin, Cout, W)
+        for has_ws, ws in ((1, need), (1, need - 1), (1, 0), (0, need), (0, 0)):
+            if ws < 0:
+                continue
+            want = wp.launch_plan(kernel, S, Cin, Cout, W, W, has_ws, ws)
+            assert _ask(lib, kernel, S, Cin, Cout, W, 0, has_ws, ws, out) == (0, want), (kernel, S, Cin, Cout, W, has_ws, ws)
+            if (has_ws, ws) == (1, need):                   # the priced workspace runs the plan describe() states
+                assert all(want[k] == d[k] for k in ("T", "nch", "nfull", "split", "per")), (kernel, S, Cin, Cout, W)
+                assert (want["conv_grid"] - want["npers"]) * wp.PART_FLOATS[kernel] == need
+                assert _ask(lib, kernel, S, Cin, Cout, W, 2, 1, need, out) == (0, want)     # the mode plays no part
+            elif d["split"] > 1:                            # anything less: every tile whole, no fix-up
+                assert (want["nfull"], want["split"], want["fixup_grid"]) == (d["T"], 1, 0)
+                assert want["conv_grid"] == want["npers"] == min(d["T"], wp.SLOTS)
+        split += d["split"] > 1
+        n += 1
+    assert n == len(wp.MAPS[kernel]) * len(GRID_S) * len(GRID_CIN) * len(GRID_COUT) and split > 0
+
+
+def test_the_plan_query_refuses_what_the_entries_refuse(lib):
+    out = (ctypes.c_int * 8)()
+    for kernel in wp.KERNELS:
+        for H in (4, 8, 12, 16, 32, 48, 64, 128):
+            for W in (8, 16, 32, 64, 128):
+                for mode in (0, 1, 2, 4):
+                    rc = lib.vf_wino_conv_plan(wp.KIND[kernel], 2, 64, 64, H, W, mode, 0, 0, ctypes.cast(out, ctypes.c_void_p))
+                    assert (rc == 0) == wp.supported(kernel, H, W, mode), (kernel, H, W, mode, rc)
+                    assert rc in (0, 1)
+        W = wp.MAPS[kernel][-1]
+        assert _ask(lib, kernel, 2, 64, 64, W, 0, 0, 0)[0] == 0
+        assert _ask(lib, kernel, 0, 64, 64, W, 0, 0, 0)[0] == 1 and _ask(lib, kernel, -1, 64, 64, W, 0, 0, 0)[0] == 1
+        assert lib.vf_wino_conv_plan(wp.KIND[kernel], 2, 64, 64, W, W, 0, 0, 0, None) == 1
+    for kind in (0, 3):
+        assert lib.vf_wino_conv_plan(kind, 2, 64, 64, 32, 32, 0, 0, 0, ctypes.cast(out, ctypes.c_void_p)) == 1
+
+
+def test_policy_cycles_equal_the_restated_cost_model(lib):
+    """ops.policy._wino_cycles reads the plan from vf_wino_conv_plan; the figure is the restated model's, bit for bit."""
+    from view_fusion_amd.ops import policy
+    assert {k: policy._WINO_COST[wp.KIND[k]] for k in wp.KERNELS} == wp.WINO_COST
+    n = 0
+    for kernel in wp.KERNELS:
+        for S, Cin, Cout, W in _grid(kernel):
+            assert policy._wino_cycles(wp.KIND[kernel], S, Cin, Cout, W, W) == wp.cycles(kernel, S, Cin, Cout, W, W), (kernel, S, Cin, Cout, W)
+            n += 1
+    assert n == 6 * len(GRID_S) * len(GRID_CIN) * len(GRID_COUT)
+
+
+def test_abi_has_the_plan_entry(lib):
+    """The header declaration, the ctypes signature and the definition agree in argument count."""
+    import os
+    import re
+    from view_fusion_amd import _lib
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "vf_hip.h")).read()
+    source = open(os.path.join(root, "view_fusion_amd", "csrc", "winograd24.hip")).read()
+    arity = lambda m: len(re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S).split(","))
+    decl = re.search(r"\bint\s+vf_wino_conv_plan\s*\(([^;{]*)\)\s*;", header)
+    defn = re.search(r"\bint\s+vf_wino_conv_plan\s*\(([^;{]*)\)\s*\{", source)
+    assert decl, "vf_wino_conv_plan is not declared in include/vf_hip.h"
+    assert defn, "vf_wino_conv_plan is not defined in csrc/winograd24.hip"
+    assert arity(decl) == arity(defn) == len(_lib.SIGNATURES["vf_wino_conv_plan"]) == 10 and hasattr(lib, "vf_wino_conv_plan")
+    I_, L_, P_ = _lib._I, _lib._L, _lib._P
+    assert _lib.SIGNATURES["vf_wino_conv_plan"] == [I_] * 8 + [L_, P_]
 
 
 def test_shape_predicates_equal_the_library(lib):

@@ -4,8 +4,9 @@ plan-class enumeration behind tests/test_gpu_wino_tail_plan.py, and the inputs /
 
 A launch of T = tile groups x ceil(Cout/64) workgroup tiles over nch = ceil(Cin/8) chunks computes tiles [0, nfull) whole
 on 256 persistent workgroups; each of the R = T - nfull tail tiles is cut into `split` K ranges [p per, min(nch, (p+1) per)),
-per = ceil(nch/split), whose raw partial outputs a fix-up launch sums.  The coverage key of a launch is its plan class
-(kernel, map width, split, last range shorter than `per`).
+per = ceil(nch/split), whose raw partial outputs a fix-up launch sums -- unless the workspace passed cannot hold them: then
+every tile is computed whole (launch_plan).  The coverage key of a launch is its plan class (kernel, map width, split,
+last range shorter than `per`).
 
 tests/test_wino_plan_host.py pins every function here to libvf_hip.so's host functions over a grid and checks that every
 class the SMALL / TINY layers reach is in cases().  Imports no GPU code."""
@@ -132,6 +133,40 @@ def describe(kernel, S, Cin, Cout, H, W):
     per = (nch + split - 1) // split
     R = T - nfull
     return dict(T=T, nch=nch, nfull=nfull, R=R, split=split, per=per, last=nch - (split - 1) * per, parts=R * split)
+
+
+KIND = {"nested": 1, "f44": 2}                                   # vf_wino_conv_plan's `kind` (ops.wino_kind's codes)
+PLAN_FIELDS = ("T", "nch", "nfull", "split", "per", "npers", "conv_grid", "fixup_grid")      # ... and its out[8]
+FIXUP_FLOATS = {"nested": 8, "f44": 4}                           # outputs one fix-up thread finishes (a 2x4 tile / a tile row)
+
+
+def launch_plan(kernel, S, Cin, Cout, H, W, has_ws, ws):
+    """vf_wino_conv_plan = csrc/wino_plan.h:wino_launch_plan, what the launchers execute: describe() after the clamp by the
+    workspace actually passed (the parts do not fit, or no workspace: every tile whole), and the two grids."""
+    d = describe(kernel, S, Cin, Cout, H, W)
+    T, nch, nfull, split = d["T"], d["nch"], d["nfull"], d["split"]
+    if not has_ws or d["parts"] * PART_FLOATS[kernel] > ws:
+        nfull, split = T, 1
+    nt, npers = T - nfull, min(nfull, SLOTS)
+    return dict(T=T, nch=nch, nfull=nfull, split=split, per=(nch + split - 1) // split, npers=npers, conv_grid=npers + nt * split,
+                fixup_grid=(nt * PART_FLOATS[kernel] // FIXUP_FLOATS[kernel] + 255) // 256)
+
+
+# shader cycles per chunk of a workgroup tile, prologue + epilogue in chunk-times (ops/policy.py:_WINO_COST)
+WINO_COST = {"nested": (3340.0, 4.2), "f44": (5390.0, 4.7)}
+
+
+def cycles(kernel, S, Cin, Cout, H, W):
+    """ops/policy.py:_wino_cycles, the model behind the choice between the two kernels: whole rounds of 256 tiles of
+    (nch + F) chunk-times; a split tail runs ceil(parts / 256) rounds of (per + F), writes and re-reads its raw partials
+    (2.5 passes at 2000 bytes per cycle) and pays 8000 cycles of fix-up launch."""
+    ch, F = WINO_COST[kernel]
+    d = describe(kernel, S, Cin, Cout, H, W)
+    T, nch, parts = d["T"], d["nch"], d["parts"]
+    if parts == 0:
+        return -(-T // SLOTS) * (nch + F) * ch
+    cyc = (T // SLOTS) * (nch + F) * ch + -(-parts // SLOTS) * (d["per"] + F) * ch
+    return cyc + parts * PART_FLOATS[kernel] * 4 * 2.5 / 2000.0 + 8000.0
 
 
 def plan_class(kernel, S, Cin, Cout, H, W):

@@ -68,6 +68,7 @@ SIGNATURES = {
     "vf_wino44_conv_ws_floats": [_I, _I, _I, _I, _I],
     "vf_wino44_conv_fill_pct": [_I, _I, _I, _I, _I, ctypes.POINTER(_I)],
     "vf_wino44_conv_fwd": [_P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],
+    "vf_wino_conv_plan": [_I, _I, _I, _I, _I, _I, _I, _I, _L, _P],
     "vf_wino_wgrad_ws_floats": [_I, _I, _I, _I, _I],
     "vf_wino_wgrad_supported": [_I, _I, _I],
     "vf_wino_wgrad": [_P, _P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _I, _I, _P],

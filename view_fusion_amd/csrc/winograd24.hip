@@ -23,32 +23,15 @@
 //   * the epilogue applies A4 per wave in registers, the four row waves exchange their 2x4 partial tiles through LDS
 //     once (A2), every wave finishes a quarter of the channels: bias + per-view bias + residual, float4 row stores.
 // MODE 0: plain input; MODE 2: nearest-x2-upsampled input (Upsample conv), as in conv.hip.
-#include "common.h"
-#include "wino_plan.h"
+#include "wino_pack.h"
 
 namespace {
 
-constexpr int WTCO = 64;      // output channels per workgroup
-constexpr int WTT = 32;       // 2x4 output tiles per workgroup
-constexpr int WCK = 8;        // input channels per chunk
-constexpr int NSL = 24;       // Winograd slices (4 transformed rows x 6 transformed columns)
-constexpr int WINO_PERSIST = 256;     // one persistent workgroup per CU
-
-struct WinoArgs {
-    const float* x;
-    const float* u;       // packed transformed weights
-    const float* bias;
-    const float* vbias;
-    const float* res;
-    float* y;
-    int S, Cin, Cout, CinP, CoutP;
-    // tail splitting (small maps): tiles [0, nfull) are computed whole (by the persistent workgroups); workgroup
-    // npers + j*tail_split + p computes the p-th K range of tile nfull + j and leaves a raw partial output in ws
-    // (wino_fixup_kernel)
-    int nfull, tail_split;
-    float* ws;
-    int npers;            // persistent workgroups = min(nfull, WINO_PERSIST)
-};
+constexpr int WTCO = WinoNested::CO;      // output channels per workgroup
+constexpr int WTT = WinoNested::TT;       // 2x4 output tiles per workgroup
+constexpr int WCK = WinoNested::CK;       // input channels per chunk
+constexpr int NSL = WinoNested::SLICES;   // Winograd slices (4 transformed rows x 6 transformed columns)
+constexpr int WINO_PERSIST = WinoNested::PERSIST;     // one persistent workgroup per CU
 
 template <int LOGW, int MODE>
 struct WGeo {
@@ -74,7 +57,6 @@ struct WGeo {
     static __device__ __forceinline__ int t_col(int tl) { return tl % TWC; }
     static __device__ __forceinline__ int g_view(int wg) { return IPG == 1 ? wg / WPI : wg * IPG; }
     static __device__ __forceinline__ int g_row(int wg) { return IPG == 1 ? (wg % WPI) * 2 * TR : 0; }
-    static int groups(int S) { return IPG == 1 ? S * WPI : (S + IPG - 1) / IPG; }
 };
 
 #ifdef VF_STAMPS
@@ -620,34 +602,6 @@ __device__ __forceinline__ void wino_pack_group(const float* __restrict__ w, flo
     }
 }
 
-__global__ __launch_bounds__(512) void wino_pack_kernel(const float* __restrict__ w, float* __restrict__ uf,
-                                                        float* __restrict__ ub, int Cout, int Cin, size_t nf,
-                                                        size_t nb) {
-    wino_pack_group(w, uf, ub, Cout, Cin, nf, nb, blockIdx.x);
-}
-
-constexpr int PACK_BLOCKS = NSL * WTCO * WCK / 256;     // 256-output units per pack group (48)
-
-struct WPackDesc {
-    const float* w;
-    float* uf;
-    float* ub;
-    long long Cout, Cin, nf, nb, first_block;         // first_block in units of 256 outputs (48 per group)
-};
-__global__ __launch_bounds__(512) void wino_pack_multi_kernel(const WPackDesc* __restrict__ desc, int nlayers) {
-    const long long vb = (long long)blockIdx.x * PACK_BLOCKS;
-    int lo = 0, hi = nlayers;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (desc[mid].first_block <= vb) lo = mid; else hi = mid;
-    }
-    const WPackDesc d = desc[lo];
-    wino_pack_group(d.w, d.uf, d.ub, (int)d.Cout, (int)d.Cin, (size_t)d.nf, (size_t)d.nb,
-                    (size_t)((vb - d.first_block) / PACK_BLOCKS));
-}
-
-inline int rup(int v, int m) { return (v + m - 1) / m * m; }
-
 // Sums the K-range partials of the tail tiles in a fixed order and applies the epilogue
 // (bias + per-view bias + residual).  One thread per (tail tile, co, 2x4 tile).
 template <int LOGW>
@@ -817,12 +771,6 @@ __global__ __launch_bounds__(512) void wino_fixup_gn_kernel(WinoArgs a, const fl
     }
 }
 
-// tiles of a launch: groups of 32 output tiles (256 pixels) x 64-channel tiles
-inline int wino_groups(int S, int H, int W) {
-    const int tiles = (H / 2) * (W / 4);
-    return tiles >= WTT ? S * (tiles / WTT) : (S + WTT / tiles - 1) / (WTT / tiles);
-}
-
 struct WinoGn {                      // GroupNorm(+Swish) behind the conv, evaluated by the fix-up launch (or gamma = null)
     const float* gamma = nullptr;
     const float* beta = nullptr;
@@ -831,30 +779,12 @@ struct WinoGn {                      // GroupNorm(+Swish) behind the conv, evalu
     float eps = 0.f;
 };
 
-// Can the fix-up launch of this shape evaluate the GroupNorm?  Every tile a K-split tail tile, maps of
-// at least 16x16 (one view per workgroup), a (view, group) of at most 2048 2x4 tiles.
-inline bool wino_gn_fusable(int S, int Cin, int Cout, int H, int W, int groups) {
-    if (W < 16 || groups <= 0 || Cout % groups != 0) return false;
-    const int T = wino_groups(S, H, W) * (rup(Cout, WTCO) / WTCO);
-    int nfull, split;
-    wino_tail_plan(T, rup(Cin, WCK) / WCK, &nfull, &split);
-    return nfull == 0 && split >= 2 && split <= 8 && (long)(Cout / groups) * (H * W / 8) <= 2048;
-}
-
 template <int LOGW, int MODE>
-int launch_wino(WinoArgs a, size_t ws_floats, hipStream_t st, const WinoGn& gn = WinoGn()) {
-    using G = WGeo<LOGW, MODE>;
-    const int T = G::groups(a.S) * (a.CoutP / WTCO);
-    wino_tail_plan(T, a.CinP / WCK, &a.nfull, &a.tail_split);
-    const int ntail = T - a.nfull;
-    if ((size_t)ntail * a.tail_split * WTCO * WTT * 8 > ws_floats || !a.ws) {   // no room: plain grid
-        a.nfull = T;
-        a.tail_split = 1;
-    }
-    const int nt = T - a.nfull;
-    if (gn.gamma && !(a.nfull == 0 && a.tail_split >= 2)) return (int)hipErrorInvalidValue;     // (callers ask wino_gn_fusable first)
-    a.npers = a.nfull < WINO_PERSIST ? a.nfull : WINO_PERSIST;
-    hipLaunchKernelGGL((wino_conv_kernel<LOGW, MODE>), dim3(a.npers + nt * a.tail_split), dim3(512), 0, st, a);
+int launch_wino(WinoArgs a, size_t ws_floats, hipStream_t st, const WinoGn& gn) {
+    const WinoLaunchPlan p = wino_launch_plan<WinoNested>(a.S, a.Cin, a.Cout, 1 << LOGW, 1 << LOGW, a.ws != nullptr, ws_floats);
+    if (gn.gamma && !p.all_split()) return (int)hipErrorInvalidValue;     // (callers ask vf_wino_conv_gn_fusable first)
+    a.nfull = p.nfull; a.tail_split = p.split; a.npers = p.npers;
+    hipLaunchKernelGGL((wino_conv_kernel<LOGW, MODE>), dim3(p.conv_grid), dim3(512), 0, st, a);
     if constexpr (LOGW >= 4) {
         if (gn.gamma) {
             const int cpg = a.Cout / gn.groups;
@@ -869,9 +799,24 @@ int launch_wino(WinoArgs a, size_t ws_floats, hipStream_t st, const WinoGn& gn =
             VF_RETURN_LAST_ERROR();
         }
     }
-    if (nt > 0)
-        hipLaunchKernelGGL((wino_fixup_kernel<LOGW>), dim3((nt * WTCO * WTT + 255) / 256), dim3(256), 0, st, a, nt);
+    if (p.fixup_grid > 0)
+        hipLaunchKernelGGL((wino_fixup_kernel<LOGW>), dim3(p.fixup_grid), dim3(256), 0, st, a, p.T - p.nfull);
     VF_RETURN_LAST_ERROR();
+}
+
+// the argument block and the instantiation for this map / mode, for both conv entries below
+int wino_conv(const float* x, const float* u, const float* bias, const float* vbias, const float* res, float* y, float* ws,
+              long ws_floats, int S, int Cin, int Cout, int W, int mode, void* stream, const WinoGn& gn) {
+    WinoArgs a;
+    a.x = x; a.u = u; a.bias = bias; a.vbias = vbias; a.res = res; a.y = y;
+    a.S = S; a.Cin = Cin; a.Cout = Cout; a.CinP = rup(Cin, WCK); a.CoutP = rup(Cout, WTCO);
+    a.ws = ws;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t nws = ws ? (size_t)ws_floats : 0;
+    if (W == 8) return mode == 0 ? launch_wino<3, 0>(a, nws, st, gn) : launch_wino<3, 2>(a, nws, st, gn);
+    if (W == 16) return mode == 0 ? launch_wino<4, 0>(a, nws, st, gn) : launch_wino<4, 2>(a, nws, st, gn);
+    if (W == 32) return mode == 0 ? launch_wino<5, 0>(a, nws, st, gn) : launch_wino<5, 2>(a, nws, st, gn);
+    return mode == 0 ? launch_wino<6, 0>(a, nws, st, gn) : launch_wino<6, 2>(a, nws, st, gn);
 }
 
 }  // namespace
@@ -879,52 +824,42 @@ int launch_wino(WinoArgs a, size_t ws_floats, hipStream_t st, const WinoGn& gn =
 extern "C" {
 
 int vf_wino_pack_sizes(int Cout, int Cin, long* fwd_floats, long* bwd_floats) {
-    *fwd_floats = (long)NSL * rup(Cin, WCK) * rup(Cout, WTCO);
-    *bwd_floats = (long)NSL * rup(Cout, WCK) * rup(Cin, WTCO);
-    return 0;
+    return wino_pack_sizes<WinoNested>(Cout, Cin, fwd_floats, bwd_floats);
 }
 
 int vf_wino_pack_weights(const float* w_oihw, float* u_fwd, float* u_bwd, int Cout, int Cin, void* stream) {
-    const size_t nf = (size_t)NSL * rup(Cin, WCK) * rup(Cout, WTCO);
-    const size_t nb = u_bwd ? (size_t)NSL * rup(Cout, WCK) * rup(Cin, WTCO) : 0;
-    hipLaunchKernelGGL(wino_pack_kernel, dim3((unsigned)((nf + nb) / (NSL * WTCO * WCK))), dim3(512), 0,
-                       (hipStream_t)stream, w_oihw, u_fwd, u_bwd, Cout, Cin, nf, nb);
-    VF_RETURN_LAST_ERROR();
+    return wino_pack_weights<WinoNested, wino_pack_group>(w_oihw, u_fwd, u_bwd, Cout, Cin, stream);
 }
 
 // desc: device int64 [nlayers][8] rows {w, u_fwd, u_bwd, Cout, Cin, fwd_floats, bwd_floats, first_block}
 int vf_wino_pack_weights_multi(const void* desc, int nlayers, long total_blocks, void* stream) {
-    if (nlayers <= 0 || total_blocks <= 0) return 0;
-    hipLaunchKernelGGL(wino_pack_multi_kernel, dim3((unsigned)(total_blocks / PACK_BLOCKS)), dim3(512), 0,
-                       (hipStream_t)stream, (const WPackDesc*)desc, nlayers);
-    VF_RETURN_LAST_ERROR();
+    return wino_pack_weights_multi<WinoNested, wino_pack_group>(desc, nlayers, total_blocks, stream);
 }
 
 // 1 if vf_wino_conv_fwd supports this (output) size / mode: 3x3 stride 1, H = W in {8, 16, 32, 64}, modes 0 / 2.
-int vf_wino_supported(int H, int W, int mode) {
-    return (H == W && (W == 8 || W == 16 || W == 32 || W == 64) && (mode == 0 || mode == 2)) ? 1 : 0;
-}
+int vf_wino_supported(int H, int W, int mode) { return WinoNested::supported(H, W, mode) ? 1 : 0; }
 
 // workspace floats vf_wino_conv_fwd wants for its split tail tiles (0 when the grid divides evenly)
 long vf_wino_conv_ws_floats(int S, int Cin, int Cout, int H, int W) {
-    const int T = wino_groups(S, H, W) * (rup(Cout, WTCO) / WTCO);
-    int nfull, split;
-    wino_tail_plan(T, rup(Cin, WCK) / WCK, &nfull, &split);
-    return (long)(T - nfull) * split * WTCO * WTT * 8;
+    return wino_launch_plan<WinoNested>(S, Cin, Cout, H, W, true, WINO_WS_ANY).ws_need;
 }
 
-// Expected CU fill (percent) of vf_wino_conv_fwd at this shape, and the tile count; hosts use it to choose between
-// this path and the direct kernel.  (Pure occupancy figure: the tail is priced WITHOUT the per-part overhead that
-// the launch's own plan uses, so the hosts' thresholds keep their meaning.)
+// Expected CU fill (percent) of vf_wino_conv_fwd at this shape, and the tile count (wino_fill_pct, wino_plan.h).
 int vf_wino_conv_fill_pct(int S, int Cin, int Cout, int H, int W, int* tiles_out) {
-    const int T = wino_groups(S, H, W) * (rup(Cout, WTCO) / WTCO);
-    const int nch = rup(Cin, WCK) / WCK;
-    int nfull, split;
-    wino_tail_plan(T, nch, &nfull, &split, 0.0);
-    if (tiles_out) *tiles_out = T;
-    if (T <= 0) return 0;
-    const double time = (nfull + WINO_SLOTS - 1) / WINO_SLOTS + (T > nfull ? wino_tail_time(T - nfull, split, nch, 0.0) : 0.0);
-    return (int)(100.0 * T / WINO_SLOTS / time);
+    return wino_fill_pct<WinoNested>(S, Cin, Cout, H, W, tiles_out);
+}
+
+// Host only, launches nothing: the plan vf_wino_conv_fwd (kind 1) / vf_wino44_conv_fwd (kind 2) executes with this
+// workspace -- wino_launch_plan, the function the launchers run.  out[8]: see include/vf_hip.h.
+int vf_wino_conv_plan(int kind, int S, int Cin, int Cout, int H, int W, int mode, int has_ws, long ws_floats, int* out) {
+    if (S <= 0 || !out) return (int)hipErrorInvalidValue;
+    WinoLaunchPlan p;
+    if (kind == 1 && WinoNested::supported(H, W, mode)) p = wino_launch_plan<WinoNested>(S, Cin, Cout, H, W, has_ws != 0, (size_t)ws_floats);
+    else if (kind == 2 && WinoF44::supported(H, W, mode)) p = wino_launch_plan<WinoF44>(S, Cin, Cout, H, W, has_ws != 0, (size_t)ws_floats);
+    else return (int)hipErrorInvalidValue;
+    const int v[8] = {p.T, p.nch, p.nfull, p.split, p.per, p.npers, p.conv_grid, p.fixup_grid};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
 }
 
 // y = conv3x3(x) (+bias +view_bias +residual), pad 1, stride 1, via the fused nested Winograd F(2,3) x F(4,3).
@@ -934,22 +869,16 @@ int vf_wino_conv_fwd(const float* x, const float* u_packed, const float* bias, c
                      int W, int mode, void* stream) {
     if (S <= 0) return 0;
     if (!vf_wino_supported(H, W, mode)) return (int)hipErrorInvalidValue;
-    WinoArgs a;
-    a.x = x; a.u = u_packed; a.bias = bias; a.vbias = view_bias; a.res = residual; a.y = y;
-    a.S = S; a.Cin = Cin; a.Cout = Cout; a.CinP = rup(Cin, WCK); a.CoutP = rup(Cout, WTCO);
-    a.ws = ws;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nws = ws ? (size_t)ws_floats : 0;
-    if (W == 8) return mode == 0 ? launch_wino<3, 0>(a, nws, st) : launch_wino<3, 2>(a, nws, st);
-    if (W == 16) return mode == 0 ? launch_wino<4, 0>(a, nws, st) : launch_wino<4, 2>(a, nws, st);
-    if (W == 32) return mode == 0 ? launch_wino<5, 0>(a, nws, st) : launch_wino<5, 2>(a, nws, st);
-    return mode == 0 ? launch_wino<6, 0>(a, nws, st) : launch_wino<6, 2>(a, nws, st);
+    return wino_conv(x, u_packed, bias, view_bias, residual, y, ws, ws_floats, S, Cin, Cout, W, mode, stream, WinoGn());
 }
 
 // 1 if vf_wino_conv_fwd_gn can evaluate GroupNorm(groups) in the conv's fix-up launch at this shape (the sampler at a few
-// views: every tile of the launch a K-split tail tile; 16x16 ... 64x64 maps)
+// views): every tile of the launch a K-split tail tile, maps of at least 16x16 (one view per workgroup; 16x16 ... 64x64),
+// a (view, group) of at most 2048 2x4 tiles.
 int vf_wino_conv_gn_fusable(int S, int Cin, int Cout, int H, int W, int mode, int groups) {
-    return (vf_wino_supported(H, W, mode) && wino_gn_fusable(S, Cin, Cout, H, W, groups)) ? 1 : 0;
+    if (!WinoNested::supported(H, W, mode) || W < 16 || groups <= 0 || Cout % groups != 0) return 0;
+    const WinoLaunchPlan p = wino_launch_plan<WinoNested>(S, Cin, Cout, H, W, true, WINO_WS_ANY);
+    return (p.all_split() && p.split <= 8 && (long)(Cout / groups) * (H * W / 8) <= 2048) ? 1 : 0;
 }
 
 // vf_wino_conv_fwd + a = [Swish](GroupNorm(groups, eps; gamma, beta)(y)) with the norm evaluated by the fix-up launch
@@ -962,17 +891,9 @@ int vf_wino_conv_fwd_gn(const float* x, const float* u_packed, const float* bias
     if (S <= 0) return 0;
     if (!vf_wino_conv_gn_fusable(S, Cin, Cout, H, W, mode, groups) || !ws || !gn_gamma || !gn_beta || !a_out)
         return (int)hipErrorInvalidValue;
-    WinoArgs a;
-    a.x = x; a.u = u_packed; a.bias = bias; a.vbias = view_bias; a.res = residual; a.y = y;
-    a.S = S; a.Cin = Cin; a.Cout = Cout; a.CinP = rup(Cin, WCK); a.CoutP = rup(Cout, WTCO);
-    a.ws = ws;
     WinoGn gn;
     gn.gamma = gn_gamma; gn.beta = gn_beta; gn.a_out = a_out; gn.groups = groups; gn.silu = silu; gn.store_y = store_y; gn.eps = eps;
-    hipStream_t st = (hipStream_t)stream;
-    const size_t nws = (size_t)ws_floats;
-    if (W == 16) return mode == 0 ? launch_wino<4, 0>(a, nws, st, gn) : launch_wino<4, 2>(a, nws, st, gn);
-    if (W == 32) return mode == 0 ? launch_wino<5, 0>(a, nws, st, gn) : launch_wino<5, 2>(a, nws, st, gn);
-    return mode == 0 ? launch_wino<6, 0>(a, nws, st, gn) : launch_wino<6, 2>(a, nws, st, gn);
+    return wino_conv(x, u_packed, bias, view_bias, residual, y, ws, ws_floats, S, Cin, Cout, W, mode, stream, gn);
 }
 
 }  // extern "C"

@@ -31,16 +31,15 @@
 //     per-view bias + residual, float4 row stores); the next tile's first loads go out before any store, its raw rows and
 //     V(0) are staged in the last two phases.
 // MODE 0: plain input; MODE 2: nearest-x2-upsampled input (Upsample conv), as in conv.hip.
-#include "common.h"
-#include "wino_plan.h"
+#include "wino_pack.h"
 
 namespace {
 
-constexpr int FCO = 64;       // output channels per workgroup
-constexpr int FTT = 32;       // 4x4 output tiles per workgroup
-constexpr int FCK = 8;        // input channels per chunk
-constexpr int FNS = 36;       // Winograd slices
-constexpr int F44_PERSIST = 256;
+constexpr int FCO = WinoF44::CO;        // output channels per workgroup
+constexpr int FTT = WinoF44::TT;        // 4x4 output tiles per workgroup
+constexpr int FCK = WinoF44::CK;        // input channels per chunk
+constexpr int FNS = WinoF44::SLICES;    // Winograd slices
+constexpr int F44_PERSIST = WinoF44::PERSIST;
 
 // slice (transformed row a, transformed column b) -> position p in wave order
 __host__ __device__ constexpr int f44_p(int a, int b) {
@@ -48,20 +47,7 @@ __host__ __device__ constexpr int f44_p(int a, int b) {
          : a == 4 ? (b < 3 ? 24 + b : 30 + b) : 27 + b;
 }
 
-struct F44Args {
-    const float* x;
-    const float* u;       // packed transformed weights
-    const float* bias;
-    const float* vbias;
-    const float* res;
-    float* y;
-    int S, Cin, Cout, CinP, CoutP;
-    // tail splitting: tiles [0, nfull) are computed whole (by the persistent workgroups); workgroup
-    // npers + j*tail_split + p computes the p-th K range of tile nfull + j and leaves a raw partial output in ws
-    int nfull, tail_split;
-    float* ws;
-    int npers;
-};
+using F44Args = WinoArgs;     // (wino_plan.h: both kernels take the same arguments)
 
 template <int LOGW, int MODE>
 struct FGeo {
@@ -81,7 +67,6 @@ struct FGeo {
     static_assert(TWC * THR >= FTT && TR >= 1 && WPI >= 1 && TR * TWC == FTT, "F(4x4) forward kernel: 32x32 and 64x64 maps");
     static __device__ __forceinline__ int t_row(int tl) { return tl / TWC; }
     static __device__ __forceinline__ int t_col(int tl) { return tl % TWC; }
-    static int groups(int S) { return S * WPI; }
 };
 
 #ifdef VF_STAMPS44F
@@ -673,34 +658,6 @@ __device__ __forceinline__ void f44_pack_group(const float* __restrict__ w, floa
     }
 }
 
-__global__ __launch_bounds__(512) void wino44f_pack_kernel(const float* __restrict__ w, float* __restrict__ uf,
-                                                           float* __restrict__ ub, int Cout, int Cin, size_t nf,
-                                                           size_t nb) {
-    f44_pack_group(w, uf, ub, Cout, Cin, nf, nb, blockIdx.x);
-}
-
-constexpr int F44_PACK_BLOCKS = FNS * FCO * FCK / 256;     // 256-output units per pack group (72)
-
-struct F44PackDesc {
-    const float* w;
-    float* uf;
-    float* ub;
-    long long Cout, Cin, nf, nb, first_block;         // first_block in units of 256 outputs (72 per group)
-};
-__global__ __launch_bounds__(512) void wino44f_pack_multi_kernel(const F44PackDesc* __restrict__ desc, int nlayers) {
-    const long long vb = (long long)blockIdx.x * F44_PACK_BLOCKS;
-    int lo = 0, hi = nlayers;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (desc[mid].first_block <= vb) lo = mid; else hi = mid;
-    }
-    const F44PackDesc d = desc[lo];
-    f44_pack_group(d.w, d.uf, d.ub, (int)d.Cout, (int)d.Cin, (size_t)d.nf, (size_t)d.nb,
-                   (size_t)((vb - d.first_block) / F44_PACK_BLOCKS));
-}
-
-inline int rupf(int v, int m) { return (v + m - 1) / m * m; }
-
 // Sums the K-range partials of the tail tiles in a fixed order and applies the epilogue (bias + per-view bias +
 // residual).  One thread per (tail tile, co, 4x4 tile, tile row).
 template <int LOGW>
@@ -740,23 +697,13 @@ __global__ __launch_bounds__(256) void wino44_fixup_kernel(F44Args a, int ntail)
     *reinterpret_cast<float4*>(a.y + o) = v;
 }
 
-inline int f44_groups(int S, int H, int W) { return S * ((H / 4) * (W / 4) / FTT); }
-
 template <int LOGW, int MODE, bool RAGGED>
 int launch_f44r(F44Args a, size_t ws_floats, hipStream_t st) {
-    using G = FGeo<LOGW, MODE>;
-    const int T = G::groups(a.S) * (a.CoutP / FCO);
-    wino_tail_plan(T, a.CinP / FCK, &a.nfull, &a.tail_split);
-    const int ntail = T - a.nfull;
-    if ((size_t)ntail * a.tail_split * FCO * FTT * 16 > ws_floats || !a.ws) {   // no room: plain grid
-        a.nfull = T;
-        a.tail_split = 1;
-    }
-    const int nt = T - a.nfull;
-    a.npers = a.nfull < F44_PERSIST ? a.nfull : F44_PERSIST;
-    hipLaunchKernelGGL((wino44_conv_kernel<LOGW, MODE, RAGGED>), dim3(a.npers + nt * a.tail_split), dim3(512), 0, st, a);
-    if (nt > 0)
-        hipLaunchKernelGGL((wino44_fixup_kernel<LOGW>), dim3((nt * FCO * FTT * 4 + 255) / 256), dim3(256), 0, st, a, nt);
+    const WinoLaunchPlan p = wino_launch_plan<WinoF44>(a.S, a.Cin, a.Cout, 1 << LOGW, 1 << LOGW, a.ws != nullptr, ws_floats);
+    a.nfull = p.nfull; a.tail_split = p.split; a.npers = p.npers;
+    hipLaunchKernelGGL((wino44_conv_kernel<LOGW, MODE, RAGGED>), dim3(p.conv_grid), dim3(512), 0, st, a);
+    if (p.fixup_grid > 0)
+        hipLaunchKernelGGL((wino44_fixup_kernel<LOGW>), dim3(p.fixup_grid), dim3(256), 0, st, a, p.T - p.nfull);
     VF_RETURN_LAST_ERROR();
 }
 
@@ -770,50 +717,29 @@ int launch_f44(F44Args a, size_t ws_floats, hipStream_t st) {
 extern "C" {
 
 int vf_wino44_pack_sizes(int Cout, int Cin, long* fwd_floats, long* bwd_floats) {
-    *fwd_floats = (long)FNS * rupf(Cin, FCK) * rupf(Cout, FCO);
-    *bwd_floats = (long)FNS * rupf(Cout, FCK) * rupf(Cin, FCO);
-    return 0;
+    return wino_pack_sizes<WinoF44>(Cout, Cin, fwd_floats, bwd_floats);
 }
 
 int vf_wino44_pack_weights(const float* w_oihw, float* u_fwd, float* u_bwd, int Cout, int Cin, void* stream) {
-    const size_t nf = (size_t)FNS * rupf(Cin, FCK) * rupf(Cout, FCO);
-    const size_t nb = u_bwd ? (size_t)FNS * rupf(Cout, FCK) * rupf(Cin, FCO) : 0;
-    hipLaunchKernelGGL(wino44f_pack_kernel, dim3((unsigned)((nf + nb) / (FNS * FCO * FCK))), dim3(512), 0,
-                       (hipStream_t)stream, w_oihw, u_fwd, u_bwd, Cout, Cin, nf, nb);
-    VF_RETURN_LAST_ERROR();
+    return wino_pack_weights<WinoF44, f44_pack_group>(w_oihw, u_fwd, u_bwd, Cout, Cin, stream);
 }
 
 // desc: device int64 [nlayers][8] rows {w, u_fwd, u_bwd, Cout, Cin, fwd_floats, bwd_floats, first_block}
 int vf_wino44_pack_weights_multi(const void* desc, int nlayers, long total_blocks, void* stream) {
-    if (nlayers <= 0 || total_blocks <= 0) return 0;
-    hipLaunchKernelGGL(wino44f_pack_multi_kernel, dim3((unsigned)(total_blocks / F44_PACK_BLOCKS)), dim3(512), 0,
-                       (hipStream_t)stream, (const F44PackDesc*)desc, nlayers);
-    VF_RETURN_LAST_ERROR();
+    return wino_pack_weights_multi<WinoF44, f44_pack_group>(desc, nlayers, total_blocks, stream);
 }
 
 // 1 if vf_wino44_conv_fwd supports this (output) size / mode: 3x3 stride 1, H = W in {32, 64}, modes 0 / 2.
-int vf_wino44_supported(int H, int W, int mode) {
-    return (H == W && (W == 32 || W == 64) && (mode == 0 || mode == 2)) ? 1 : 0;
-}
+int vf_wino44_supported(int H, int W, int mode) { return WinoF44::supported(H, W, mode) ? 1 : 0; }
 
 // workspace floats vf_wino44_conv_fwd wants for its split tail tiles (0 when the grid divides evenly)
 long vf_wino44_conv_ws_floats(int S, int Cin, int Cout, int H, int W) {
-    const int T = f44_groups(S, H, W) * (rupf(Cout, FCO) / FCO);
-    int nfull, split;
-    wino_tail_plan(T, rupf(Cin, FCK) / FCK, &nfull, &split);
-    return (long)(T - nfull) * split * FCO * FTT * 16;
+    return wino_launch_plan<WinoF44>(S, Cin, Cout, H, W, true, WINO_WS_ANY).ws_need;
 }
 
-// Expected CU fill (percent) of vf_wino44_conv_fwd at this shape, and the tile count (as vf_wino_conv_fill_pct).
+// Expected CU fill (percent) of vf_wino44_conv_fwd at this shape, and the tile count (wino_fill_pct, wino_plan.h).
 int vf_wino44_conv_fill_pct(int S, int Cin, int Cout, int H, int W, int* tiles_out) {
-    const int T = f44_groups(S, H, W) * (rupf(Cout, FCO) / FCO);
-    const int nch = rupf(Cin, FCK) / FCK;
-    int nfull, split;
-    wino_tail_plan(T, nch, &nfull, &split, 0.0);
-    if (tiles_out) *tiles_out = T;
-    if (T <= 0) return 0;
-    const double time = (nfull + WINO_SLOTS - 1) / WINO_SLOTS + (T > nfull ? wino_tail_time(T - nfull, split, nch, 0.0) : 0.0);
-    return (int)(100.0 * T / WINO_SLOTS / time);
+    return wino_fill_pct<WinoF44>(S, Cin, Cout, H, W, tiles_out);
 }
 
 // y = conv3x3(x) (+bias +view_bias +residual), pad 1, stride 1, via the fused Winograd F(4x4,3x3).
@@ -825,7 +751,7 @@ int vf_wino44_conv_fwd(const float* x, const float* u_packed, const float* bias,
     if (!vf_wino44_supported(H, W, mode)) return (int)hipErrorInvalidValue;
     F44Args a;
     a.x = x; a.u = u_packed; a.bias = bias; a.vbias = view_bias; a.res = residual; a.y = y;
-    a.S = S; a.Cin = Cin; a.Cout = Cout; a.CinP = rupf(Cin, FCK); a.CoutP = rupf(Cout, FCO);
+    a.S = S; a.Cin = Cin; a.Cout = Cout; a.CinP = rup(Cin, FCK); a.CoutP = rup(Cout, FCO);
     a.ws = ws;
     hipStream_t st = (hipStream_t)stream;
     const size_t nws = ws ? (size_t)ws_floats : 0;

@@ -19,25 +19,24 @@ _WINO_ABI = {1: ("_vf_wpack", "vf_wino_pack_sizes", "vf_wino_pack_weights", "vf_
 #   F(4x4,3x3)          : CH = 5390 per chunk of a 512-pixel tile,            F = 4.7
 # the tiles run in rounds of 256 (one workgroup per CU); K-split tail parts additionally write and re-read their raw
 # partial outputs (64 / 128 KB per part, priced at 4 TB/s = 2000 bytes per cycle) and pay the fix-up launch.
-_WINO_COST = {1: (3340.0, 4.2, 64 * 32 * 8), 2: (5390.0, 4.7, 64 * 32 * 16)}
+_WINO_COST = {1: (3340.0, 4.2), 2: (5390.0, 4.7)}
 
 
 def _wino_cycles(kind, S, Cin, Cout, H, W):
+    """Priced on the plan the launch runs with the workspace packing._wino_ws gives it (vf_wino_conv_plan; mode plays no
+    part in the plan)."""
     lib = _lib.load()
-    ch, F, part_floats = _WINO_COST[kind]
-    tiles = ctypes.c_int(0)
-    getattr(lib, "vf_wino_conv_fill_pct" if kind == 1 else "vf_wino44_conv_fill_pct")(S, Cin, Cout, H, W, ctypes.byref(tiles))
-    T = tiles.value
-    parts = getattr(lib, _WINO_ABI[kind][4])(S, Cin, Cout, H, W) // part_floats     # K-split tail parts (0: plain grid)
-    nch = (Cin + 7) // 8
-    if parts == 0:
+    ch, F = _WINO_COST[kind]
+    ws = getattr(lib, _WINO_ABI[kind][4])(S, Cin, Cout, H, W)
+    plan = (ctypes.c_int * 8)()
+    if lib.vf_wino_conv_plan(kind, S, Cin, Cout, H, W, 0, 1, ws, ctypes.cast(plan, ctypes.c_void_p)):
+        raise _lib.VFHipError(f"vf_wino_conv_plan refused kind {kind} at {(S, Cin, Cout, H, W)}")
+    T, nch, nfull, split, per = plan[:5]
+    if split == 1:
         return -(-T // 256) * (nch + F) * ch
-    ntail = T % 256
-    split = max(1, parts // max(ntail, 1))
-    cyc = (T // 256) * (nch + F) * ch + -(-parts // 256) * (-(-nch // split) + F) * ch
-    return cyc + parts * part_floats * 4 * 2.5 / 2000.0 + 8000.0     # partials written + read (+ output), fix-up launch
-
-
+    parts = (T - nfull) * split                                       # K-split tail parts
+    cyc = (T // 256) * (nch + F) * ch + -(-parts // 256) * (per + F) * ch
+    return cyc + ws * 4 * 2.5 / 2000.0 + 8000.0     # partials written + read (+ output), fix-up launch
 
 
 def wino_kind(S, Cin, Cout, H, W, KS, m, train=None):
