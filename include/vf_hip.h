@@ -124,6 +124,21 @@ int vf_conv_small_gn(const float* x, const float* x2 /*|NULL*/, int C1, const fl
                      unsigned long long* out_stats /*|NULL*/, const float* rx /*|NULL*/, const float* rx2 /*|NULL*/,
                      int rC1, int rC, const float* rw_oihw, const float* rbias /*|NULL*/, const float* w_packed /*|NULL*/,
                      int mode, void* stream);
+/* Host only, launches nothing: the plan the launcher behind the three entries above executes for a vf_conv_small_gn
+ * call of these sizes and operands (has_*: the pointer is not NULL; has_in_affine: in_gamma and in_beta both), as
+ * out = { [0] 0 if taken, else the refusal branch in the order the launcher tests them: 1 unsupported layer, 2 x2 (not
+ *         1x1 / C1 outside (0, Cin)), in_stats with 3 x2, 4 no affine, 5 in_groups <= 0, 6 Cin % in_groups, 7 1x1 Cin > 1024,
+ *         8 3x3 Cin / 8 > 64, 9 mode 2 with rx or in_stats, rx with 10 KS != 3, 11 residual, 12 no rw, 13 rC < 4,
+ *         14 rC % 4, 15 rC1 outside (0, rC);
+ *   [1] kernel: 0 none (refused, or S <= 0), 1 conv1_small_kernel<false>, 2 conv1_small_kernel<true>, 3 conv3_small_kernel;
+ *   [2] LOGTC, [3] RS (16 RS output channels per workgroup; 2 for 1x1), [4] PACKED, [5] workgroups,
+ *   [6] n: products per wave of the 1x1 kernel, [7] rn: the same of the folded residual conv (0 without rx),
+ *   [8] rounds per wave (3x3), [9] channels of the last round (8 or 4), [10] x upsampled on read,
+ *   [11] GroupNorm on load, [12] output statistics, [13] residual conv folded in, [14] log2 W, [15] channels per group }.
+ * Fields that do not apply are 0.  Returns hipErrorInvalidValue only for out == NULL. */
+int vf_conv_small_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, int has_x2, int C1, int has_in_stats,
+                       int has_in_affine, int in_groups, int has_out_stats, int has_rx, int has_rx2, int rC1, int rC,
+                       int has_rw, int has_residual, int has_w_packed, int* out /*[16]*/);
 /* 3x3 weights in the load order of the one-launch kernel (every weight load of a wave = 1 KB of consecutive memory instead
  * of 16 pieces of 16 OIHW rows); static weights (the sampler) are packed once.  Cin % 32 == 0. */
 long vf_conv_small_pack_floats(int Cout, int Cin);

@@ -167,8 +167,10 @@ SMALL_CASES = [c for c in CONV_CASES if c[4] == "same" and c[0] % (4 if c[3] == 
 @pytest.mark.parametrize("S", [1, 3])
 @pytest.mark.parametrize("Cin,Cout,Hin,KS,mode", SMALL_CASES)
 def test_conv_small_sampler_kernel(dev, Cin, Cout, Hin, KS, mode, S):
-    """The sampler's one-launch conv (csrc/conv_small.hip: K split over the waves of a workgroup, unpacked weights)
-    against an fp64 convolution, through the same ops.conv2d call the no-grad UNet forward makes."""
+    """The sampler's one-launch conv (csrc/conv_small.hip: K split over the waves of a workgroup) against an fp64
+    convolution, through the same ops.conv2d call the no-grad UNet forward makes: a 1x1 layer reads the unpacked OIHW
+    parameter through vf_conv_small, a 3x3 layer the packed copy (vf_conv_small_pack, made once per weight version)
+    through vf_conv_small_gn.  The unpacked 3x3 kernels run in tests/test_gpu_conv_small_plan.py."""
     from view_fusion_amd import ops
     layer = torch.nn.Conv2d(Cin, Cout, KS, padding=KS // 2)
     with torch.no_grad():

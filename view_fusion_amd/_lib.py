@@ -103,6 +103,7 @@ SIGNATURES = {
     "vf_conv_small_res": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P],
     "vf_conv_small_gn": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _I, _P, _P, _P, _I, _I,
                          _P, _P, _P, _I, _P],
+    "vf_conv_small_plan": [_I] * 20 + [_P],
     "vf_conv_small_pack_floats": [_I, _I],
     "vf_conv_small_pack": [_P, _P, _I, _I, _P],
     "vf_adam_multi_dev": [_P, _I, _L, _P, _F, _F, _F, _P],

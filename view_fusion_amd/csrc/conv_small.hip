@@ -421,14 +421,16 @@ __global__ __launch_bounds__(512) void conv3_small_kernel(SmallArgs a) {
     small_epilogue<RS>(a, lds, acc, ep);
 }
 
-template <int RS, bool PACKED>
-int launch_conv3(const SmallArgs& a, hipStream_t st) {
-    const int W = 1 << a.logW;
-    const long grid = (long)a.S * ((a.Cout + 16 * RS - 1) / (16 * RS)) * (W * W / SM_PX);
-    if (W >= 16) hipLaunchKernelGGL((conv3_small_kernel<4, RS, PACKED>), dim3((unsigned)grid), dim3(512), 0, st, a);
-    else if (W == 8) hipLaunchKernelGGL((conv3_small_kernel<3, RS, PACKED>), dim3((unsigned)grid), dim3(512), 0, st, a);
-    else hipLaunchKernelGGL((conv3_small_kernel<2, RS, PACKED>), dim3((unsigned)grid), dim3(512), 0, st, a);
+template <int LOGTC, int RS, bool PACKED>
+int launch_conv3(const SmallArgs& a, unsigned grid, hipStream_t st) {
+    hipLaunchKernelGGL((conv3_small_kernel<LOGTC, RS, PACKED>), dim3(grid), dim3(512), 0, st, a);
     VF_RETURN_LAST_ERROR();
+}
+template <int RS, bool PACKED>
+int launch_conv3(int logtc, const SmallArgs& a, unsigned grid, hipStream_t st) {
+    if (logtc == 4) return launch_conv3<4, RS, PACKED>(a, grid, st);
+    if (logtc == 3) return launch_conv3<3, RS, PACKED>(a, grid, st);
+    return launch_conv3<2, RS, PACKED>(a, grid, st);
 }
 
 // [16-row block 2 ceil(Cout/32)][wave 8][round nr][group 5][lane 64] float4: lane (j, kk) of group q, round r, wave wv holds
@@ -480,41 +482,119 @@ struct SmallGn {                       // GroupNorm on the input (applied on loa
     const float* wp = nullptr;         // packed 3x3 weights (vf_conv_small_pack), or null
 };
 
+// Every host decision of a launch, in one place: conv_small_launch executes it, vf_conv_small_plan reports it.
+// The operands enter as presence flags; rC1 / rC as the entries normalise them (rC1 = rC without rx2, both 0 without rx).
+enum { SM_K_NONE = 0, SM_K_1X1 = 1, SM_K_1X1_CAT = 2, SM_K_3X3 = 3 };
+struct SmallPlan {
+    int code;          // 0 = taken, else the refusal branch (1 ... 15, in the order they are tested)
+    int kernel;        // SM_K_*; SM_K_NONE for a refusal and for S <= 0 (nothing is launched)
+    int logtc, rs, packed;             // 3x3: the conv3_small_kernel<LOGTC, RS, PACKED> instantiation
+    long grid;
+    int n, rn;         // products per wave of the 1x1 kernel / of the folded residual conv (multiples of 16)
+    int nr, last;      // 3x3: rounds per wave, channels of the last round (8 or 4)
+    int up, gn, ostats, fold, logW, icpg;
+};
+
+static SmallPlan conv_small_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, bool x2, int C1, bool ist,
+                                 bool affine, int groups, bool ost, bool rx, bool rx2, int rC1, int rC, bool rw,
+                                 bool residual, bool wp) {
+    SmallPlan p = {};
+    auto refuse = [&](int code) { p.code = code; return p; };
+    if (!vf_conv_small_supported(Cin, Cout, H, W, KS, mode)) return refuse(1);
+    if (x2 && (KS != 1 || C1 <= 0 || C1 >= Cin)) return refuse(2);
+    if (ist) {
+        if (x2) return refuse(3);
+        if (!affine) return refuse(4);
+        if (groups <= 0) return refuse(5);
+        if (Cin % groups != 0) return refuse(6);
+        if (KS == 1 && Cin > SM_GN_MAXC) return refuse(7);
+        if (KS == 3 && Cin / 8 > 64) return refuse(8);
+    }
+    if (mode == 2 && (rx || ist)) return refuse(9);
+    if (rx) {
+        if (KS != 3) return refuse(10);
+        if (residual) return refuse(11);
+        if (!rw) return refuse(12);
+        if (rC < 4) return refuse(13);
+        if (rC % 4 != 0) return refuse(14);
+        if (rx2 ? (rC1 <= 0 || rC1 >= rC) : rC1 != rC) return refuse(15);
+    }
+    if (S <= 0) return p;
+    p.logW = ilog2(W);
+    p.n = (((Cin + 7) / 8) + 15) & ~15;
+    p.rn = rx ? ((((rC + 7) / 8) + 15) & ~15) : 0;
+    p.gn = ist ? 1 : 0;
+    p.icpg = ist ? Cin / groups : 1;
+    p.ostats = ost ? 1 : 0;
+    p.fold = rx ? 1 : 0;
+    p.up = mode == 2 ? 1 : 0;
+    // 32-channel tiles when they alone fill the chip, 16-channel tiles (twice the workgroups) otherwise
+    const long wgs32 = (long)S * ((Cout + 31) / 32) * (H * W / SM_PX);
+    if (KS == 1) {
+        p.kernel = x2 ? SM_K_1X1_CAT : SM_K_1X1;
+        p.rs = 2;
+        p.grid = wgs32;
+        return p;
+    }
+    p.kernel = SM_K_3X3;
+    p.logtc = W >= 16 ? 4 : (W == 8 ? 3 : 2);
+    p.rs = wgs32 >= 256 ? 2 : 1;
+    p.packed = wp ? 1 : 0;
+    p.grid = (long)S * ((Cout + 16 * p.rs - 1) / (16 * p.rs)) * (H * W / SM_PX);
+    const int cw = Cin >> 3;
+    p.nr = (cw + 7) / 8;
+    p.last = cw - (p.nr - 1) * 8;
+    return p;
+}
+
 static int conv_small_launch(const float* x, const float* x2, int C1, const float* w, const float* bias,
                              const float* view_bias, const float* residual, float* y, int S, int Cin, int Cout, int H,
                              int W, int KS, int mode, const float* rx, const float* rx2, int rC1, int rC,
                              const float* rw, const float* rbias, void* stream, const SmallGn& gn = SmallGn()) {
-    if (!vf_conv_small_supported(Cin, Cout, H, W, KS, mode) || (x2 && (KS != 1 || C1 <= 0 || C1 >= Cin)))
-        return (int)hipErrorInvalidValue;
-    if (gn.ist && (x2 || !gn.ig || !gn.ib || gn.groups <= 0 || Cin % gn.groups != 0 || (KS == 1 && Cin > SM_GN_MAXC)
-                   || (KS == 3 && Cin / 8 > 64)))
-        return (int)hipErrorInvalidValue;
-    if (mode == 2 && (rx || gn.ist)) return (int)hipErrorInvalidValue;
-    if (rx && (KS != 3 || residual || !rw || rC < 4 || rC % 4 != 0 || (rx2 ? (rC1 <= 0 || rC1 >= rC) : rC1 != rC)))
-        return (int)hipErrorInvalidValue;
-    if (S <= 0) return 0;
+    const SmallPlan p = conv_small_plan(S, Cin, Cout, H, W, KS, mode, x2 != nullptr, C1, gn.ist != nullptr,
+                                        gn.ig && gn.ib, gn.groups, gn.ost != nullptr, rx != nullptr, rx2 != nullptr, rC1,
+                                        rC, rw != nullptr, residual != nullptr, KS == 3 && gn.wp);
+    if (p.code) return (int)hipErrorInvalidValue;
+    if (p.kernel == SM_K_NONE) return 0;
     SmallArgs a;
     a.x = x; a.x2 = x2; a.w = w; a.bias = bias; a.vbias = view_bias; a.res = residual; a.y = y;
-    a.S = S; a.Cin = Cin; a.C1 = x2 ? C1 : Cin; a.Cout = Cout; a.logW = ilog2(W);
-    a.n = (((Cin + 7) / 8) + 15) & ~15;
+    a.S = S; a.Cin = Cin; a.C1 = x2 ? C1 : Cin; a.Cout = Cout; a.logW = p.logW;
+    a.n = p.n;
     a.rx = rx; a.rx2 = rx2; a.rw = rw; a.rbias = rbias; a.rC = rC; a.rC1 = rC1;
-    a.rn = rx ? ((((rC + 7) / 8) + 15) & ~15) : 0;
+    a.rn = p.rn;
     a.ost = gn.ost; a.ist = gn.ist; a.ig = gn.ig; a.ib = gn.ib;
-    a.icpg = gn.ist ? Cin / gn.groups : 1; a.isilu = gn.silu; a.ieps = gn.eps;
-    a.iinv = gn.ist ? 1.0 / (16777216.0 * (double)a.icpg * (double)H * (double)W) : 0.0;
-    a.up = mode == 2 ? 1 : 0;
-    a.wp = KS == 3 ? gn.wp : nullptr;
+    a.icpg = p.icpg; a.isilu = gn.silu; a.ieps = gn.eps;
+    a.iinv = p.gn ? 1.0 / (16777216.0 * (double)a.icpg * (double)H * (double)W) : 0.0;
+    a.up = p.up;
+    a.wp = p.packed ? gn.wp : nullptr;
     hipStream_t st = (hipStream_t)stream;
-    if (KS == 1) {
-        const long grid = (long)S * ((Cout + 31) / 32) * (H * W / SM_PX);
-        if (x2) hipLaunchKernelGGL((conv1_small_kernel<true>), dim3((unsigned)grid), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((conv1_small_kernel<false>), dim3((unsigned)grid), dim3(512), 0, st, a);
+    const unsigned grid = (unsigned)p.grid;
+    if (p.kernel == SM_K_1X1_CAT) {
+        hipLaunchKernelGGL((conv1_small_kernel<true>), dim3(grid), dim3(512), 0, st, a);
         VF_RETURN_LAST_ERROR();
     }
-    // 32-channel tiles when they alone fill the chip, 16-channel tiles (twice the workgroups) otherwise
-    const long wgs32 = (long)S * ((Cout + 31) / 32) * (H * W / SM_PX);
-    if (a.wp) return wgs32 >= 256 ? launch_conv3<2, true>(a, st) : launch_conv3<1, true>(a, st);
-    return wgs32 >= 256 ? launch_conv3<2, false>(a, st) : launch_conv3<1, false>(a, st);
+    if (p.kernel == SM_K_1X1) {
+        hipLaunchKernelGGL((conv1_small_kernel<false>), dim3(grid), dim3(512), 0, st, a);
+        VF_RETURN_LAST_ERROR();
+    }
+    if (p.packed) return p.rs == 2 ? launch_conv3<2, true>(p.logtc, a, grid, st) : launch_conv3<1, true>(p.logtc, a, grid, st);
+    return p.rs == 2 ? launch_conv3<2, false>(p.logtc, a, grid, st) : launch_conv3<1, false>(p.logtc, a, grid, st);
+}
+
+// The plan of a vf_conv_small_gn call with these sizes and operands (has_*: the pointer is not NULL; has_in_affine: both
+// in_gamma and in_beta), host only -- see include/vf_hip.h for the row.
+int vf_conv_small_plan(int S, int Cin, int Cout, int H, int W, int KS, int mode, int has_x2, int C1, int has_in_stats,
+                       int has_in_affine, int in_groups, int has_out_stats, int has_rx, int has_rx2, int rC1, int rC,
+                       int has_rw, int has_residual, int has_w_packed, int* out) {
+    if (!out) return (int)hipErrorInvalidValue;
+    const SmallPlan p = conv_small_plan(S, Cin, Cout, H, W, KS, mode, has_x2 != 0, C1, has_in_stats != 0, has_in_affine != 0,
+                                        in_groups, has_out_stats != 0, has_rx != 0, has_rx2 != 0,
+                                        has_rx ? (has_rx2 ? rC1 : rC) : 0, has_rx ? rC : 0, has_rw != 0, has_residual != 0,
+                                        KS == 3 && has_w_packed);
+    const int row[16] = {p.code, p.kernel, p.logtc, p.rs, p.packed, (int)p.grid, p.n, p.rn, p.nr, p.last, p.up, p.gn,
+                         p.ostats, p.fold, p.logW, p.icpg};
+    for (int i = 0; i < 16; ++i) out[i] = row[i];
+    return 0;
 }
 
 int vf_conv_small(const float* x, const float* x2, int C1, const float* w, const float* bias, const float* view_bias,
