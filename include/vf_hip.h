@@ -296,6 +296,13 @@ int vf_attn_stream_fwd(const float* qkv, float* out, float* rowstat /*|NULL*/, i
  * delta [S][L] workspace (rowsum(dO o out)); writes all of dqkv [S][3C][L].  Three launches: delta, dK + dV, dQ. */
 int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* rowstat, float* delta,
                        float* dqkv, int S, int C, int L, void* stream);
+/* ... their launch plan, host only (nothing is launched; the two launchers execute the function that answers; qkv and dO
+ * count by their alignment alone): out[10] = {state (0 empty: S <= 0 or L <= 0, the launchers return 0; 1 runs; 2 refused:
+ * C <= 0 or C > 512, hipErrorInvalidValue), NT of the <NT> kernels (1..4), 16-byte loads in the forward (L % 4 == 0 and
+ * qkv aligned), in the backward (and dO aligned), grid x = ceil(L / 32) and y = S of the forward, dK / dV and dQ kernels,
+ * grid x of the delta kernel, 128-wide blocks per workgroup, floats of rowstat (2 S L) and of delta (S L), saturating at
+ * INT_MAX}; every field but state is 0 where nothing runs.  Returns hipErrorInvalidValue only for out == NULL. */
+int vf_attn_stream_plan(const void* qkv, const void* dO, int S, int C, int L, int* out /*[10]*/);
 int vf_softmax_fwd(const float* x, float* y, int rows, int cols, void* stream);
 int vf_softmax_bwd(const float* y, const float* dy, float* dx, int rows, int cols, void* stream);
 /* The launch plans of this family, host only (nothing is launched); the launchers execute the functions that answer.

@@ -305,7 +305,7 @@ GN_SHAPES = [(64, 64, 64), (32, 16, 16), (192, 8, 8), (96, 8, 8), (64, 6, 10), (
 GN_SILU = {(64, 64, 64): True, (32, 16, 16): False, (192, 8, 8): True, (96, 8, 8): False, (64, 6, 10): True, (32, 5, 5): False}
 GN_CASES = [(r, s, None) for r in GN_RATIOS for s in GN_SIGMAS] + [(10, 1.0, "const"), (10, 1.0, "outlier")]
 ATTN_SHAPES = [(64, 16, 16, 1), (32, 16, 16, 17), (192, 16, 16, 97), (64, 8, 8, 3), (96, 8, 8, 3), (32, 32, 32, 2)]      # (C, H, W, S)
-STREAM_SHAPES = [(64, 10, 20, 2), (96, 10, 20, 2), (64, 16, 24, 2), (96, 16, 24, 2)]
+STREAM_SHAPES = [(64, 10, 20, 2), (96, 10, 20, 2), (64, 16, 24, 2), (96, 16, 24, 2), (192, 10, 20, 2), (64, 7, 29, 2)]
 ATTN_CASES = [(sc, sh, False) for sc in ATTN_SCALES for sh in ATTN_SHIFTS] + [(14, 8, True)]
 COMPOSE_CASES = [(N, ls) for N in (1, 2, 23) for ls in COMPOSE_SCALES]
 CONV_GN_SHAPES = [(6, 128, 64, 64, "vf_wino_conv_fwd_gn"), (1, 384, 192, 16, "vf_conv_fwd_gn")]      # (S, Cin, Cout, H, entry)

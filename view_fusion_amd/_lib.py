@@ -87,6 +87,7 @@ SIGNATURES = {
     "vf_attention_dvdk": [_P, _P, _P, _P, _P, _I, _I, _I, _P],
     "vf_attn_stream_fwd": [_P, _P, _P, _I, _I, _I, _P],
     "vf_attn_stream_bwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P],
+    "vf_attn_stream_plan": [_P, _P, _I, _I, _I, _P],
     "vf_softmax_fwd": [_P, _P, _I, _I, _P],
     "vf_softmax_bwd": [_P, _P, _P, _I, _I, _P],
     "vf_bgemm_plan": [_P, _P, _I, _I, _I, _I, _L, _L, _L, _L, _L, _L, _L, _P],

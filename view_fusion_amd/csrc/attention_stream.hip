@@ -374,19 +374,68 @@ int tiles_per_wave(int C) { return ((C + 31) / 32 + 3) / 4; }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
+// The plan of one vf_attn_stream_fwd / vf_attn_stream_bwd pair: every decision the two launchers take on the host, made in
+// ONE place (attn_stream_plan below) that both execute and vf_attn_stream_plan reports.
+enum { AS_EMPTY = 0, AS_RUNS = 1, AS_REFUSED = 2 };
+
+struct AttnStreamPlan {
+    int state;            // AS_EMPTY: S <= 0 or L <= 0, nothing runs; AS_REFUSED: C <= 0 or C > 512
+    int nt;               // channel tiles per wave: the <NT> of the forward, dK / dV and dQ kernels
+    int vec_fwd, vec_bwd; // ld4 takes 16-byte loads (forward: of V; backward: of dO, Q and K)
+    int gx, gy;           // grid of the forward, dK / dV and dQ kernels: (32-wide blocks of L, views)
+    int delta_gx;         // grid x of attn_stream_delta_kernel (256 queries per workgroup; y = views)
+    int nblocks;          // 128-wide blocks each workgroup streams
+    long rowstat_floats, delta_floats;
+};
+
+AttnStreamPlan attn_stream_plan(const void* qkv, const void* dO, int S, int C, int L) {
+    AttnStreamPlan p = {AS_EMPTY, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (S <= 0 || L <= 0) return p;
+    if (C <= 0 || C > 512) {
+        p.state = AS_REFUSED;
+        return p;
+    }
+    p.state = AS_RUNS;
+    p.nt = tiles_per_wave(C);
+    p.vec_fwd = L % 4 == 0 && aligned16(qkv);
+    p.vec_bwd = p.vec_fwd && aligned16(dO);
+    p.gx = (L + SQ - 1) / SQ; p.gy = S;
+    p.delta_gx = (L + 255) / 256;
+    p.nblocks = (L + SKB - 1) / SKB;
+    p.rowstat_floats = 2L * S * L;
+    p.delta_floats = (long)S * L;
+    return p;
+}
+
 }  // namespace
 
 extern "C" {
 
+// Host only, launches nothing: the plan vf_attn_stream_fwd and vf_attn_stream_bwd execute for these arguments (qkv and
+// dO count by their alignment alone) -> out[10] = {state (0 empty: S <= 0 or L <= 0, both return 0 and launch nothing;
+// 1 runs; 2 refused: C <= 0 or C > 512), NT, vec of the forward, vec of the backward, grid x and y of the forward,
+// dK / dV and dQ kernels, grid x of the delta kernel, 128-wide blocks per workgroup, floats of rowstat (2 S L), floats
+// of delta (S L); the two float counts saturate at INT_MAX}.  Every field but state is 0 where nothing runs.
+int vf_attn_stream_plan(const void* qkv, const void* dO, int S, int C, int L, int* out) {
+    if (!out) return (int)hipErrorInvalidValue;
+    const AttnStreamPlan p = attn_stream_plan(qkv, dO, S, C, L);
+    auto sat = [](long v) { return v > 2147483647L ? 2147483647 : (int)v; };
+    const int v[10] = {p.state, p.nt, p.vec_fwd, p.vec_bwd, p.gx, p.gy, p.delta_gx, p.nblocks, sat(p.rowstat_floats),
+                       sat(p.delta_floats)};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 0;
+}
+
 // qkv [S][3C][L] -> out [S][C][L]; rowstat [S][2][L] (training) or NULL.  Any L >= 1, 1 <= C <= 512.
 int vf_attn_stream_fwd(const float* qkv, float* out, float* rowstat, int S, int C, int L, void* stream) {
-    if (S <= 0 || L <= 0) return 0;
-    if (C <= 0 || C > 512) return (int)hipErrorInvalidValue;
+    const AttnStreamPlan p = attn_stream_plan(qkv, qkv, S, C, L);        // (the forward reads no dO)
+    if (p.state == AS_EMPTY) return 0;
+    if (p.state == AS_REFUSED) return (int)hipErrorInvalidValue;
     const float alpha = 1.0f / sqrtf((float)C);
-    const int vec = L % 4 == 0 && aligned16(qkv);
+    const int vec = p.vec_fwd;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((L + SQ - 1) / SQ, S);
-    switch (tiles_per_wave(C)) {
+    const dim3 grid(p.gx, p.gy);
+    switch (p.nt) {
         case 1: hipLaunchKernelGGL(attn_stream_fwd_kernel<1>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
         case 2: hipLaunchKernelGGL(attn_stream_fwd_kernel<2>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
         case 3: hipLaunchKernelGGL(attn_stream_fwd_kernel<3>, grid, dim3(256), 0, st, qkv, out, rowstat, C, L, alpha, vec); break;
@@ -400,17 +449,18 @@ int vf_attn_stream_fwd(const float* qkv, float* out, float* rowstat, int S, int 
 // delta, dK + dV, dQ.  Every element of dqkv is written.
 int vf_attn_stream_bwd(const float* qkv, const float* out, const float* dO, const float* rowstat, float* delta,
                        float* dqkv, int S, int C, int L, void* stream) {
-    if (S <= 0 || L <= 0) return 0;
-    if (C <= 0 || C > 512) return (int)hipErrorInvalidValue;
+    const AttnStreamPlan p = attn_stream_plan(qkv, dO, S, C, L);
+    if (p.state == AS_EMPTY) return 0;
+    if (p.state == AS_REFUSED) return (int)hipErrorInvalidValue;
     const float alpha = 1.0f / sqrtf((float)C);
-    const int vec = L % 4 == 0 && aligned16(qkv) && aligned16(dO);
+    const int vec = p.vec_bwd;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(attn_stream_delta_kernel, dim3((L + 255) / 256, S), dim3(256), 0, st, out, dO, delta, C, L);
-    const dim3 grid((L + SQ - 1) / SQ, S);
+    hipLaunchKernelGGL(attn_stream_delta_kernel, dim3(p.delta_gx, p.gy), dim3(256), 0, st, out, dO, delta, C, L);
+    const dim3 grid(p.gx, p.gy);
 #define VF_AS_BWD(NT_)                                                                                                \
     hipLaunchKernelGGL(attn_stream_dkv_kernel<NT_>, grid, dim3(256), 0, st, qkv, dO, rowstat, delta, dqkv, C, L, alpha, vec); \
     hipLaunchKernelGGL(attn_stream_dq_kernel<NT_>, grid, dim3(256), 0, st, qkv, dO, rowstat, delta, dqkv, C, L, alpha, vec);
-    switch (tiles_per_wave(C)) {
+    switch (p.nt) {
         case 1: VF_AS_BWD(1) break;
         case 2: VF_AS_BWD(2) break;
         case 3: VF_AS_BWD(3) break;
