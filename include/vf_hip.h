@@ -333,6 +333,16 @@ int vf_concat_channels(float* a, float* b, float* out, int S, long na, long nb, 
 /* nn.Dropout(p) inside Block, unet.py:207-216 (training mode): y = x * (u >= p) / (1-p), u = caller's uniform draws;
  * applied to dy it is the backward */
 int vf_dropout(const float* x, const float* u, float* y, long n, float p, void* stream);
+/* The same with the mask drawn in the kernel (csrc/rng.h, kind 5): element e of row v (view v - off[b] of sample b) is
+ * kept iff (word e % 4 of block e / 4) >> 8 >= thr, thr = ceil(float32(p) * 2^24); y = keep ? x * scale : 0 with
+ * scale = 1.0f / (1.0f - p): bit-identical to vf_dropout fed u = (word >> 8) * 2^-24.  Applied to dy it is the backward.
+ * x, y [S][n]; ids DEVICE int64 [B]; off DEVICE int32 [B + 1] (every sample at most 4095 views: the caller's check).
+ * hipErrorInvalidValue for n % 4, thr > 2^24, layer outside [0, 2^16), n / 4 >= 2^32. */
+int vf_dropout_seeded(const float* x, float* y, unsigned long long seed, const long long* ids, const int* off, int B,
+                      int S, long n, unsigned thr, float scale, int layer, void* stream);
+/* Host mirror (HOST pointers, no stream, no GPU needed): keep [S][n], 1 = kept */
+int vf_dropout_mask_host(unsigned long long seed, const long long* ids, const int* off, int B, int S, long n,
+                         unsigned thr, int layer, unsigned char* keep /*[S][n]*/);
 
 /* ---- ViewFusion : view_fusion.py:162-164 (q_sample), :244-263/:95-115 (stack), :265-298/:116-150
  *      (compose, mean ablation, MSE), :70-84,152-177 (posterior + p_sample), :314-317 (extract) ---- */

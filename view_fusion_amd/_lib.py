@@ -98,6 +98,8 @@ SIGNATURES = {
     "vf_swish_bwd": [_P, _P, _P, _L, _P],
     "vf_concat_channels": [_P, _P, _P, _I, _L, _L, _I, _P],
     "vf_dropout": [_P, _P, _P, _L, _F, _P],
+    "vf_dropout_seeded": [_P, _P, _U64, _P, _P, _I, _I, _L, ctypes.c_uint, _F, _I, _P],
+    "vf_dropout_mask_host": [_U64, _P, _P, _I, _I, _L, ctypes.c_uint, _I, _P],
     "vf_adam_multi": [_P, _I, _L, _F, _F, _F, _F, _F, _F, _P],
     "vf_conv_small_supported": [_I, _I, _I, _I, _I, _I],
     "vf_conv_small": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -2,6 +2,7 @@
 // channel concat / split.  Reference: model/unet.py:142-157 (encoding), :180-182 (Swish),
 // :134 (skip concat).
 #include "common.h"
+#include "rng.h"
 
 namespace {
 
@@ -45,6 +46,33 @@ __global__ void dropout_kernel(const float4* __restrict__ x, const float4* __res
     const float4 a = x[i], r = u[i];
     y[i] = make_float4(r.x >= p ? a.x * scale : 0.f, r.y >= p ? a.y * scale : 0.f, r.z >= p ? a.z * scale : 0.f,
                        r.w >= p ? a.w * scale : 0.f);
+}
+
+// The same Dropout with the mask drawn here (csrc/rng.h, kind 5, "Dropout masks"): no u tensor, forward or saved; the
+// same launch on dy is the backward.  x, y: [S][n4] float4; row v is view v - off[b] of sample b (off: int32 [B + 1]).
+// grid (chunks of 256 float4, min(S, 65535)); one Philox call per float4.  Every index is bounded by n4 and S, which
+// the launcher takes from the caller's tensor; off only selects the sample whose id is read (b in [0, B) by
+// construction of the search).
+__global__ void dropout_seeded_kernel(const float4* __restrict__ x, float4* __restrict__ y, unsigned long long seed,
+                                      const long long* __restrict__ ids, const int* __restrict__ off, int B, int S,
+                                      size_t n4, unsigned thr, float scale, unsigned layer) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    for (int v = blockIdx.y; v < S; v += gridDim.y) {
+        int lo = 0, hi = B;                       // find b with off[b] <= v < off[b+1]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (off[mid] <= v) lo = mid; else hi = mid;
+        }
+        uint32_t w[4];
+        vf_rng_words(seed, (unsigned long long)ids[lo], VF_RNG_DROPOUT, vf_rng_dropout_step(layer, (uint32_t)(v - off[lo])),
+                     (uint32_t)i, w);
+        const float4 a = x[(size_t)v * n4 + i];
+        y[(size_t)v * n4 + i] = make_float4(vf_rng_dropout_keep(w[0], thr) ? a.x * scale : 0.f,
+                                            vf_rng_dropout_keep(w[1], thr) ? a.y * scale : 0.f,
+                                            vf_rng_dropout_keep(w[2], thr) ? a.z * scale : 0.f,
+                                            vf_rng_dropout_keep(w[3], thr) ? a.w * scale : 0.f);
+    }
 }
 
 // out[s] = [a[s] | b[s]] along channels; na4 / nb4 = float4 per sample of a / b.
@@ -95,6 +123,44 @@ int vf_dropout(const float* x, const float* u, float* y, long n, float p, void* 
     hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const float4*)x, (const float4*)u, (float4*)y, n4, p, 1.0f / (1.0f - p));
     VF_RETURN_LAST_ERROR();
+}
+
+static bool dropout_seeded_args_ok(int B, int S, long n, unsigned thr, int layer) {
+    return B > 0 && S > 0 && n > 0 && !(n & 3) && thr <= (1u << 24) && layer >= 0 && layer < (1 << 16) &&
+           (unsigned long long)(n >> 2) < (1ull << 32);
+}
+
+// x, y: [S][n]; ids: DEVICE int64 [B]; off: DEVICE int32 [B + 1] with off[B] == S (ops.view_offsets), every sample with
+// at most 4095 views (the caller's check: the counts live on the device).  thr = ceil(float32(p) * 2^24),
+// scale = 1.0f / (1.0f - p).
+int vf_dropout_seeded(const float* x, float* y, unsigned long long seed, const long long* ids, const int* off, int B,
+                      int S, long n, unsigned thr, float scale, int layer, void* stream) {
+    if (S <= 0 || n <= 0) return 0;
+    if (!dropout_seeded_args_ok(B, S, n, thr, layer) || !x || !y || !ids || !off) return (int)hipErrorInvalidValue;
+    const size_t n4 = (size_t)n >> 2;
+    hipLaunchKernelGGL(dropout_seeded_kernel, dim3((unsigned)((n4 + 255) / 256), (unsigned)(S < 65535 ? S : 65535)),
+                       dim3(256), 0, (hipStream_t)stream, (const float4*)x, (float4*)y, seed, ids, off, B, S, n4, thr,
+                       scale, (unsigned)layer);
+    VF_RETURN_LAST_ERROR();
+}
+
+// The masks of vf_dropout_seeded on the CPU (HOST pointers, no stream, no GPU): keep [S][n], 1 = kept.  Refuses what
+// the launcher refuses, and an off that is not a prefix sum of counts in [1, 4095] ending at S.
+int vf_dropout_mask_host(unsigned long long seed, const long long* ids, const int* off, int B, int S, long n,
+                         unsigned thr, int layer, unsigned char* keep) {
+    if (!dropout_seeded_args_ok(B, S, n, thr, layer) || !ids || !off || !keep) return (int)hipErrorInvalidValue;
+    if (off[0] != 0 || off[B] != S) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b)
+        if (off[b + 1] <= off[b] || off[b + 1] - off[b] > 4095) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b)
+        for (int v = off[b]; v < off[b + 1]; ++v)
+            for (size_t i = 0; i < (size_t)n >> 2; ++i) {
+                uint32_t w[4];
+                vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_DROPOUT,
+                             vf_rng_dropout_step((uint32_t)layer, (uint32_t)(v - off[b])), (uint32_t)i, w);
+                for (int j = 0; j < 4; ++j) keep[(size_t)v * n + 4 * i + j] = (unsigned char)vf_rng_dropout_keep(w[j], thr);
+            }
+    return 0;
 }
 
 // a: [S][Ca*HW], b: [S][Cb*HW], out: [S][(Ca+Cb)*HW]; per-sample sizes in floats, multiples of 4.

@@ -1,7 +1,7 @@
 // Seeded counter-based random draws for training and sampling: Philox4x32-10 (Salmon et al., "Parallel random
 // numbers: as easy as 1, 2, 3", SC'11; the Random123 constants).  This comment is the ONE written specification of
-// the layout; tests/rng_ref.py restates it in numpy, and the host mirrors at the end of diffusion.hip run these very
-// functions on the CPU.
+// the layout; tests/rng_ref.py restates it in numpy (tests/dropout_ref.py the Dropout masks), and the host mirrors at
+// the end of diffusion.hip (elementwise.hip for the Dropout masks) run these very functions on the CPU.
 //
 // A draw is a pure function of (seed, sample id, kind, step, block): no state, no communication, so the noise a
 // sample receives does not depend on its row in the batch, on the rest of the batch or on the rank that holds it.
@@ -16,6 +16,7 @@
 //   kind 2  sampler start noise y_T, step 0
 //   kind 3  reverse-step noise z, step = the timestep index t[b]
 //   kind 4  batch assembly (the view store, batch_plan.h / batch.hip), step 0: see "Data draws" below
+//   kind 5  residual-block Dropout masks (elementwise.hip), step = (layer << 12) | view: see "Dropout masks" below
 //
 // One Philox call gives four 32-bit words w0..w3.
 //   t = 1 + mulhi32(w0, T - 1)          in [1, T - 1] = the reference's randint(1, T); exact integer arithmetic
@@ -61,6 +62,24 @@
 //   relative_cond[k] = cat(views[src[1]], views[src[k + 1]]) on the channel axis (6 channels)
 //   pixel          = float32(byte) / float32(255), correctly rounded
 //
+// Dropout masks (kind 5): the mask of nn.Dropout(p) in block2 of a residual block (training mode, `seed=` given), drawn
+// inside the kernel that applies it and drawn again, not stored, by the backward.  One row of the block's (S, C, H, W)
+// activation is one view of one sample:
+//   counter = (block, id lo, id hi, (5 << 28) | step),  step = (layer << 12) | view
+//   layer   = the residual block's index in execution order (downs, mid, ups: the order of UNet.forward's dropout_u),
+//             < 2^16
+//   view    = the row's index inside its sample, row - off[b], < 2^12 (so layer and view share no bit of `step`)
+//   block   = the float4 index inside the row's (C, H, W) activation; C * H * W % 4 == 0 (UNet.check_input_size)
+//   element e of the row uses word e % 4 of block e / 4: with k = w >> 8 the element is kept iff k >= thr, where
+//   thr = ceil(float32(p) * 2^24) comes from the host (the product is exact in double precision).  u = k * 2^-24 is
+//   exact in fp32 and so is thr * 2^-24 (thr <= 2^24), hence  k >= thr  <=>  u >= thr * 2^-24  <=>  u >= float32(p)
+//   (no multiple of 2^-24 lies in [float32(p), thr * 2^-24)): the integer compare IS dropout_kernel's `u >= p` fed
+//   u = k * 2^-24, for every p.  The kept value is x * scale with scale = 1.0f / (1.0f - p) in fp32, the expression
+//   vf_dropout evaluates, so the seeded launch and vf_dropout on those u agree bit for bit.
+//   P(keep) = 1 - thr / 2^24 against the ideal 1 - p: 0 <= thr / 2^24 - float32(p) < 2^-24, so the mean of the output,
+//   E[y] = x * P(keep) * scale, differs from the ideal E[y] = x by at most 2^-24 / (1 - p) relative (and the fp32
+//   rounding of scale).
+//
 // Plain C++: no inline assembly, every value leaves a kernel through an ordinary vector store.
 #pragma once
 #include <math.h>
@@ -72,7 +91,8 @@
 #define VF_RNG_HD inline
 #endif
 
-enum { VF_RNG_TRAIN_SCALARS = 0, VF_RNG_TRAIN_NOISE = 1, VF_RNG_START_NOISE = 2, VF_RNG_STEP_NOISE = 3, VF_RNG_DATA = 4 };
+enum { VF_RNG_TRAIN_SCALARS = 0, VF_RNG_TRAIN_NOISE = 1, VF_RNG_START_NOISE = 2, VF_RNG_STEP_NOISE = 3, VF_RNG_DATA = 4,
+       VF_RNG_DROPOUT = 5 };
 
 VF_RNG_HD void vf_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
     uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
@@ -107,6 +127,13 @@ VF_RNG_HD long long vf_rng_distill_step(uint32_t w0, int K) { return (long long)
 VF_RNG_HD float vf_rng_uniform24(uint32_t w1) { return (float)(w1 >> 8) * 5.9604644775390625e-8f; }   // 2^-24
 
 VF_RNG_HD int vf_rng_cond_drop(uint32_t w2, uint32_t thr) { return (w2 >> 8) < thr; }   // thr = ceil(p * 2^24) <= 2^24
+
+// Dropout masks (kind 5): kept iff (w >> 8) >= thr, thr = ceil(float32(p) * 2^24) <= 2^24 -- the same predicate as
+// vf_rng_uniform24(w) >= float32(p)
+VF_RNG_HD int vf_rng_dropout_keep(uint32_t w, uint32_t thr) { return (w >> 8) >= thr; }
+
+// the `step` field of a Dropout call: layer < 2^16, view < 2^12
+VF_RNG_HD uint32_t vf_rng_dropout_step(uint32_t layer, uint32_t view) { return (layer << 12) | view; }
 
 VF_RNG_HD float vf_rng_open_uniform(uint32_t w) {                                                      // (0, 1]
     return (float)w * 2.3283064365386963e-10f + 1.1641532182693481e-10f;                               // 2^-32, 2^-33

@@ -40,8 +40,8 @@ from .conv import (  # noqa: F401
     _Conv1x1CatFn, _Conv2dFn, _conv_small, _conv_small_res, conv1x1_cat, conv2d, conv2d_gn
 )
 from .dense import (  # noqa: F401
-    _DropoutFn, _LinearFn, _SwishFn, _TimeAffineFn, _bgemm, _ta_desc, dropout, linear, sincos_embedding, swish,
-    time_affine_all
+    _DropoutFn, _DropoutSeededFn, _LinearFn, _SwishFn, _TimeAffineFn, _bgemm, _ta_desc, dropout, dropout_constants,
+    dropout_seeded, linear, sincos_embedding, swish, time_affine_all
 )
 from .attention import (  # noqa: F401
     _AttentionFn, _AttentionStreamFn, _ConcatFn, attention, attention_bwd_route, attention_route, attention_streaming, concat_channels

@@ -1,6 +1,8 @@
 """Linear layers, the grouped FeatureWiseAffine launch, Swish, Dropout and the sin / cos embedding (reference
 model/unet.py:27-32, 142-182)."""
 import ctypes
+import functools
+import math
 
 import torch
 
@@ -182,6 +184,76 @@ def dropout(x, p, u=None):
     if u is None:
         u = torch.rand_like(x)
     return _DropoutFn.apply(x, _c(u), p)
+
+
+_DROPOUT_MAX_VIEWS, _DROPOUT_MAX_LAYERS = (1 << 12) - 1, 1 << 16     # csrc/rng.h, kind 5: step = (layer << 12) | view
+
+
+@functools.lru_cache(maxsize=16)
+def dropout_constants(p):
+    """(thr, scale) of the seeded Dropout (csrc/rng.h, "Dropout masks"): thr = ceil(float32(p) * 2^24), the product
+    exact in double precision, and scale = 1.0f / (1.0f - p) evaluated in fp32 as vf_dropout does."""
+    p32 = torch.tensor(float(p), dtype=torch.float32)
+    if not 0.0 <= float(p32) < 1.0:                  # (also refuses NaN)
+        raise ValueError(f"dropout probability has to be in [0, 1), got {p}")
+    return int(math.ceil(float(p32) * 2.0 ** 24)), float(1.0 / (1.0 - p32))
+
+
+class _DropoutSeededFn(torch.autograd.Function):
+    """Dropout whose mask is drawn in the kernel: nothing but ids and off (a few hundred bytes) is saved, and the
+    backward is the same launch on dy."""
+
+    @staticmethod
+    def forward(ctx, x, seed, ids, off, thr, scale, layer):
+        ctx.save_for_backward(ids, off)
+        ctx.args = (seed, thr, scale, layer)
+        return _dropout_seeded_launch(x, seed, ids, off, thr, scale, layer)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ids, off = ctx.saved_tensors
+        seed, thr, scale, layer = ctx.args
+        return _dropout_seeded_launch(_c(dy), seed, ids, off, thr, scale, layer), None, None, None, None, None, None
+
+
+def _dropout_seeded_launch(x, seed, ids, off, thr, scale, layer):
+    y = torch.empty_like(x)
+    S = x.shape[0]
+    _call("vf_dropout_seeded", _ptr(x), _ptr(y), seed, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(off.data_ptr()),
+          ids.numel(), S, x.numel() // S, thr, scale, layer, _stream())
+    return y
+
+
+def dropout_seeded(x, p, seed, ids, off, layer, max_views=None):
+    """nn.Dropout(p) in training mode with the mask drawn inside the kernel from the counter-based generator
+    (csrc/rng.h, kind 5): a pure function of (seed, sample id, view index, layer, element), so it does not depend on the
+    row a sample occupies, on the rest of the batch or on the rank.  Bit-identical to dropout(x, p, u) with
+    u = (word >> 8) * 2^-24; no u exists, forward or saved.
+    x (S, ...): one row per view; ids: device int64 (B,) (ops.sample_ids); off: device int32 (B + 1,) (ops.view_offsets),
+    off[B] == S.  max_views: the largest view count when the caller knows it on the host (view_offsets' third result).
+    ValueError, before any launch, for a sample with more than 4095 views or layer outside [0, 65536)."""
+    _check(x)
+    layer = int(layer)
+    if not 0 <= layer < _DROPOUT_MAX_LAYERS:
+        raise ValueError(f"a seeded Dropout layer index must be in [0, {_DROPOUT_MAX_LAYERS}), got {layer}")
+    B, S = ids.numel(), x.shape[0]
+    if (not ids.is_cuda or ids.dtype != torch.int64 or not ids.is_contiguous() or not off.is_cuda
+            or off.dtype != torch.int32 or not off.is_contiguous() or off.numel() != B + 1):
+        raise _lib.VFHipError(f"seeded Dropout needs device int64 ids (B,) and device int32 off (B + 1,), B = {B}")
+    if max_views is None and S > _DROPOUT_MAX_VIEWS:
+        # only a batch of more than 4095 rows can hold such a sample: the counts are read back in that case alone
+        host = off.cpu()
+        max_views = int((host[1:] - host[:-1]).max())
+    if max_views is not None and max_views > _DROPOUT_MAX_VIEWS:
+        raise ValueError(f"seeded Dropout numbers a sample's views in 12 bits: {max_views} views exceed "
+                         f"{_DROPOUT_MAX_VIEWS}")
+    if S == 0 or x.numel() == 0:
+        return x
+    if (x.numel() // S) % 4:
+        raise ValueError(f"seeded Dropout draws four elements per call: a row of {x.numel() // S} elements is no "
+                         f"multiple of 4")
+    thr, scale = dropout_constants(p)
+    return _DropoutSeededFn.apply(x, int(seed) & 0xFFFFFFFFFFFFFFFF, ids, off, thr, scale, layer)
 
 
 def sincos_embedding(level, angle, dim):

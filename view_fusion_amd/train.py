@@ -205,6 +205,13 @@ class Trainer:
     `model.last_cond_drop` is a static buffer of the captured step (the last micro-batch's with accum_steps > 1).  An
     injected `cond_drop=` mask runs the step eagerly, like every injected argument that is not a graph input.
 
+    Residual-block Dropout (`UNet(dropout=p)`) needs no argument here: with seed= every mask is a function of (seed,
+    sample id, view index, layer, element) drawn inside the Dropout kernel and drawn again by its backward
+    (ops.dropout_seeded).  The seed is a constant of the captured launches; the ids and the offsets table they read, in
+    the forward and in the backward, are the graph's `sample_ids` input and its offsets buffer.  With accum_steps > 1
+    each micro-batch keys its masks by its own slice of the ids, so they are the undivided batch's.  Without seed= the
+    masks come from torch's device generator, as before.
+
     Noise-level sampling (`model.set_level_sampler(...)`, csrc/level_sampler.h; default None: nothing above changes) is the
     model's as well, and every call of it drops the captured steps.  Its three launches -- the table draw in place of the
     uniform one, the scaled loss finish, the statistics update -- are part of the captured step: the table, the

@@ -44,12 +44,17 @@ class _ResBlock(nn.Module):
         self.res_conv = nn.Conv2d(cin, cout, 1) if cin != cout else nn.Identity()
         self.groups = groups
         self.dropout = float(dropout)      # reference: nn.Dropout in block2 only (slot "2", no parameters), unet.py:236
+        self._vf_layer = 0                 # this block's index among the UNet's residual blocks (UNet.__init__ numbers them)
 
-    def _drop(self, a, draws):
-        """block2's nn.Dropout between Swish and the conv: identity in eval mode, as in torch."""
+    def _drop(self, a, draws, rng=None):
+        """block2's nn.Dropout between Swish and the conv: identity in eval mode, as in torch.  Injected draws win; else
+        rng = (seed, ids, off[, max_views]) draws the mask inside the kernel (ops.dropout_seeded, csrc/rng.h kind 5);
+        else torch's device RNG."""
         if self.dropout == 0 or not self.training:
             return a
         from . import ops
+        if draws is None and rng is not None:
+            return ops.dropout_seeded(a, self.dropout, rng[0], rng[1], rng[2], self._vf_layer, *rng[3:4])
         return ops.dropout(a, self.dropout, next(draws) if draws is not None else None)
 
     def _forward_inference(self, x, e, skip, a_in, next_gn):
@@ -84,7 +89,7 @@ class _ResBlock(nn.Module):
             return ops.conv2d(a2, conv2, residual=res, res_fold=fold), None
         return ops.conv2d_gn(a2, conv2, next_gn[0], self.groups, next_gn[1], residual=res, want_y=True, res_fold=fold)
 
-    def forward(self, x, e, skip=None, tap=False, draws=None):
+    def forward(self, x, e, skip=None, tap=False, draws=None, rng=None):
         """tap=True (encoder blocks): also return a handle on the INPUT x for the decoder's skip connection, whose
         gradient is then added inside this block's GroupNorm backward instead of by an autograd add.
         e = this block's FeatureWiseAffine Linear(emb), (S,Cout): all blocks' are computed in one grouped
@@ -100,13 +105,13 @@ class _ResBlock(nn.Module):
         if skip is not None:
             a, x1, x2 = ops.group_norm_cat_skip(x, skip, b1["0"].weight, b1["0"].bias, self.groups, silu=True)
             h = ops.conv2d(a, b1["3"], view_bias=e)
-            a = self._drop(ops.group_norm(h, b2["0"].weight, b2["0"].bias, self.groups, silu=True), draws)
+            a = self._drop(ops.group_norm(h, b2["0"].weight, b2["0"].bias, self.groups, silu=True), draws, rng)
             return ops.conv2d(a, b2["3"], residual=ops.conv1x1_cat(x1, x2, self.res_conv), twin=self.res_conv)
         # x feeds both the first GroupNorm and the residual branch: the GN op hands x back so that
         # the residual gradient is summed inside its backward kernel
         a, xs, xt = ops.group_norm_skip(x, b1["0"].weight, b1["0"].bias, self.groups, silu=True, tap=True)
         h = ops.conv2d(a, b1["3"], view_bias=e)
-        a = self._drop(ops.group_norm(h, b2["0"].weight, b2["0"].bias, self.groups, silu=True), draws)
+        a = self._drop(ops.group_norm(h, b2["0"].weight, b2["0"].bias, self.groups, silu=True), draws, rng)
         twin = None if isinstance(self.res_conv, nn.Identity) else self.res_conv
         skip = xs if twin is None else ops.conv2d(xs, twin)
         y = ops.conv2d(a, b2["3"], residual=skip, twin=twin)
@@ -148,12 +153,12 @@ class _ResAttnBlock(nn.Module):
             return self.attn(y, n), None
         return self.res_block._forward_inference(x, e, skip, a_in, next_gn)
 
-    def forward(self, x, e, skip=None, tap=False, draws=None):
+    def forward(self, x, e, skip=None, tap=False, draws=None, rng=None):
         xt = None
         if tap:
-            x, xt = self.res_block(x, e, skip, tap=True, draws=draws)
+            x, xt = self.res_block(x, e, skip, tap=True, draws=draws, rng=rng)
         else:
-            x = self.res_block(x, e, skip, draws=draws)
+            x = self.res_block(x, e, skip, draws=draws, rng=rng)
         x = self.attn(x) if self.with_attn else x
         return (x, xt) if tap else x
 
@@ -217,6 +222,11 @@ class UNet(nn.Module):
         self.final_conv = _norm_act_conv(ch, out_channel if out_channel is not None else in_channel,
                                          norm_groups)
         self.norm_groups = norm_groups
+        # the residual blocks in execution order (downs, mid, ups): the order of forward()'s dropout_u and the `layer`
+        # of the seeded Dropout masks (csrc/rng.h, kind 5)
+        blocks = [m for m in list(self.downs) + list(self.mid) + list(self.ups) if isinstance(m, _ResAttnBlock)]
+        for i, m in enumerate(blocks):
+            m.res_block._vf_layer = i
         self._annotate_geometry(image_size)
 
     def _annotate_geometry(self, image_size):
@@ -319,12 +329,18 @@ class UNet(nn.Module):
         a = a_next if a_next is not None else ops.group_norm(x, fc["0"].weight, fc["0"].bias, self.norm_groups, silu=True)
         return ops.conv2d(a, fc["3"])
 
-    def forward(self, x, angle, time, dropout_u=None):
+    def forward(self, x, angle, time, dropout_u=None, drop_rng=None):
         """x (S,Cin,H,W), angle (S,1), time = noise level (S,1)  ->  (S,Cout,H,W).
         dropout_u (extra, default None = torch's device RNG): the uniform draws of the residual blocks' Dropout
-        layers in execution order, for parity runs (only consulted when dropout > 0 and self.training)."""
+        layers in execution order, for parity runs (only consulted when dropout > 0 and self.training).
+        drop_rng (extra, default None) = (seed, ids, off): the Dropout masks come from the counter-based generator
+        instead (ops.dropout_seeded: ids device int64 (B,), off device int32 (B + 1,) with row v of x the view v - off[b]
+        of sample b; a fourth entry, the largest view count, spares the op's check a read-back).  Drawn inside the
+        kernel, recomputed in backward, no u tensor; only consulted when dropout > 0, self.training and dropout_u is
+        None."""
         from . import ops
         draws = iter(dropout_u) if dropout_u is not None else None
+        rng = drop_rng if dropout_u is None else None
         ops._check(x)                        # (a CPU tensor is refused as such, before the size check)
         self.check_input_size(x.shape[2], x.shape[3])
         if torch.is_grad_enabled() and self.final_conv["block"]["3"].weight.requires_grad:
@@ -349,7 +365,7 @@ class UNet(nn.Module):
         feats = []
         for layer in self.downs:
             if isinstance(layer, _ResAttnBlock):
-                x, xin = layer(x, next(es), tap=True, draws=draws)
+                x, xin = layer(x, next(es), tap=True, draws=draws, rng=rng)
                 if feats:
                     feats[-1] = xin
             elif isinstance(layer, _Resample):
@@ -362,13 +378,13 @@ class UNet(nn.Module):
         first = True
         for layer in self.mid:
             if first:
-                x, feats[-1] = layer(x, next(es), tap=True, draws=draws)
+                x, feats[-1] = layer(x, next(es), tap=True, draws=draws, rng=rng)
                 first = False
             else:
-                x = layer(x, next(es), draws=draws)
+                x = layer(x, next(es), draws=draws, rng=rng)
         for layer in self.ups:
             if isinstance(layer, _ResAttnBlock):
-                x = layer(x, next(es), feats.pop(), draws=draws)
+                x = layer(x, next(es), feats.pop(), draws=draws, rng=rng)
             else:
                 x = layer(x)
         fc = self.final_conv["block"]

@@ -593,10 +593,10 @@ class ViewFusion(nn.Module):
             elif any(v is None for v in tgt.values()):
                 raise ValueError("distill_z / distill_level / distill_eps / distill_x0 (distill_targets) come together")
             level = tgt["distill_level"].reshape(-1)
-            off, S, _ = ops.view_offsets(view_count, dev)
+            off, S, max_v = ops.view_offsets(view_count, dev)
             self.last_cond_drop = None
             x, level_s, angle_s = ops.stack_views(y_cond, tgt["distill_z"].contiguous(), None, level, angle, off, S)
-            out = self.denoise_fn(x, angle_s, level_s)
+            out = self.denoise_fn(x, angle_s, level_s, **self._drop_rng(seed, sample_ids, off, max_v, b, dev))
             return self._objective(out, tgt["distill_eps"], tgt["distill_x0"], level, off, b)
         # conditioning dropout (set_cond_dropout): an injected mask wins; else drawn in training mode when p > 0
         drop_p = self._cond_drop_p if (cond_drop is None and self.training) else 0.0
@@ -608,6 +608,7 @@ class ViewFusion(nn.Module):
             if smp is None:
                 raise ValueError("the level sampler runs on the GPU only: move the model there and call "
                                  "set_level_sampler again")
+        ids = sample_ids
         if seed is not None:              # whatever was not injected comes from the counter-based generator
             ids = ops.sample_ids(dev, b, sample_ids)
             if drop_p > 0:                # word 2 of the call that gives the sample's t and u
@@ -639,14 +640,25 @@ class ViewFusion(nn.Module):
             drop = torch.rand(b, device=dev) < drop_p
         if level is None:
             level = ops.gather_level(self.gammas, t, u.reshape(-1).contiguous())
-        off, S, _ = ops.view_offsets(view_count, dev)
+        off, S, max_v = ops.view_offsets(view_count, dev)
         if drop is not None:
             drop = ops.diffusion._drop_mask(drop, b, dev)
         self.last_cond_drop = drop
         x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S,
                                               drop=drop)
-        out = self.denoise_fn(x, angle_s, level_s)
+        out = self.denoise_fn(x, angle_s, level_s, **self._drop_rng(seed, ids, off, max_v, b, dev))
         return self._objective(out, noise, y_0, level, off, b, smp, iw, t)
+
+    def _drop_rng(self, seed, sample_ids, off, max_views, b, dev):
+        """The keyword that keys the UNet's residual-block Dropout masks by (seed, sample id, view, layer)
+        (UNet.forward, drop_rng): only with seed=, in training mode and when denoise_fn is our UNet with dropout > 0.
+        Anything else -- a foreign denoise_fn(x, angle, level) above all -- is called as before."""
+        from .unet import UNet
+        fn = self.denoise_fn
+        if seed is None or not self.training or not (isinstance(fn, UNet) and fn._has_dropout()):
+            return {}
+        from . import ops
+        return {"drop_rng": (seed, ops.sample_ids(dev, b, sample_ids), off, max_views)}
 
     def _objective(self, out, noise, y_0, level, off, b, smp=None, iw=None, t=None):
         """The training loss of the composed output against (noise, y_0) at `level`: the reference's MSE, or the
