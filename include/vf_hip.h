@@ -572,6 +572,28 @@ int vf_rng_host_normal(unsigned long long seed, const long long* ids, int kind, 
 int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int T, long long* t, float* u, int B);
 /* vf_draw_cond_drop on the CPU */
 int vf_cond_drop_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* drop /*[B]*/, int B);
+/* ---- self-conditioning (csrc/diffusion.hip holds the definition): the network also sees its own previous estimate of
+ *      the clean image, as three more input channels.  Siblings of the kernels above, which are untouched. ---- */
+/* vf_stack_views_cfg plus the third part: x [S (+ B)][Cc+6][HW], row v = [ cond | target | sc[b] ]; sc (DEVICE
+ * [B][3][HW] | NULL: zeros).  drop / null_rows / copy_cond as there; copy_cond == 0 rewrites the target and sc parts only. */
+int vf_stack_views_sc(const float* y_cond, const float* y_t, const float* noise /*|NULL*/, const float* level,
+                      const float* angle, const int* off /*[B+1]*/, const unsigned char* drop /*[B]|NULL*/,
+                      const float* sc /*[B][3][HW]|NULL*/, float* x, float* level_s, float* angle_s, int B, int Nmax,
+                      int Cc, int HW, int S, int copy_cond, int null_rows, void* stream);
+/* keep[b] = (w3 >> 8) < thr: word 3 of the training-scalar call (kind 0) of sample ids[b]; thr = ceil(p 2^24) <= 2^24 */
+int vf_draw_self_cond(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* keep /*[B]*/, int B,
+                      void* stream);
+/* x_hat[b] = keep[b] clamp(a(g) y_t - b(g) out_b, -1, 1), g = level[b], out_b composed over the sample's rows of unet_out
+ * ([off[B]][Cout][HW]; weighting: softmax of channels 3..5, else the mean); pred 0 eps | 1 v | 2 x0 (x_hat = clamp(out_b),
+ * y and level not read).  y_t of sample b is read at y + row * y_stride + y_off floats (both multiples of 4), row = off[b]
+ * when y_by_view != 0 (the stacked input: y_stride = (Cc + 6) HW, y_off = Cc HW), else b.  keep (DEVICE uint8 [B] | NULL:
+ * all kept); keep[b] == 0 writes zeros. */
+int vf_self_cond_estimate(const float* unet_out, const int* off, const float* level, const float* y /*|NULL for x0*/,
+                          long y_stride, long y_off, int y_by_view, const unsigned char* keep /*[B]|NULL*/,
+                          float* x_hat /*[B][3][HW]*/, int B, int Cout, int HW, int weighting, int pred, void* stream);
+/* Host mirrors (HOST pointers, no stream): vf_draw_self_cond on the CPU, and the (a, b) of the estimate at levels [n] */
+int vf_self_cond_draw_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* out /*[B]*/, int B);
+int vf_self_cond_coeffs_host(const float* level, int pred, float* a /*[n]*/, float* b /*[n]*/, int n);
 
 /* ---- batch assembly from a device-resident view store (csrc/batch.hip; data.ViewStore): the reference loader's
  *      process_sample + collate + H2D, data/nmr_dataset.py:10-52, as one launch.  store: planar uint8 [N][24][3][H][W],

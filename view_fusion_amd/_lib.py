@@ -178,6 +178,11 @@ SIGNATURES = {
     "vf_distill_target": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P],
     "vf_distill_step_host": [_U64, _P, _I, _P, _I],
     "vf_loss_weights_trunc_snr_host": [_P, _I, _I, _P],
+    "vf_stack_views_sc": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "vf_draw_self_cond": [_U64, _P, ctypes.c_uint, _P, _I, _P],
+    "vf_self_cond_estimate": [_P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _I, _P],
+    "vf_self_cond_draw_host": [_U64, _P, ctypes.c_uint, _P, _I],
+    "vf_self_cond_coeffs_host": [_P, _I, _P, _P, _I],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

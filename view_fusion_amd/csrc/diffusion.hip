@@ -44,6 +44,8 @@
 //                   selection on a plain buffer: abs_quantile_kernel) -> an EPS tail: the thresholded / rescaled step.
 //   distillation    distill_begin_kernel (the draw of i, z_t) and distill_target_kernel<CFG> (the second teacher step's tail:
 //                   x2, x~, eps~), siblings of draw_train / stack_views and of sampler_step_kernel.
+//   self-conditioning  stack_views_sc_kernel (stack_views_cfg_kernel plus the third part), self_cond_estimate_kernel<PRED>
+//                   (the first pass's clamped x0 estimate) and draw_self_cond_kernel: siblings, behind the distillation pair.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
 //                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The five
@@ -140,6 +142,34 @@
 //   The draw of i (seeded): i_b = mulhi32(w0, K), w0 = word 0 of the sample's kind-0 call (where t comes from otherwise);
 //   an injected i is clamped to 0..K-1 before any table is read.  i, k1, k0 (int64), g, tables and weights live in device
 //   memory: a captured phase replays for every step.  No EPS / threshold / rescale flavour.
+//
+// Self-conditioning (Chen et al., "Analog Bits", 2.2): the network is also shown its own previous estimate of the clean
+// image.  This comment is the ONE written definition; tests/selfcond_ref.py restates it.  Opt-in: three sibling kernels
+// (stack_views_sc_kernel, self_cond_estimate_kernel<PRED>, draw_self_cond_kernel), everything above is untouched.
+//   Input.  UNet(in_channel = Cc + 6): row v of sample b is [ cond (Cc) | noisy target (3) | sc_b (3) ], Cc = 3 or 6 as
+//     before; sc_b is the same in all the sample's rows; under guidance the null row S + b is [ 0 | y_b | sc_b ];
+//     sc_b = 0 means "no estimate".  The first Cc + 3 channels are stack_views_cfg_kernel's expressions.
+//   Estimate (training; g = level[b], the sample's continuous level; out_b = the composition over the sample's views of
+//     channels 0..2 under weighting_train: compose4, softmax of channels 3..5 or the mean):
+//       x^_b = keep_b clamp(a(g) y_t - b(g) out_b, -1, 1)
+//     with y_t READ BACK from the target part of the stacked input the first pass saw (stack_views_kernel's q_sample
+//     expression, so its bits), and, in fp32,
+//       eps   a = sqrtf(1 / g),  b = sqrtf((1 - g) / g)    ( = sqrt(1 / g - 1) without its cancellation at g -> 1: 1 - g is
+//                                                            exact for g >= 1/2, so b is within 2 ulp for every level)
+//       v     a = sqrtf(g),      b = sqrtf(1 - g)
+//       x0    a = 0, b = -1: x^ = clamp(out) to the bit -- y_t is not read and nothing is multiplied.
+//     Rounding: a y_t and b out_b are each rounded, then subtracted (y0_hat_as<false>, as sampler_step_kernel forms y0),
+//     then clamped; keep_b = 0 writes exact zeros and reads nothing of `out`.  vf_self_cond_coeffs (below) is the one copy
+//     of (a, b); vf_self_cond_coeffs_host runs it on the CPU.
+//   Coin.  keep_b = 1 with probability p, per sample.  Seeded: keep = (w3 >> 8) < thr, thr = ceil(p 2^24) on the host, w3 =
+//     word 3 of the kind-0, step-0, block-0 call that gives t (word 0), u (word 1) and the conditioning drop (word 2): an
+//     integer compare and a function of (seed, sample id) alone.  p = 0 launches nothing extra; p = 1 keeps every sample.
+//   Training step.  Pass 1, no gradient, no Dropout: the stacked input with zero sc channels (same y_t, level, angle and
+//     conditioning-drop mask as pass 2) -> out -> x^.  Pass 2: the ordinary step on the input whose sc channels hold x^.
+//     Samples with keep = 0 still run pass 1 (static shapes).  The objective is unchanged.
+//   Sampling.  sc = the history buffer sampler_step_kernel writes (y0_prev: the step's final y0 -- clamped or thresholded,
+//     guided), zero before the first step; the stacking kernel reads it at the top of a step, the tail overwrites it at the
+//     end.  With dpmpp2m the tail reads the same buffer as its own history: both want the previous step's y0.
 #include "common.h"
 #include "level_sampler.h"
 #include "loss_weight.h"
@@ -1343,6 +1373,116 @@ __global__ __launch_bounds__(256) void distill_target_kernel(
     }
 }
 
+// ---- self-conditioning (the head of this file) ----
+// stack_views_cfg_kernel plus the third part: row v = [ cond (nc4) | target (n4) | sc_b (n4) ], sc (B,3,HW) | null = zeros.
+// grid (chunks, rows), rows = S or S + B; the first two parts are that kernel's expressions, so equal inputs give equal
+// bits.  copy_cond == 0 rewrites the target and sc parts only (the per-step re-stack of generate).
+__global__ void stack_views_sc_kernel(const float4* __restrict__ y_cond, const float4* __restrict__ y_t,
+                                      const float4* __restrict__ noise, const float* __restrict__ level,
+                                      const float* __restrict__ angle, const int* __restrict__ off,
+                                      const unsigned char* __restrict__ drop, const float4* __restrict__ sc,
+                                      float4* __restrict__ x, float* __restrict__ level_s, float* __restrict__ angle_s,
+                                      int B, int Nmax, int nc4, int n4, int copy_cond, int S) {
+    const int v = blockIdx.y;
+    const bool null_row = v >= S;
+    const int b = null_row ? v - S : sample_of_view(off, B, v);
+    const int j = null_row ? 0 : v - off[b];
+    const bool zero = null_row || (drop != nullptr && drop[b] != 0);
+    const float lv = level[b];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        level_s[v] = lv;
+        angle_s[v] = angle[b];
+    }
+    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    const float4* c = y_cond + ((size_t)b * Nmax + j) * nc4;
+    const float4* t = y_t + (size_t)b * n4;
+    const float4* z = noise ? noise + (size_t)b * n4 : nullptr;
+    const float4* s = sc ? sc + (size_t)b * n4 : nullptr;
+    float4* o = x + (size_t)v * (nc4 + 2 * (size_t)n4);
+    if (copy_cond) {
+        if (zero)
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x)
+                o[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        else
+            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x) o[i] = c[i];
+    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
+        float4 y = t[i];
+        if (z) {
+            const float4 e = z[i];
+            y.x = sa * y.x + sb * e.x;
+            y.y = sa * y.y + sb * e.y;
+            y.z = sa * y.z + sb * e.z;
+            y.w = sa * y.w + sb * e.w;
+        }
+        o[nc4 + i] = y;
+        o[nc4 + n4 + i] = s ? s[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// keep[b] = the self-conditioning coin of sample ids[b] (rng.h: word 3 of the training-scalar call against thr)
+__global__ void draw_self_cond_kernel(unsigned long long seed, const long long* __restrict__ ids, unsigned thr,
+                                      unsigned char* __restrict__ keep, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    uint32_t w[4];
+    vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+    keep[b] = (unsigned char)vf_rng_self_cond(w[3], thr);
+}
+
+// (a, b) of x^ = a y_t - b out at the continuous level g, in fp32 (the head of this file); x0: (0, -1), not multiplied.
+__host__ __device__ inline void vf_self_cond_coeffs(int pred, float g, float* a, float* b) {
+    if (pred == VF_PRED_V) {
+        *a = sqrtf(g);
+        *b = sqrtf(1.0f - g);
+    } else if (pred == VF_PRED_X0) {
+        *a = 0.0f;
+        *b = -1.0f;
+    } else {
+        *a = sqrtf(1.0f / g);
+        *b = sqrtf((1.0f - g) / g);
+    }
+}
+
+// x^[b] = keep[b] clamp(a y_t - b out_b, -1, 1): out_b composed with compose4 from the first pass's output, y_t read at
+// y + row * y_stride + y_off (floats; row = off[b] for the stacked input, b for a plain buffer).  grid (chunks, B); one
+// read of each input, one write, no atomics.  keep (uint8 [B] | null = all kept); a sample with keep = 0 gets exact zeros.
+template <int PRED>
+__global__ __launch_bounds__(256) void self_cond_estimate_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ level,
+    const float* __restrict__ y, long long y_stride, long long y_off, int y_by_view,
+    const unsigned char* __restrict__ keep, float* __restrict__ x_hat, int Cout, int HW, int weighting) {
+    const int b = blockIdx.y;
+    const int n4 = 3 * HW / 4;
+    float* xo = x_hat + (size_t)b * 3 * HW;
+    if (keep != nullptr && keep[b] == 0) {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256)
+            *reinterpret_cast<float4*>(xo + 4 * (size_t)i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const int v0 = off[b], v1 = off[b + 1];
+    float a_g = 0.f, b_g = -1.f;
+    const float* yt = nullptr;
+    if (PRED != VF_PRED_X0) {
+        vf_self_cond_coeffs(PRED, level[b], &a_g, &b_g);
+        yt = y + (size_t)(y_by_view ? v0 : b) * (size_t)y_stride + (size_t)y_off;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const float4 e = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
+        float r[4] = {e.x, e.y, e.z, e.w};
+        if (PRED != VF_PRED_X0) {
+            const float4 yy = *reinterpret_cast<const float4*>(yt + 4 * (size_t)i);
+            const float ys[4] = {yy.x, yy.y, yy.z, yy.w};
+#pragma unroll
+            for (int q = 0; q < 4; ++q) r[q] = y0_hat_as<false>(a_g, ys[q], b_g, r[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r[q] = fminf(fmaxf(r[q], -1.0f), 1.0f);
+        *reinterpret_cast<float4*>(xo + 4 * (size_t)i) = make_float4(r[0], r[1], r[2], r[3]);
+    }
+}
+
 // ---- the loss family: the run-time (penalty, pred) -> the kernel pair (the launchers stand with the entry points) ----
 struct LossKernels {
     decltype(&compose_loss_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) fwd;
@@ -1913,6 +2053,73 @@ int vf_distill_step_host(unsigned long long seed, const long long* ids, int K, l
 int vf_loss_weights_trunc_snr_host(const float* level, int B, int pred, float* out) {
     if (B < 0 || pred < VF_PRED_EPS || pred > VF_PRED_X0) return (int)hipErrorInvalidValue;
     for (int s = 0; s < B; ++s) out[s] = vf_loss_weight_pred(pred, VF_LOSS_W_TRUNC_SNR, 0.0f, 0.0f, level[s]);
+    return 0;
+}
+
+// ---- self-conditioning (the head of this file) ----
+// vf_stack_views_cfg plus sc (DEVICE [B][3][HW] | NULL: zeros): x [S (+ B)][Cc+6][HW], level_s / angle_s [S (+ B)].
+int vf_stack_views_sc(const float* y_cond, const float* y_t, const float* noise, const float* level, const float* angle,
+                      const int* off, const unsigned char* drop, const float* sc, float* x, float* level_s,
+                      float* angle_s, int B, int Nmax, int Cc, int HW, int S, int copy_cond, int null_rows,
+                      void* stream) {
+    if (S <= 0 || B <= 0) return 0;
+    if ((HW & 3) || Cc < 1 || (null_rows && S < B)) return (int)hipErrorInvalidValue;
+    if (!y_t || !level || !angle || !off || !x || !level_s || !angle_s || (copy_cond && !y_cond))
+        return (int)hipErrorInvalidValue;
+    const int rows = null_rows ? S + B : S;
+    if (rows > 65535) return (int)hipErrorInvalidValue;
+    const int n4 = 3 * HW / 4, nc4 = Cc * HW / 4;
+    hipLaunchKernelGGL(stack_views_sc_kernel, dim3(chunks_for(nc4 > n4 ? nc4 : n4), rows), dim3(256), 0,
+                       (hipStream_t)stream, (const float4*)y_cond, (const float4*)y_t, (const float4*)noise, level, angle,
+                       off, drop, (const float4*)sc, (float4*)x, level_s, angle_s, B, Nmax, nc4, n4, copy_cond, S);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_draw_self_cond(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* keep, int B,
+                      void* stream) {
+    if (B <= 0) return 0;
+    if (thr > (1u << 24) || !ids || !keep) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(draw_self_cond_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, seed, ids, thr, keep,
+                       B);
+    VF_RETURN_LAST_ERROR();
+}
+
+// unet_out [off[B]][Cout][HW]: the first pass's output; y_t of sample b at y + row * y_stride + y_off floats, row = off[b]
+// (y_by_view != 0: the stacked input, y_stride = (Cc + 6) HW, y_off = Cc HW) or b (a plain [B][3][HW] buffer: 3 HW, 0);
+// both multiples of 4; y is not read for pred 2 (x0) and may be NULL there.  keep (DEVICE uint8 [B] | NULL: all kept).
+int vf_self_cond_estimate(const float* unet_out, const int* off, const float* level, const float* y, long y_stride,
+                          long y_off, int y_by_view, const unsigned char* keep, float* x_hat, int B, int Cout, int HW,
+                          int weighting, int pred, void* stream) {
+    if (B <= 0) return 0;
+    if (HW <= 0 || (HW & 3) || Cout < 3 || (weighting && Cout < 6) || B > 65535) return (int)hipErrorInvalidValue;
+    if (pred < VF_PRED_EPS || pred > VF_PRED_X0 || !unet_out || !off || !x_hat) return (int)hipErrorInvalidValue;
+    if (pred != VF_PRED_X0 && (!y || !level || y_stride < 3l * HW || y_off < 0 || (y_stride & 3) || (y_off & 3) ||
+                               y_off + 3l * HW > y_stride))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(chunks_for(3 * HW / 4), B);
+    auto kernel = pred == VF_PRED_V ? self_cond_estimate_kernel<VF_PRED_V>
+                                    : (pred == VF_PRED_X0 ? self_cond_estimate_kernel<VF_PRED_X0>
+                                                          : self_cond_estimate_kernel<VF_PRED_EPS>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, unet_out, off, level, y, (long long)y_stride,
+                       (long long)y_off, y_by_view, keep, x_hat, Cout, HW, weighting);
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirrors.  The coin on the CPU: out[b] = (word 3 >> 8) < thr for the ids (HOST int64 [B]) ...
+int vf_self_cond_draw_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* out, int B) {
+    if (B < 0 || thr > (1u << 24)) return (int)hipErrorInvalidValue;
+    for (int b = 0; b < B; ++b) {
+        uint32_t w[4];
+        vf_rng_words(seed, (unsigned long long)ids[b], VF_RNG_TRAIN_SCALARS, 0, 0, w);
+        out[b] = (unsigned char)vf_rng_self_cond(w[3], thr);
+    }
+    return 0;
+}
+
+// ... and vf_self_cond_coeffs itself: (a, b) of the estimate at levels level [n] for pred 0 | 1 | 2.
+int vf_self_cond_coeffs_host(const float* level, int pred, float* a, float* b, int n) {
+    if (n < 0 || pred < VF_PRED_EPS || pred > VF_PRED_X0) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i) vf_self_cond_coeffs(pred, level[i], &a[i], &b[i]);
     return 0;
 }
 

@@ -11,7 +11,8 @@
 //   stream  = (kind << 28) | step                             step < 2^28
 //   block   = the float4 index inside the sample's (3, H, W) image; 0 for kind 0
 //
-//   kind 0  training scalars, step 0: word 0 -> t, word 1 -> u, word 2 -> the conditioning-dropout draw (below)
+//   kind 0  training scalars, step 0: word 0 -> t, word 1 -> u, word 2 -> the conditioning-dropout draw, word 3 -> the
+//           self-conditioning coin (both below)
 //   kind 1  training noise, step 0
 //   kind 2  sampler start noise y_T, step 0
 //   kind 3  reverse-step noise z, step = the timestep index t[b]
@@ -25,6 +26,9 @@
 //   drop = (w2 >> 8) < thr              conditioning dropout (classifier-free guidance, diffusion.hip): thr = ceil(p * 2^24)
 //                                       from the host, an integer compare like the view store's 10 % draw below, so no
 //                                       float rounding takes part; P(drop) = thr / 2^24 (p = 1 drops all, p = 0 none)
+//   keep = (w3 >> 8) < thr              the self-conditioning coin (diffusion.hip): the sample's estimate is fed back iff keep;
+//                                       thr = ceil(p * 2^24) from the host, the same integer compare on the word the call
+//                                       left unused; P(keep) = thr / 2^24 (p = 1 keeps all, p = 0 none)
 //   normals, four per call (Box-Muller): with U(w) = float(w) * 2^-32 + 2^-33 (round to nearest; in (0, 1], so the
 //   logarithm never sees 0; the scale is a power of two, so contracting the multiply-add cannot change the result)
 //     r = sqrtf(-2 * logf(U(w0))), a = 6.283185307179586f * U(w1)  ->  (r * cosf(a), r * sinf(a))
@@ -127,6 +131,8 @@ VF_RNG_HD long long vf_rng_distill_step(uint32_t w0, int K) { return (long long)
 VF_RNG_HD float vf_rng_uniform24(uint32_t w1) { return (float)(w1 >> 8) * 5.9604644775390625e-8f; }   // 2^-24
 
 VF_RNG_HD int vf_rng_cond_drop(uint32_t w2, uint32_t thr) { return (w2 >> 8) < thr; }   // thr = ceil(p * 2^24) <= 2^24
+
+VF_RNG_HD int vf_rng_self_cond(uint32_t w3, uint32_t thr) { return (w3 >> 8) < thr; }   // the self-conditioning coin, likewise
 
 // Dropout masks (kind 5): kept iff (w >> 8) >= thr, thr = ceil(float32(p) * 2^24) <= 2^24 -- the same predicate as
 // vf_rng_uniform24(w) >= float32(p)

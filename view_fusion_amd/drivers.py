@@ -129,7 +129,9 @@ def _check_distill_extra(d):
 def save_checkpoint(path, model, optimizer, **extra):
     """{"model": state_dict, "optimizer": state_dict, + extra (it, t, run_id, ssim, psnr)} -- the
     reference's file layout, so either side can load the other's checkpoints.  distill=dict(steps=K) records the stage of
-    a progressive distillation (load_checkpoint); the teacher's weights are not part of the file."""
+    a progressive distillation (load_checkpoint); the teacher's weights are not part of the file.
+    self_cond=model.self_cond records the self-conditioning setting, which state_dict() does not hold (only the stem's
+    shape differs)."""
     out = dict(extra)
     if out.get("distill") is not None:
         _check_distill_extra(out["distill"])
@@ -149,7 +151,9 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     before anything is loaded.  A "distill" entry (save_checkpoint(..., distill=dict(steps=K)): the stage of a progressive
     distillation the weights were saved in -- the model samples in K steps, and its next stage is K / 2 with these weights
     as the teacher) is a plain dict with an integer steps >= 1, checked (ValueError otherwise) and returned with the other
-    extras: the caller builds the teacher and calls set_distill.  Files without the entry load as before."""
+    extras: the caller builds the teacher and calls set_distill.  A "self_cond" entry (save_checkpoint(...,
+    self_cond=model.self_cond): the self-conditioning probability, or None) must equal the model's own: ValueError
+    otherwise, before anything is loaded.  Files without the entry load as before."""
     sd = torch.load(path, map_location=device, weights_only=False)
     if sd.get("distill") is not None:
         _check_distill_extra(sd["distill"])
@@ -157,6 +161,9 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     if sd.get("prediction") is not None and sd["prediction"] != mine:
         raise ValueError(f"the checkpoint was trained with prediction {sd['prediction']!r}, the model is set to {mine!r} "
                          "(set_prediction)")
+    if "self_cond" in sd and sd["self_cond"] != getattr(model, "self_cond", None):
+        raise ValueError(f"the checkpoint was trained with self-conditioning {sd['self_cond']!r}, the model is set to "
+                         f"{getattr(model, 'self_cond', None)!r} (set_self_cond)")
     model.load_state_dict(sd["model"])
     if optimizer is not None and "optimizer" in sd and sd["optimizer"].get("state"):
         optimizer.load_state_dict(sd["optimizer"])

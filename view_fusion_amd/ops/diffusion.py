@@ -127,12 +127,16 @@ def philox_ids(seed, ids, kind, step, n):
     return out
 
 
-def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True, drop=None, null_rows=False):
+def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True, drop=None, null_rows=False,
+                self_cond=None, sc_channels=False):
     """Ragged stacking (+ optional q_sample): -> x (S,Cc+3,H,W), level_s (S,1), angle_s (S,1); Cc = y_cond's
     channel count (3, or 6 for the `relative` configs).
     Classifier-free guidance (csrc/diffusion.hip), through a sibling kernel taken only when one of the two is used:
     drop (device bool / uint8 (B,)): the conditioning half of every row of a sample with drop[b] != 0 is zeros;
-    null_rows=True: S + B rows come back, row S + b = [ 0 | y_t[b] ] with the sample's own level and angle."""
+    null_rows=True: S + B rows come back, row S + b = [ 0 | y_t[b] ] with the sample's own level and angle.
+    Self-conditioning (csrc/diffusion.hip), through a third sibling taken only when asked for: self_cond (B,3,H,W) --
+    x is (rows,Cc+6,H,W) and every row of sample b (its null row too) ends with self_cond[b]; sc_channels=True with
+    self_cond=None writes zeros there ("no estimate").  The first Cc + 3 channels carry the bits of the call without it."""
     y_cond, y_t = _c(y_cond), _c(y_t)
     angle = _c(angle.reshape(-1).float())
     _check(y_cond, y_t, noise, level, angle)
@@ -140,12 +144,32 @@ def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True
     if y_t.shape[1] != 3:
         raise ValueError(f"the noisy target must have 3 channels, got {tuple(y_t.shape)}")
     rows = S + B if null_rows else S
+    sc_on = self_cond is not None or sc_channels
+    Cx = Cc + (6 if sc_on else 3)
     if x is None:
-        x = torch.empty(rows, Cc + 3, H, W, device=y_cond.device, dtype=torch.float32)
+        x = torch.empty(rows, Cx, H, W, device=y_cond.device, dtype=torch.float32)
     elif x.shape[0] != rows:
         raise ValueError(f"stack_views writes {rows} rows, x has {x.shape[0]}")
     ls = torch.empty(rows, 1, device=y_cond.device, dtype=torch.float32)
     as_ = torch.empty(rows, 1, device=y_cond.device, dtype=torch.float32)
+    if sc_on:
+        _check(x, self_cond)
+        if tuple(x.shape) != (rows, Cx, H, W):
+            raise ValueError(f"a self-conditioned stack_views writes x of shape {(rows, Cx, H, W)}, got {tuple(x.shape)}")
+        if self_cond is not None and tuple(self_cond.shape) != tuple(y_t.shape):
+            raise ValueError(f"self_cond must have the target's shape {tuple(y_t.shape)}, got {tuple(self_cond.shape)}")
+        if level.numel() != B or angle.numel() != B or y_t.shape[0] != B or tuple(y_t.shape[2:]) != (H, W) or \
+                (noise is not None and tuple(noise.shape) != tuple(y_t.shape)):
+            raise ValueError(f"stack_views needs y_t (and noise) of shape {(B, 3, H, W)} and one level and angle per sample")
+        if off.dtype != torch.int32 or off.numel() != B + 1 or rows > 65535:
+            raise ValueError(f"off must be the int32 offsets table of {B} samples (ops.view_offsets), at most 65535 rows")
+        if drop is not None:
+            drop = _drop_mask(drop, B, y_cond.device)
+        _call("vf_stack_views_sc", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
+              ctypes.c_void_p(off.data_ptr()), None if drop is None else ctypes.c_void_p(drop.data_ptr()),
+              _ptr(self_cond), _ptr(x), _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond),
+              int(bool(null_rows)), _stream())
+        return x, ls, as_
     if drop is None and not null_rows:
         _call("vf_stack_views", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
               ctypes.c_void_p(off.data_ptr()), _ptr(x), _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond),
@@ -831,6 +855,92 @@ def distill_target(unet_out, off, y, x1, z_t, level_s, i, k0, tables, w1, w2, B,
           _ptr(tables["b"]), _ptr(w1), _ptr(w2), _ptr(x_t), _ptr(e_t), B, Cout, H * W, int(weighting), _ptr(guidance),
           _stream())
     return x_t, e_t
+
+
+# ---- self-conditioning (csrc/diffusion.hip holds the definition) ----
+def self_cond_threshold(p):
+    """thr = ceil(p * 2^24) of the seeded self-conditioning coin, p in [0, 1] (p * 2^24 is exact in double precision)."""
+    p = float(p)
+    if not 0.0 <= p <= 1.0:                      # (also refuses NaN)
+        raise ValueError(f"the self-conditioning probability must be in [0, 1], got {p}")
+    return int(math.ceil(p * 2.0 ** 24))
+
+
+def draw_self_cond(seed, ids, p):
+    """The seeded self-conditioning coin of samples `ids`: device uint8 (B,), 1 = the estimate is fed back.  A function
+    of (seed, id) alone: word 3 of the call that gives the sample's t, u and conditioning drop, against ceil(p * 2^24).
+    One launch."""
+    thr = self_cond_threshold(p)
+    B = ids.numel()
+    _check_ids(ids, B)
+    keep = torch.empty(B, device=ids.device, dtype=torch.uint8)
+    _call("vf_draw_self_cond", _seed(seed), ctypes.c_void_p(ids.data_ptr()), thr, ctypes.c_void_p(keep.data_ptr()), B,
+          _stream())
+    return keep
+
+
+def self_cond_draw_host(seed, ids, p):
+    """The host mirror of draw_self_cond: ids (any integer tensor / sequence) -> uint8 CPU tensor.  No GPU."""
+    thr = self_cond_threshold(p)
+    ids = torch.as_tensor(ids).detach().cpu().reshape(-1).to(torch.int64).contiguous()
+    out = torch.empty(ids.numel(), dtype=torch.uint8)
+    rc = _lib.load().vf_self_cond_draw_host(_seed(seed), ctypes.c_void_p(ids.data_ptr()), thr,
+                                            ctypes.c_void_p(out.data_ptr()), ids.numel())
+    if rc != 0:
+        raise _lib.VFHipError(f"vf_self_cond_draw_host failed with {rc}")
+    return out
+
+
+def self_cond_coeffs_host(level, prediction="eps"):
+    """The host mirror of the estimate's coefficients: levels -> (a, b) float32 CPU tensors of x^ = a y_t - b out.  No GPU."""
+    check_prediction(prediction)
+    lv = torch.as_tensor(level, dtype=torch.float32).detach().cpu().reshape(-1).contiguous()
+    a, b = torch.empty_like(lv), torch.empty_like(lv)
+    rc = _lib.load().vf_self_cond_coeffs_host(ctypes.c_void_p(lv.data_ptr()), PREDICTIONS[prediction],
+                                              ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()), lv.numel())
+    if rc != 0:
+        raise _lib.VFHipError(f"vf_self_cond_coeffs_host failed with {rc}")
+    return a, b
+
+
+def self_cond_estimate(unet_out, off, level, B, weighting, prediction="eps", x=None, y_t=None, keep=None):
+    """The self-conditioning estimate of a first pass, one launch: -> x^ (B,3,H,W) = keep_b clamp(a(g) y_t - b(g) out_b, -1, 1),
+    out_b the composition of unet_out (S rows) over the sample's views (weighting: softmax of channels 3..5, else the
+    mean), g = level[b] (device fp32 (B,)).  y_t is read back from the stacked input x (S,Cc+6,H,W) the pass saw -- its
+    channels Cc..Cc+2 in the sample's first row -- or from a plain y_t (B,3,H,W); "x0" reads neither.  keep (device
+    bool / uint8 (B,), default None: every sample): a sample with keep = 0 gets exact zeros."""
+    check_prediction(prediction)
+    _check(unet_out, level, x, y_t)
+    if unet_out.dim() != 4:
+        raise ValueError(f"self_cond_estimate takes unet_out (S, C, H, W), got {tuple(unet_out.shape)}")
+    S, Cout, H, W = unet_out.shape
+    HW = H * W
+    if HW % 4 or Cout < (6 if weighting else 3):
+        raise ValueError(f"self_cond_estimate needs H W % 4 == 0 and {6 if weighting else 3} output channels, got "
+                         f"{tuple(unet_out.shape)}")
+    if off.dtype != torch.int32 or off.numel() != B + 1 or not off.is_cuda or level.numel() != B or B > 65535:
+        raise ValueError(f"self_cond_estimate needs the int32 offsets table of {B} samples (ops.view_offsets) and one level "
+                         "per sample")
+    src, stride, choff, by_view = None, 0, 0, 0
+    if prediction != "x0":
+        if (x is None) == (y_t is None):
+            raise ValueError("self_cond_estimate reads y_t from exactly one of x= (the stacked input) and y_t=")
+        if x is not None:
+            if x.dim() != 4 or x.shape[0] < S or x.shape[1] < 7 or tuple(x.shape[2:]) != (H, W):
+                raise ValueError(f"x must be the self-conditioned stacked input (rows >= {S}, Cc + 6, {H}, {W}), got "
+                                 f"{tuple(x.shape)}")
+            src, stride, choff, by_view = x, x.shape[1] * HW, (x.shape[1] - 6) * HW, 1
+        else:
+            if tuple(y_t.shape) != (B, 3, H, W):
+                raise ValueError(f"y_t must have shape {(B, 3, H, W)}, got {tuple(y_t.shape)}")
+            src, stride = y_t, 3 * HW
+    if keep is not None:
+        keep = _drop_mask(keep, B, unet_out.device)
+    x_hat = torch.empty(B, 3, H, W, device=unet_out.device, dtype=torch.float32)
+    _call("vf_self_cond_estimate", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(level), _ptr(src), stride, choff,
+          by_view, None if keep is None else ctypes.c_void_p(keep.data_ptr()), _ptr(x_hat), B, Cout, HW, int(weighting),
+          PREDICTIONS[prediction], _stream())
+    return x_hat
 
 
 def psnr(generated, target):

@@ -203,7 +203,15 @@ class Trainer:
     model's too, and p is part of the same key: a change between steps drops the captured steps.  With seed= a sample's
     mask is a function of (seed, sample id) -- the same under accum_steps, graph replay and any split over ranks;
     `model.last_cond_drop` is a static buffer of the captured step (the last micro-batch's with accum_steps > 1).  An
-    injected `cond_drop=` mask runs the step eagerly, like every injected argument that is not a graph input.
+    injected `cond_drop=` mask is a graph input, like the injected draws.
+
+    Self-conditioning (`model.set_self_cond(p)`, csrc/diffusion.hip; default None: nothing above changes) is the model's
+    as well, and p is part of the same key.  Its first pass -- the no-grad forward that makes the estimate
+    (ViewFusion.self_cond_targets) -- runs launch by launch in front of every (micro-)step, in every launch mode, and
+    hands the step `self_cond` (and, without seed=, the t / u / noise / cond_drop it drew) as injected inputs, which are
+    graph inputs: a captured step holds the second pass alone.  With seed= a sample's coin is a function of (seed,
+    sample id), the same under accum_steps and graph replay.  `model.last_self_cond` = (keep, x^) of the last first pass.
+    Multi-rank: the phase has no collective; nothing else is built for it.
 
     Residual-block Dropout (`UNet(dropout=p)`) needs no argument here: with seed= every mask is a function of (seed,
     sample id, view index, layer, element) drawn inside the Dropout kernel and drawn again by its backward
@@ -455,7 +463,7 @@ class Trainer:
             return None
         # injected draws are graph inputs, and so are the sample ids of the seeded draws and the teacher phase's outputs of a
         # distillation step; the seed is a constant of the captured launches, so it is part of the key; nothing else is
-        if any(k not in ("t", "u", "noise", "seed", "sample_ids") + DISTILL_INPUTS for k in extra):
+        if any(k not in ("t", "u", "noise", "seed", "sample_ids", "self_cond", "cond_drop") + DISTILL_INPUTS for k in extra):
             return None
         seed = extra.get("seed")
         extra = {k: v for k, v in extra.items() if k != "seed" and v is not None}
@@ -670,6 +678,14 @@ class Trainer:
             draws = {k: extra[k] for k in ("t", "noise", "seed", "sample_ids") if extra.get(k) is not None}
             tgt = self.module.distill_targets(batch["y_cond"], batch["view_count"], batch["angle"], batch["y_0"], **draws)
             extra = {**{k: v for k, v in extra.items() if k not in ("t", "u", "noise")}, **tgt}
+        if getattr(self.module, "self_cond", None) is not None and "self_cond" not in extra:
+            # self-conditioning: the first pass of this (micro-)batch, no-grad and launch by launch, in front of the step,
+            # which takes the estimate (and, unseeded, the draws the pass used) as injected inputs -- so a capture holds
+            # the second pass alone, and its accounting is the default step's
+            draws = {k: extra[k] for k in ("t", "u", "noise", "cond_drop", "seed", "sample_ids") if extra.get(k) is not None}
+            first = self.module.self_cond_targets(batch["y_cond"], batch["view_count"], batch["angle"], batch["y_0"],
+                                                  **draws)
+            extra = {**extra, **first}
         key, vc = self._graph_key(batch, extra) or (None, None)
         if key is not None and accum is None and self._graph_epoch is not None and \
                 self.opt.graph_epoch != self._graph_epoch:      # (a micro-batch graph addresses no Adam state)

@@ -329,7 +329,7 @@ class UNet(nn.Module):
         a = a_next if a_next is not None else ops.group_norm(x, fc["0"].weight, fc["0"].bias, self.norm_groups, silu=True)
         return ops.conv2d(a, fc["3"])
 
-    def forward(self, x, angle, time, dropout_u=None, drop_rng=None):
+    def forward(self, x, angle, time, dropout_u=None, drop_rng=None, no_dropout=False):
         """x (S,Cin,H,W), angle (S,1), time = noise level (S,1)  ->  (S,Cout,H,W).
         dropout_u (extra, default None = torch's device RNG): the uniform draws of the residual blocks' Dropout
         layers in execution order, for parity runs (only consulted when dropout > 0 and self.training).
@@ -337,8 +337,12 @@ class UNet(nn.Module):
         instead (ops.dropout_seeded: ids device int64 (B,), off device int32 (B + 1,) with row v of x the view v - off[b]
         of sample b; a fourth entry, the largest view count, spares the op's check a read-back).  Drawn inside the
         kernel, recomputed in backward, no u tensor; only consulted when dropout > 0, self.training and dropout_u is
-        None."""
+        None.
+        no_dropout (extra, default False): under no_grad, run the inference path -- which has no Dropout -- even in
+        training mode (the first pass of a self-conditioned step: the estimate a sampler feeds back is made without it)."""
         from . import ops
+        if no_dropout and torch.is_grad_enabled():
+            raise ValueError("no_dropout= belongs to a no-grad forward (the inference path)")
         draws = iter(dropout_u) if dropout_u is not None else None
         rng = drop_rng if dropout_u is None else None
         ops._check(x)                        # (a CPU tensor is refused as such, before the size check)
@@ -346,7 +350,7 @@ class UNet(nn.Module):
         if torch.is_grad_enabled() and self.final_conv["block"]["3"].weight.requires_grad:
             ops.pack_all(self, x.shape[0], tuple(x.shape[2:]))   # training: all conv layers re-packed (one launch per format)
         mlp = self.noise_level_mlp
-        inference = not torch.is_grad_enabled() and not (self.training and self._has_dropout())
+        inference = not torch.is_grad_enabled() and (no_dropout or not (self.training and self._has_dropout()))
 
         def embed():
             pe = ops.sincos_embedding(time, angle, self.inner_channel)                  # (S,inner)

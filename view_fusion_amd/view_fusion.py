@@ -45,6 +45,10 @@ prediction, so generate() and everything built on it need no new argument.  csrc
 step of progressive distillation (Salimans & Ho): the target is what the frozen `teacher` -- another ViewFusion, held
 outside the module tree -- reaches in two deterministic DDIM steps of its 2K-step chain, and the model learns to get
 there in one step of its own K-step chain.  csrc/diffusion.hip holds the definition; drivers.progressive_distill halves K.
+
+`set_self_cond(p)` (default None: every launch and every bit as before) shows the network -- built with three more input
+channels -- its own previous estimate of the clean image: in training the estimate of one extra no-grad forward, kept
+with probability p; in sampling the y0 the previous reverse step computed anyway.  csrc/diffusion.hip holds the definition.
 """
 import torch
 from torch import nn
@@ -80,6 +84,10 @@ class ViewFusion(nn.Module):
         object.__setattr__(self, "_distill", None)
         self._distill_gen = 0
         self.last_distill = None
+        # self-conditioning (set_self_cond): the probability p (None: off) and the last training forward's (keep, x^):
+        # plain attributes too
+        self._self_cond_p = None
+        self.last_self_cond = None
 
     # -- training objective -------------------------------------------------------------------
     def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
@@ -149,6 +157,9 @@ class ViewFusion(nn.Module):
         state_dict() / load_state_dict()) is a plain attribute: no parameter, no buffer.  Needs the noise schedule
         (set_new_noise_schedule) and, to run, a GPU model.  A Trainer drops its captured steps when this is called."""
         from . import ops
+        if kind is not None and self._self_cond_p is not None:
+            raise ValueError("a level sampler together with self-conditioning is not built (DESIGN 8): "
+                             "set_self_cond(None) first")
         self._level_gen += 1
         if kind is None:
             self._level_spec = self.level_sampler = None
@@ -216,6 +227,9 @@ class ViewFusion(nn.Module):
             raise ValueError("a thresholded or rescaled teacher is not built: the teacher's two steps use the static clamp")
         if not isinstance(teacher, ViewFusion) or teacher is self:
             raise ValueError("the teacher must be another ViewFusion model")
+        if self._self_cond_p is not None or teacher._self_cond_p is not None:
+            raise ValueError("distillation on or with a self-conditioned model is not built (DESIGN 8): "
+                             "set_self_cond(None) on the student and the teacher first")
         if getattr(self, "betas64", None) is None or getattr(teacher, "betas64", None) is None:
             raise ValueError("set_distill needs the noise schedule of both models: call set_new_noise_schedule first")
         import numpy as np
@@ -310,14 +324,138 @@ class ViewFusion(nn.Module):
         self.last_distill = (i, x_t)
         return dict(distill_z=z_t, distill_level=level, distill_eps=eps_t, distill_x0=x_t)
 
+    # -- self-conditioning --------------------------------------------------------------------
+    def set_self_cond(self, p=0.5):
+        """Self-conditioning (Chen et al., "Analog Bits", 2.2; csrc/diffusion.hip holds the definition).
+        set_self_cond(None), the default: off -- every launch and every bit as before.
+
+        The network -- UNet(in_channel = Cc + 6), Cc the conditioning views' channels -- is also shown an estimate of the
+        clean image, as three more input channels behind the noisy target; zeros mean "no estimate".
+        Training: forward() first runs the network once under no_grad, without Dropout and with zeros there, turns its
+        composed output into x^ = clamp(a y_t - b out, -1, 1) and keeps it per sample with probability p (seeded: word 3
+        of the call that gives the sample's t and u, ops.draw_self_cond; unseeded: torch.rand(B) < p after every other
+        draw); the ordinary step then sees x^ and takes the ordinary objective.  No gradient flows through the first
+        pass.  p = 0 runs no first pass; in eval mode every sample keeps its estimate and nothing is drawn.
+        forward(self_cond=x) injects the (already masked) estimate instead; self_cond_targets() is the first pass on its
+        own; `last_self_cond` = (keep uint8 (B,), x^) of the last one.
+        Sampling: generate() feeds back the y0 the previous step's tail wrote (zeros at the first step); p_sample /
+        p_mean_variance take self_cond= (None: zeros).
+        A plain attribute (`self_cond` reads it back): no buffer, no parameter -- save it as
+        save_checkpoint(..., self_cond=model.self_cond).  A Trainer drops its captured steps when it changes and runs the
+        first pass in front of every (micro-)step.  Refused with ValueError: together with set_distill (on
+        either model) or a level sampler and, when it runs, a CPU model or a network whose input is not Cc + 6 channels."""
+        if p is None:
+            self._self_cond_p = None
+            self.last_self_cond = None
+            return
+        p = float(p)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"the self-conditioning probability must be in [0, 1], got {p}")
+        if self._distill is not None:
+            raise ValueError("self-conditioning on a distillation student is not built (DESIGN 8): set_distill(None) first")
+        if self._level_spec is not None:
+            raise ValueError("self-conditioning together with a level sampler is not built (DESIGN 8): "
+                             "set_level_sampler(None) first")
+        self._self_cond_p = p
+
+    @property
+    def self_cond(self):
+        """The self-conditioning probability p of set_self_cond, None while it is off."""
+        return self._self_cond_p
+
+    def _check_self_cond(self, Cc, dev):
+        """ValueError, before any launch, where a self-conditioned pass cannot run: a CPU model, or a network whose stem
+        does not take [ cond (Cc) | noisy target (3) | estimate (3) ]."""
+        have = self._in_channels(self.denoise_fn)
+        if have is not None and have != Cc + 6:
+            raise ValueError(f"a self-conditioned model stacks {Cc} conditioning + 3 target + 3 estimate channels = "
+                             f"{Cc + 6}, the network takes in_channel = {have}")
+        if torch.device(dev).type != "cuda":
+            raise ValueError("self-conditioning runs on the GPU only (its stacking and its estimate are HIP kernels): move "
+                             "the model and the batch there")
+
+    def _history_buffer(self, y):
+        """The buffer the few-step tail writes the step's y0 into (dpmpp2m's history; a self-conditioned chain's estimate)."""
+        return torch.empty_like(y)
+
+    @torch.no_grad()
+    def self_cond_targets(self, y_cond, view_count, angle, y_0, noise=None, t=None, u=None, cond_drop=None, seed=None,
+                          sample_ids=None):
+        """The first pass of a self-conditioned training step (csrc/diffusion.hip), under no_grad: draws whatever is not
+        injected exactly as forward() would -- same order, same kernels -- then the coin, stacks the input with zero
+        estimate channels, runs the network on its inference path (no Dropout) and forms the masked estimate x^.
+        -> the dict forward() takes in place of running the phase itself: always `self_cond`; without seed= also the `t`,
+        `u`, `noise` (and `cond_drop`) it used, so that the step that follows uses the same ones (with seed= that step
+        draws them again from the same counters).  p = 0: no pass, `self_cond` is None (forward stacks zeros).
+        Sets `last_self_cond` = (keep uint8 (B,), x^)."""
+        from . import ops
+        from .unet import UNet
+        p = self._self_cond_p
+        if p is None:
+            raise ValueError("self_cond_targets needs set_self_cond(p)")
+        if self._distill is not None or self._level_spec is not None:
+            raise ValueError("self-conditioning with distillation or a level sampler is not built (DESIGN 8)")
+        b, dev = y_0.shape[0], y_0.device
+        self._check_self_cond(y_cond.shape[2], dev)
+        # forward()'s draws, in forward()'s order
+        drop_p = self._cond_drop_p if (cond_drop is None and self.training) else 0.0
+        drop, level, ids = cond_drop, None, sample_ids
+        if seed is not None:
+            ids = ops.sample_ids(dev, b, sample_ids)
+            if drop_p > 0:
+                drop = ops.draw_cond_drop(seed, ids, drop_p)
+            if t is None or u is None:
+                t_d, level_d, u_d = ops.draw_train(seed, ids, self.gammas, want_u=t is not None)
+                if t is None and u is None:
+                    t, level = t_d, level_d
+                elif t is None:
+                    t = t_d
+                else:
+                    u = u_d
+            if noise is None:
+                noise = ops.randn_ids(seed, ids, ops.diffusion.RNG_TRAIN_NOISE, 0, tuple(y_0.shape[1:]))
+        if t is None:
+            t = torch.randint(1, self.num_timesteps, (b,), device=dev).long()
+        if u is None and level is None:
+            u = torch.rand((b, 1), device=dev)
+        if noise is None:
+            noise = torch.randn_like(y_0)
+        if drop is None and drop_p > 0:
+            drop = torch.rand(b, device=dev) < drop_p
+        res = {} if seed is not None else dict(t=t, u=u, noise=noise)
+        if seed is None and drop is not None:
+            res["cond_drop"] = drop
+        # the coin: after every other draw; eval mode keeps every sample and draws nothing
+        if not self.training:
+            keep = None
+        elif seed is not None:
+            keep = ops.draw_self_cond(seed, ids, p) if p > 0 else None
+        else:
+            keep = (torch.rand(b, device=dev) < p).view(torch.uint8) if p > 0 else None
+        if self.training and p == 0:
+            self.last_self_cond = (torch.zeros(b, dtype=torch.uint8, device=dev), None)
+            res["self_cond"] = None
+            return res
+        if level is None:
+            level = ops.gather_level(self.gammas, t, u.reshape(-1).contiguous())
+        off, S, _ = ops.view_offsets(view_count, dev)
+        x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S,
+                                              drop=drop, sc_channels=True)
+        fn = self.denoise_fn
+        out = fn(x, angle_s, level_s, **({"no_dropout": True} if isinstance(fn, UNet) else {}))
+        x_hat = ops.self_cond_estimate(out, off, level, b, bool(self.weighting_train), self.prediction, x=x, keep=keep)
+        self.last_self_cond = (torch.ones(b, dtype=torch.uint8, device=dev) if keep is None else keep, x_hat)
+        res["self_cond"] = x_hat
+        return res
+
     def loss_key(self):
         """What a captured training step depends on besides its inputs: the objective, the attached histogram, the
-        conditioning-dropout probability, the level sampler (every set_level_sampler call counts), the prediction and the
-        distillation settings (every set_distill call counts)."""
+        conditioning-dropout probability, the level sampler (every set_level_sampler call counts), the prediction, the
+        distillation settings (every set_distill call counts) and the self-conditioning probability."""
         h = self.loss_hist
         return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
                 None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p,
-                self._level_gen, self.prediction, self._distill_gen)
+                self._level_gen, self.prediction, self._distill_gen, self._self_cond_p)
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -391,24 +529,37 @@ class ViewFusion(nn.Module):
         return sample_gammas.sqrt() * y_0 + (1 - sample_gammas).sqrt() * noise
 
     # -- reverse process ---------------------------------------------------------------------
-    def _denoise(self, y_t, y_cond, angle, t, off, S, x=None, copy_cond=True, levels=None, null_rows=False):
+    def _denoise(self, y_t, y_cond, angle, t, off, S, x=None, copy_cond=True, levels=None, null_rows=False, sc=None):
+        """sc (default None: the launches of before): the self-conditioning keywords of ops.stack_views."""
         from . import ops
         level = ops.gather_level(self.gammas if levels is None else levels, t)
         x, level_s, angle_s = ops.stack_views(y_cond, y_t, None, level, angle, off, S, x=x, copy_cond=copy_cond,
-                                              null_rows=null_rows)
+                                              null_rows=null_rows, **(sc or {}))
         return x, self.denoise_fn(x, angle_s, level_s)
 
+    def _sc_step(self, y_t, y_cond, self_cond):
+        """The stack_views keywords of one self-conditioned reverse step (None while the feature is off and no estimate
+        is handed over): checked before any launch."""
+        if self_cond is None and self._self_cond_p is None:
+            return None
+        self._check_self_cond(y_cond.shape[2], y_t.device)
+        if self_cond is not None and tuple(self_cond.shape) != tuple(y_t.shape):
+            raise ValueError(f"self_cond must have y_t's shape {tuple(y_t.shape)}, got {tuple(self_cond.shape)}")
+        return dict(self_cond=None if self_cond is None else self_cond.contiguous(), sc_channels=True)
+
     def p_mean_variance(self, y_t, y_cond, view_count, angle, t, clip_denoised: bool, guidance=None, threshold=None,
-                        threshold_max=None, guidance_rescale=None):
+                        threshold_max=None, guidance_rescale=None, self_cond=None):
         """guidance (a scale, or one per sample): the mean of the guided step; logits are the S conditional rows'.
-        threshold / threshold_max / guidance_rescale: as in generate()."""
+        threshold / threshold_max / guidance_rescale: as in generate().
+        self_cond (B,3,H,W; a self-conditioned model, set_self_cond): the estimate shown to the network; None is zeros."""
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
         self._check_samplable()
+        sc = self._sc_step(y_t, y_cond, self_cond)
         dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
-        _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None)
+        _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None, sc=sc)
         w_on = bool(self.weighting_inference)
         _, mean, weights = ops.p_sample_tail(out, off, y_t, None, t, self._sched(), y_t.shape[0], max_v, w_on,
                                              clip=clip_denoised, want_mean=True, guidance=gs, S=S, **dyn)
@@ -417,14 +568,16 @@ class ViewFusion(nn.Module):
 
     @torch.no_grad()
     def p_sample(self, y_t, y_cond, view_count, angle, t, clip_denoised=True, z=None, guidance=None, threshold=None,
-                 threshold_max=None, guidance_rescale=None):
+                 threshold_max=None, guidance_rescale=None, self_cond=None):
+        """self_cond (B,3,H,W; a self-conditioned model): the estimate shown to the network; None is zeros."""
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
         self._check_samplable()
+        sc = self._sc_step(y_t, y_cond, self_cond)
         dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
-        _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None)
+        _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None, sc=sc)
         if z is None:
             z = torch.randn_like(y_t) if bool((t > 0).any()) else None
         elif not bool((t > 0).any()):
@@ -470,12 +623,23 @@ class ViewFusion(nn.Module):
         conditional prediction's.  Either one turns the tail into three launches (composed eps, per-sample statistics,
         tail) that stay inside the captured step; their scratch buffers are made once per call.  Both combine with
         everything above.  No schedule of q / phi over the steps.
+
+        A self-conditioned model (set_self_cond; csrc/diffusion.hip): the estimate channels of every step's input are the
+        y0 the step before wrote into the few-step tail's history buffer -- clamped or thresholded, guided -- and zeros at
+        the first step; with dpmpp2m the tail's own history is that same buffer.  Only the table-driven tail hands y0 back,
+        so sample_steps=None runs as sample_steps=T, solver="ddim", eta=1.0: the ancestral chain through that tail (the
+        sampler tests pin the two to each other within the chain tolerance).  Everything above combines with it unchanged.
         """
         from . import ops
         q_on, _, phi = ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None)
         dyn = {}
         plan = tau = None
         self._check_samplable()
+        sc_on = self._self_cond_p is not None
+        if sc_on:                                         # only the table-driven tail hands y0 back
+            self._check_self_cond(y_cond.shape[2], y_cond.device)
+            if sample_steps is None:
+                sample_steps, solver, eta = self.num_timesteps, "ddim", 1.0
         if sample_steps is not None:                      # argument errors first: nothing has been launched yet
             _schedule.check_sampler(solver, eta)
             tau = _schedule.sample_timesteps(self.num_timesteps, sample_steps).tolist()
@@ -504,7 +668,10 @@ class ViewFusion(nn.Module):
         if tau is not None:
             plan = self._sampler_plan(tau, solver, eta, dev)
             levels = plan["level"]
-            hist = torch.empty_like(y) if plan["multistep"] else None      # y0 of the step before; never read first
+            # y0 of the step before; the multistep tail never reads it first ...
+            hist = self._history_buffer(y) if plan["multistep"] or sc_on else None
+            if sc_on:                                     # ... but the stacking reads it at the top of EVERY step: zeros
+                hist.zero_()                              # = "no estimate" before the first one
             if not any(plan["noisy"]):                    # eta = 0: no z anywhere -- no buffer, no draw
                 z_seed = z = None
         if q_on is not None or phi > 0.0:                 # the three-launch tail and what it keeps between its launches
@@ -513,10 +680,13 @@ class ViewFusion(nn.Module):
         y_cond = y_cond.contiguous()
         angle = angle.contiguous()
         # the conditioning half of the stacked input never changes: copy it once (guided: the null rows' zeros too)
-        x, _, _ = ops.stack_views(y_cond, y, None, ops.gather_level(levels, t), angle, off, S, null_rows=guided)
+        # (self-conditioned: the sibling kernel, whose third part is the history buffer the tail below writes)
+        sc = dict(self_cond=hist, sc_channels=True) if sc_on else {}
+        x, _, _ = ops.stack_views(y_cond, y, None, ops.gather_level(levels, t), angle, off, S, null_rows=guided, **sc)
 
         def step():
-            _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False, levels=levels, null_rows=guided)
+            _, out = self._denoise(y, y_cond, angle, t, off, S, x=x, copy_cond=False, levels=levels, null_rows=guided,
+                                   sc=sc)
             if plan is not None:
                 _, weights = ops.sampler_step(out, off, y, z, t, plan, b, max_v, w_on, y0_prev=hist, inplace=True,
                                               seed=z_seed, ids=ids, guidance=gs, S=S, **dyn)
@@ -538,6 +708,8 @@ class ViewFusion(nn.Module):
             with torch.cuda.graph(graph):
                 out, weights = step()
             y.copy_(y0)                                    # capture does not execute, but be explicit
+            if sc_on:                                      # the warm-up step wrote its y0 into the history buffer
+                hist.zero_()
 
         ret, logit_arr, weight_arr = [y_t], [], []
         for i in reversed(range(n_steps)):
@@ -571,7 +743,7 @@ class ViewFusion(nn.Module):
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
                 z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0,
                 guidance=None, cond_drop=None, threshold=None, threshold_max=None, guidance_rescale=None, distill_z=None,
-                distill_level=None, distill_eps=None, distill_x0=None):
+                distill_level=None, distill_eps=None, distill_x0=None, self_cond=None):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
             return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
                                  sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta,
@@ -585,6 +757,8 @@ class ViewFusion(nn.Module):
             # progressive distillation (set_distill): the teacher phase -- or its four outputs, injected -- then the
             # student's ordinary stacking of z_t at its level, the UNet and the ordinary objective on (eps~, x~)
             tgt = dict(distill_z=distill_z, distill_level=distill_level, distill_eps=distill_eps, distill_x0=distill_x0)
+            if self._self_cond_p is not None or self_cond is not None:
+                raise ValueError("a distillation step on a self-conditioned model is not built (DESIGN 8)")
             if distill_z is None:
                 if cond_drop is not None or u is not None:
                     raise ValueError("a distillation step takes no cond_drop= / u=: its level is gammas[tau_S[i]]")
@@ -598,6 +772,21 @@ class ViewFusion(nn.Module):
             x, level_s, angle_s = ops.stack_views(y_cond, tgt["distill_z"].contiguous(), None, level, angle, off, S)
             out = self.denoise_fn(x, angle_s, level_s, **self._drop_rng(seed, sample_ids, off, max_v, b, dev))
             return self._objective(out, tgt["distill_eps"], tgt["distill_x0"], level, off, b)
+        # self-conditioning (set_self_cond): an injected estimate wins and is used as is; else the first pass runs here
+        # and hands back the estimate and, unseeded, the draws it used -- the ordinary step below then draws nothing again
+        sc_on = self_cond is not None or self._self_cond_p is not None
+        if sc_on:
+            self._check_self_cond(y_cond.shape[2], dev)
+            if self._level_spec is not None:
+                raise ValueError("self-conditioning together with a level sampler is not built (DESIGN 8)")
+            if self_cond is None:
+                first = self.self_cond_targets(y_cond, view_count, angle, y_0, noise=noise, t=t, u=u, cond_drop=cond_drop,
+                                               seed=seed, sample_ids=sample_ids)
+                self_cond = first["self_cond"]
+                t, u, noise = first.get("t", t), first.get("u", u), first.get("noise", noise)
+                cond_drop = first.get("cond_drop", cond_drop)
+            elif tuple(self_cond.shape) != tuple(y_0.shape):
+                raise ValueError(f"self_cond must have y_0's shape {tuple(y_0.shape)}, got {tuple(self_cond.shape)}")
         # conditioning dropout (set_cond_dropout): an injected mask wins; else drawn in training mode when p > 0
         drop_p = self._cond_drop_p if (cond_drop is None and self.training) else 0.0
         drop = cond_drop
@@ -644,8 +833,9 @@ class ViewFusion(nn.Module):
         if drop is not None:
             drop = ops.diffusion._drop_mask(drop, b, dev)
         self.last_cond_drop = drop
+        sc = {} if not sc_on else dict(self_cond=None if self_cond is None else self_cond.contiguous(), sc_channels=True)
         x, level_s, angle_s = ops.stack_views(y_cond, y_0.contiguous(), noise.contiguous(), level, angle, off, S,
-                                              drop=drop)
+                                              drop=drop, **sc)
         out = self.denoise_fn(x, angle_s, level_s, **self._drop_rng(seed, ids, off, max_v, b, dev))
         return self._objective(out, noise, y_0, level, off, b, smp, iw, t)
 
