@@ -27,7 +27,7 @@ from .policy import (  # noqa: F401
     wino_kind
 )
 from .packing import (  # noqa: F401
-    _WINO_ABI, _conv_ws, _packed, _packed_small, _packed_wino, _wino_ws, pack_all
+    _WINO_ABI, _conv_ws, _pack_rows, _pack_sizes, _packed, _packed_small, _packed_wino, _wino_ws, pack_all
 )
 from .bf16x3 import (  # noqa: F401
     _packed_b3, _use_b3

@@ -89,6 +89,33 @@ def _packed_wino(layer, force, kind=1):
     return uf, ub
 
 
+_PACK_MULTI = ("vf_conv_pack_weights_multi", "vf_wino_pack_weights_multi", "vf_wino44_pack_weights_multi")
+
+
+def _pack_sizes(Cout, Cin, KS, kind):
+    """(forward, backward) floats of a layer's pack in the format of kernel `kind` (0 direct; wino_kind otherwise)."""
+    nf, nb = ctypes.c_long(), ctypes.c_long()
+    if kind:
+        _lib.call(_WINO_ABI[kind][1], Cout, Cin, ctypes.byref(nf), ctypes.byref(nb))
+    else:
+        _lib.call("vf_conv_pack_sizes", Cout, Cin, KS, ctypes.byref(nf), ctypes.byref(nb))
+    return nf.value, nb.value
+
+
+def _pack_rows(shapes, kinds, ptrs=None):
+    """The tables of pack_all's three launches (host only, launches nothing).  shapes: (Cout, Cin, KS) per layer, kinds:
+    its format (wino_kind), ptrs: its (weight, forward pack, backward pack) addresses (default: zeros).
+    -> (rows, totals), both indexed by kind: rows[0] = [w, fwd, bwd, Cout, Cin, KS, nf, nb, first_block], rows[1], rows[2] =
+    [w, fwd, bwd, Cout, Cin, nf, nb, first_block]; first_block and totals[k] in units of 256 outputs."""
+    rows, first = ([], [], []), [0, 0, 0]
+    for i, ((Cout, Cin, KS), kind) in enumerate(zip(shapes, kinds)):
+        w, pf, pb = ptrs[i] if ptrs is not None else (0, 0, 0)
+        nf, nb = _pack_sizes(Cout, Cin, KS, kind)
+        rows[kind].append([w, pf, pb, Cout, Cin] + ([] if kind else [KS]) + [nf, nb, first[kind]])
+        first[kind] += (nf + nb + 255) // 256
+    return rows, tuple(first)
+
+
 def pack_all(root, S=None, hw=None):
     """Training forward: re-pack the weights of EVERY conv layer under `root` with one launch per
     format (device-side descriptor tables, rebuilt only if a parameter moved or the geometry changed).
@@ -117,30 +144,22 @@ def pack_all(root, S=None, hw=None):
     key = (hw, kinds)
     if plan is None or plan[1] != key:
         dev = layers[0].weight.device
-        rows, first = {0: [], 1: [], 2: []}, {0: 0, 1: 0, 2: 0}
+        shapes, ptrs = [], []
         for l, (_, kind) in zip(layers, kinds):
             w = l.weight
             Cout, Cin, KS, _ = w.shape
-            nf, nb = ctypes.c_long(), ctypes.c_long()
-            if kind:
-                _lib.call(_WINO_ABI[kind][1], Cout, Cin, ctypes.byref(nf), ctypes.byref(nb))
-            else:
-                _lib.call("vf_conv_pack_sizes", Cout, Cin, KS, ctypes.byref(nf), ctypes.byref(nb))
-            pf = torch.empty(nf.value, device=dev, dtype=torch.float32)
-            pb = torch.empty(nb.value, device=dev, dtype=torch.float32)
-            nblk = (nf.value + nb.value + 255) // 256
-            if kind:
-                object.__setattr__(l, _WINO_ABI[kind][0], (None, pf, pb))
-                rows[kind].append([w.data_ptr(), pf.data_ptr(), pb.data_ptr(), Cout, Cin, nf.value, nb.value, first[kind]])
-            else:
-                object.__setattr__(l, "_vf_pack", (None, pf, pb))
-                rows[0].append([w.data_ptr(), pf.data_ptr(), pb.data_ptr(), Cout, Cin, KS, nf.value, nb.value, first[0]])
-            first[kind] += nblk
+            nf, nb = _pack_sizes(Cout, Cin, KS, kind)
+            pf = torch.empty(nf, device=dev, dtype=torch.float32)
+            pb = torch.empty(nb, device=dev, dtype=torch.float32)
+            object.__setattr__(l, _WINO_ABI[kind][0] if kind else "_vf_pack", (None, pf, pb))
+            shapes.append((Cout, Cin, KS))
+            ptrs.append((w.data_ptr(), pf.data_ptr(), pb.data_ptr()))
+        rows, first = _pack_rows(shapes, [kind for _, kind in kinds], ptrs)
         descs = tuple((torch.tensor(rows[k], dtype=torch.int64).to(dev) if rows[k] else None, len(rows[k]), first[k])
                       for k in (0, 1, 2))
         plan = (layers, key, descs)
         object.__setattr__(root, "_vf_pack_plan", plan)
-    for k, fn in ((0, "vf_conv_pack_weights_multi"), (1, "vf_wino_pack_weights_multi"), (2, "vf_wino44_pack_weights_multi")):
+    for k, fn in enumerate(_PACK_MULTI):
         desc, n, blk = plan[2][k]
         if n:
             _call(fn, ctypes.c_void_p(desc.data_ptr()), n, blk, _stream())
