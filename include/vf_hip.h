@@ -594,6 +594,50 @@ int vf_self_cond_estimate(const float* unet_out, const int* off, const float* le
 /* Host mirrors (HOST pointers, no stream): vf_draw_self_cond on the CPU, and the (a, b) of the estimate at levels [n] */
 int vf_self_cond_draw_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* out /*[B]*/, int B);
 int vf_self_cond_coeffs_host(const float* level, int pred, float* a /*[n]*/, float* b /*[n]*/, int n);
+/* ---- learned variance (csrc/diffusion.hip holds the definition, csrc/vlb.h the arithmetic): unet_out has nine channels,
+ *      0..2 the prediction, 3..5 the view logits, 6..8 the raw variance output.  Siblings of the entries above. ---- */
+/* The hybrid loss L_simple + lambda L_vlb: vf_compose_loss_pred_fwd / _bwd for pred 0 | 1 | 2 (0: noise is the ready-made
+ * target, y_0 not read) plus t (DEVICE int64 [B], clamped into [0, T - 1]), the fp32 tables c1 (posterior_mean_coef1), hi,
+ * lo [T], var_hat [B][3][HW] (the composed channels 6..8), vlb_part [B * 64], sample_vlb [B] (bits per dimension).  No
+ * per-sample scale.  The backward writes all nine channels of dout. */
+int vf_compose_loss_lv_fwd(const float* unet_out, const int* off, const float* noise /*|NULL for x0*/,
+                           const float* y_0 /*|NULL for eps*/, const float* level, const long long* t, const float* c1,
+                           const float* hi, const float* lo, float* noise_hat, float* var_hat, float* loss_part,
+                           float* vlb_part, float* sample_loss, float* sample_w, float* sample_vlb, float* loss,
+                           float* bin_sum /*|NULL*/, int* bin_cnt /*|NULL*/, int B, int Cout, int HW, int weighting,
+                           int penalty, float delta, int weight_kind, float a, float b, int K, int pred, int T,
+                           float lambda, void* stream);
+int vf_compose_loss_lv_bwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                           const float* level, const long long* t, const float* c1, const float* hi, const float* lo,
+                           const float* noise_hat, const float* var_hat, const float* gloss, const float* sample_w,
+                           float* dout, int B, int Cout, int HW, int weighting, int penalty, float delta, int pred, int T,
+                           float lambda, void* stream);
+/* The learned-variance reverse step: vf_sampler_step{, _rng, _cfg, _cfg_rng} on the "ddim", eta = 1 tables without c1,
+ * with hi, lo [K] behind sigma -- where sigma[k] != 0 the noise scale is expf(0.5 lp) per element, lp between lo[k] and
+ * hi[k] by the composed channels 6..8 of the conditional rows -- and lp_out ([B][3][HW] | NULL: lp itself). */
+int vf_sampler_step_lv(const float* unet_out, const int* off, const float* y_t, const float* z /*|NULL*/,
+                       const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                       const float* sigma, const float* hi, const float* lo, float* y0_prev /*|NULL*/, float* y_next,
+                       float* weights /*|NULL*/, float* lp_out /*|NULL*/, int B, int Cout, int HW, int maxV,
+                       int weighting, void* stream);
+int vf_sampler_step_lv_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                           const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                           const float* b, const float* cy, const float* c0, const float* sigma, const float* hi,
+                           const float* lo, float* y0_prev, float* y_next, float* weights, float* lp_out, int B, int Cout,
+                           int HW, int maxV, int weighting, void* stream);
+int vf_sampler_step_lv_cfg(const float* unet_out, const int* off, const float* y_t, const float* z,
+                           const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                           const float* sigma, const float* hi, const float* lo, float* y0_prev, float* y_next,
+                           float* weights, float* lp_out, int B, int Cout, int HW, int maxV, int weighting, const float* g,
+                           void* stream);
+int vf_sampler_step_lv_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                               const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                               const float* b, const float* cy, const float* c0, const float* sigma, const float* hi,
+                               const float* lo, float* y0_prev, float* y_next, float* weights, float* lp_out, int B,
+                               int Cout, int HW, int maxV, int weighting, const float* g, void* stream);
+/* Host mirror of csrc/vlb.h (HOST pointers, no stream): per element lp, KL in bits and dKL/dlp */
+int vf_vlb_terms_host(const float* o, const float* hi, const float* lo, const float* c1, const float* level,
+                      const float* r, int pred, float* lp, float* kl, float* dkl, int n);
 
 /* ---- batch assembly from a device-resident view store (csrc/batch.hip; data.ViewStore): the reference loader's
  *      process_sample + collate + H2D, data/nmr_dataset.py:10-52, as one launch.  store: planar uint8 [N][24][3][H][W],

@@ -183,6 +183,13 @@ SIGNATURES = {
     "vf_self_cond_estimate": [_P, _P, _P, _P, _L, _L, _I, _P, _P, _I, _I, _I, _I, _I, _P],
     "vf_self_cond_draw_host": [_U64, _P, ctypes.c_uint, _P, _I],
     "vf_self_cond_coeffs_host": [_P, _I, _P, _P, _I],
+    "vf_compose_loss_lv_fwd": [_P] * 19 + [_I, _I, _I, _I, _I, _F, _I, _F, _F, _I, _I, _I, _F, _P],
+    "vf_compose_loss_lv_bwd": [_P] * 14 + [_I, _I, _I, _I, _I, _F, _I, _I, _F, _P],
+    "vf_sampler_step_lv": [_P] * 16 + [_I, _I, _I, _I, _I, _P],
+    "vf_sampler_step_lv_rng": [_P, _P, _P, _U64] + [_P] * 14 + [_I, _I, _I, _I, _I, _P],
+    "vf_sampler_step_lv_cfg": [_P] * 16 + [_I, _I, _I, _I, _I, _P, _P],
+    "vf_sampler_step_lv_cfg_rng": [_P, _P, _P, _U64] + [_P] * 14 + [_I, _I, _I, _I, _I, _P, _P],
+    "vf_vlb_terms_host": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

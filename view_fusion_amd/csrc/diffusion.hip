@@ -46,6 +46,10 @@
 //                   x2, x~, eps~), siblings of draw_train / stack_views and of sampler_step_kernel.
 //   self-conditioning  stack_views_sc_kernel (stack_views_cfg_kernel plus the third part), self_cond_estimate_kernel<PRED>
 //                   (the first pass's clamped x0 estimate) and draw_self_cond_kernel: siblings, behind the distillation pair.
+//   learned variance  compose4_var, compose_loss_lv_fwd_kernel<PEN, PRED> -> compose_loss_lv_finish_kernel,
+//                   compose_loss_lv_bwd_kernel<PEN, PRED> (the hybrid loss: the family plus three variance channels and a KL
+//                   term taken in registers) and sampler_step_lv_kernel<CFG, RNG> (the few-step tail with a per-pixel noise
+//                   scale): siblings, behind the self-conditioning kernels; vlb.h holds the arithmetic.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
 //                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The five
@@ -170,10 +174,43 @@
 //   Sampling.  sc = the history buffer sampler_step_kernel writes (y0_prev: the step's final y0 -- clamped or thresholded,
 //     guided), zero before the first step; the stacking kernel reads it at the top of a step, the tail overwrites it at the
 //     end.  With dpmpp2m the tail reads the same buffer as its own history: both want the previous step's y0.
+//
+// Learned variance (Nichol & Dhariwal, "Improved DDPM", 3.1 and 4): the network also predicts, per pixel, where between
+// log beta~ and log beta the log-variance of a reverse step lies, and is trained with L_simple + lambda L_vlb.  This
+// comment is the ONE written definition (the arithmetic, operation by operation: vlb.h); tests/vlb_ref.py restates it.
+// Opt-in: sibling kernels (compose_loss_lv_fwd / _finish / _bwd, sampler_step_lv_kernel<CFG, RNG>), everything above is
+// untouched.
+//   Network.  UNet(out_channel = 9): channels 0..2 the prediction (eps, v or x0) and 3..5 the view logits as before, 6..8
+//     the raw variance output o.  o_b = the composition over the sample's real views of channels 6..8 under the weights of
+//     channels 0..2 (the softmax of 3..5, or the mean).  v = 0.5 o_b + 0.5, unconstrained;  lp = v hi + (1 - v) lo, every
+//     operation rounded in this order, no fused multiply-add.
+//   Tables (schedule.variance_tables, float64, rounded to fp32 once).  For a chain tau (default 0..T-1), gt = gammas[tau[k]],
+//     gp = gammas[tau[k-1]] (1 at k = 0):  hi[k] = log(1 - gt/gp),  lo[k] = log(max((1 - gt/gp)(1 - gp)/(1 - gt), 1e-20));
+//     on the full schedule hi = log(betas) and lo = posterior_log_variance_clipped, value for value.
+//   Training term.  Sample b: timestep t in 1..T-1, continuous level g, r = the native residual the loss family forms
+//     (composed prediction - pred_target4), a CONSTANT inside the vlb term: it carries no gradient there.
+//       m^2 = c1[t]^2 kappa^2(g) r^2, c1 = posterior_mean_coef1; kappa^2 = (1 - g)/g (eps) | 1 - g (v) | 1 (x0): the squared
+//             distance of the posterior means, (mu~ - mu_theta)^2, with y0_hat = a(g) y_t - b(g) out unclamped;
+//       KL  = 0.5 (-1 + lp - lo[t] + exp(lo[t] - lp) + m^2 exp(-lp)) / ln 2;
+//       vlb_b = the mean of KL over the sample's 3 H W elements, in bits per dimension;
+//       loss = L_simple + lambda (1/B) sum_b vlb_b.
+//     L_simple is the loss family's objective, unchanged: penalties, the noise-level weight, the per-sample loss and the
+//     histogram, all on r.  The vlb term takes no SNR weight.  t is never 0 in training (draw_train gives 1..T-1), so the
+//     discretised decoder likelihood of t = 0 is not needed and not built.
+//   Gradient.  dloss/dlp = (lambda / (n B)) 0.5 (1 - exp(lo - lp) - m^2 exp(-lp)) / ln 2;  dlp/do_b = 0.5 (hi - lo);
+//     channels 6..8 get w_v g, the logits 3..5 get w_v (o_v - o_b) g ADDED to L_simple's logit gradient, channels 0..2 get
+//     L_simple's gradient only; mean ablation: channels 6..8 get g / count, the logits 0.
+//   Sampling step (the table-driven tail on the "ddim", eta = 1 tables, whose mean is the posterior mean):
+//     y0 = clamp(a[k] y - b[k] out, -1, 1);  r = cy[k] y + c0[k] y0, both rounded as sampler_step_kernel<CFG, false, RNG>
+//     rounds them;  where sigma[k] != 0 (every step but k = 0): r += expf(0.5f lp) z with lp from hi[k], lo[k] and o_b;
+//     y0_prev <- y0 when a history buffer is passed.  Weights, logits and the draw of z (step = tau[k]) are that kernel's.
+//     Guided: `out` is guided as before; o_b comes from the CONDITIONAL rows only, the null row's channels 6..8 are
+//     ignored (GLIDE).  No EPS / threshold / rescale flavour.
 #include "common.h"
 #include "level_sampler.h"
 #include "loss_weight.h"
 #include "rng.h"
+#include "vlb.h"
 
 namespace {
 
@@ -1483,6 +1520,299 @@ __global__ __launch_bounds__(256) void self_cond_estimate_kernel(
     }
 }
 
+// ---- learned variance (the head of this file holds the definition, vlb.h the arithmetic) ----
+// o_b of one float4 (c, p): channel 6 + c composed under the weights of channel c -- the softmax of channel 3 + c with
+// the (mx, inv) compose4 handed back, or the mean.
+__device__ __forceinline__ float4 compose4_var(const float* __restrict__ out, int Cout, int HW, int v0, int v1, int c,
+                                               int p, int weighting, const float4& mx, const float4& inv) {
+    const size_t vs = (size_t)Cout * HW;
+    const float* l0 = out + (size_t)v0 * vs + (size_t)(3 + c) * HW + p;
+    const float* o0 = l0 + (size_t)3 * HW;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!weighting) {
+        for (int v = v0; v < v1; ++v) {
+            const float4 o = *reinterpret_cast<const float4*>(o0 + (size_t)(v - v0) * vs);
+            acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
+        }
+        const float n = 1.0f / (float)(v1 - v0);
+        return make_float4(acc.x * n, acc.y * n, acc.z * n, acc.w * n);
+    }
+    for (int v = v0; v < v1; ++v) {
+        const float4 l = *reinterpret_cast<const float4*>(l0 + (size_t)(v - v0) * vs);
+        const float4 o = *reinterpret_cast<const float4*>(o0 + (size_t)(v - v0) * vs);
+        acc.x += expf(l.x - mx.x) * o.x; acc.y += expf(l.y - mx.y) * o.y;
+        acc.z += expf(l.z - mx.z) * o.z; acc.w += expf(l.w - mx.w) * o.w;
+    }
+    return make_float4(acc.x * inv.x, acc.y * inv.y, acc.z * inv.z, acc.w * inv.w);
+}
+
+// What a workgroup of the hybrid loss knows about its sample: the tables at t[b] (clamped into [0, T - 1] before any
+// table is read) and kappa^2 of its level.
+struct VlbSample {
+    float c1, hi, lo, k2;
+};
+template <int PRED>
+__device__ __forceinline__ VlbSample vlb_sample(const long long* __restrict__ t, const float* __restrict__ tc1,
+                                                const float* __restrict__ thi, const float* __restrict__ tlo, int T,
+                                                float g) {
+    long long tb = t[blockIdx.y];
+    tb = tb < 0 ? 0 : (tb > T - 1 ? T - 1 : tb);
+    return VlbSample{tc1[tb], thi[tb], tlo[tb], vf_vlb_kappa2(PRED, g)};
+}
+
+// compose_loss_fwd_kernel plus the variance channels: the same composition, residual and (b, chunk) partial sums of
+// rho(r), and next to them the partial sums of KL(r, o_b) in bits.  noise_hat and var_hat receive the composed prediction
+// and the composed o_b (what the backward kernel reads back).
+template <int PEN, int PRED>
+__global__ __launch_bounds__(256) void compose_loss_lv_fwd_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ noise,
+    const float* __restrict__ y_0, const float* __restrict__ level, const long long* __restrict__ t,
+    const float* __restrict__ tc1, const float* __restrict__ thi, const float* __restrict__ tlo,
+    float* __restrict__ noise_hat, float* __restrict__ var_hat, float* __restrict__ loss_part,
+    float* __restrict__ vlb_part, int Cout, int HW, int weighting, float delta, int T) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const float g = level[b];
+    float sa = 0.f, sb = 0.f;
+    if (PRED != VF_PRED_EPS) sa = sqrtf(g), sb = sqrtf(1.0f - g);
+    const VlbSample s = vlb_sample<PRED>(t, tc1, thi, tlo, T, g);
+    float acc = 0.f, kl = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        float4 mx = make_float4(0.f, 0.f, 0.f, 0.f), inv = mx;
+        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
+        const float4 ob = compose4_var(out, Cout, HW, v0, v1, c, p, weighting, mx, inv);
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        *reinterpret_cast<float4*>(noise_hat + o) = nh;
+        *reinterpret_cast<float4*>(var_hat + o) = ob;
+        const float4 tg = pred_target4<PRED>(noise, y_0, o, sa, sb);
+        const float r[4] = {nh.x - tg.x, nh.y - tg.y, nh.z - tg.z, nh.w - tg.w};
+        const float os[4] = {ob.x, ob.y, ob.z, ob.w};
+        acc += (vf_loss_rho<PEN>(r[0], delta) + vf_loss_rho<PEN>(r[1], delta)) +
+               (vf_loss_rho<PEN>(r[2], delta) + vf_loss_rho<PEN>(r[3], delta));
+        float k[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            k[j] = vf_vlb_kl(vf_vlb_logvar(os[j], s.hi, s.lo), s.lo, vf_vlb_m2(s.c1, s.k2, r[j]));
+        kl += (k[0] + k[1]) + (k[2] + k[3]);
+    }
+    acc = block_sum<256>(acc, red);
+    kl = block_sum<256>(kl, red);
+    if (threadIdx.x == 0) {
+        loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+        vlb_part[blockIdx.y * gridDim.x + blockIdx.x] = kl;
+    }
+}
+
+// compose_loss_finish_kernel with the vlb term and without a per-sample scale (a level sampler is refused with a
+// learned variance): sample_vlb[s] = its `ch` partials in index order / n; loss = sum_s sample_w[s] sample_loss[s] / B +
+// lambda sum_s sample_vlb[s] / B, each sum in index order by one thread.  The histogram is the family's: L_simple alone.
+__global__ __launch_bounds__(64) void compose_loss_lv_finish_kernel(
+    const float* __restrict__ part, const float* __restrict__ vlb_part, const float* __restrict__ level,
+    float* __restrict__ sample_loss, float* __restrict__ sample_w, float* __restrict__ sample_vlb,
+    float* __restrict__ loss, float* __restrict__ bin_sum, int* __restrict__ bin_cnt, int B, int ch, int K, float inv_n,
+    int kind, float a, float b, int pred, float lambda) {
+    for (int s = threadIdx.x; s < B; s += 64) {
+        float acc = 0.f, kl = 0.f;
+        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
+        for (int c = 0; c < ch; ++c) kl += vlb_part[s * ch + c];
+        sample_loss[s] = acc * inv_n;
+        sample_vlb[s] = kl * inv_n;
+        sample_w[s] = vf_loss_weight_pred(pred, kind, a, b, level[s]);
+    }
+    __syncthreads();                        // (also makes the workgroup's global stores above visible to it)
+    if (threadIdx.x == 0) {
+        float acc = 0.f, kl = 0.f;
+        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
+        for (int s = 0; s < B; ++s) kl += sample_vlb[s];
+        *loss = acc / (float)B + lambda * (kl / (float)B);
+    }
+    if (bin_sum == nullptr) return;
+    for (int k = threadIdx.x; k < K; k += 64) {
+        float sum = 0.f;
+        int cnt = 0;
+        for (int s = 0; s < B; ++s) {
+            int bin = (int)(level[s] * (float)K);
+            bin = bin > K - 1 ? K - 1 : bin;
+            if (bin == k) {
+                sum += sample_loss[s];
+                ++cnt;
+            }
+        }
+        bin_sum[k] += sum;
+        bin_cnt[k] += cnt;
+    }
+}
+
+// compose_loss_bwd_kernel into nine channels.  g: L_simple's gradient on the composed prediction, the family's expression;
+// gv = gloss lambda / (n B) dKL/dlp 0.5 (hi - lo): the vlb term's gradient on o_b, with the residual a constant.  Then
+//   channels 0..2  w_v g                                     (mean: g / count)
+//   channels 3..5  w_v (e_v - nh) g + w_v (o_v - o_b) gv     (mean: 0)
+//   channels 6..8  w_v gv                                    (mean: gv / count)
+// every address of dout's nine channels written exactly once.
+template <int PEN, int PRED>
+__global__ __launch_bounds__(256) void compose_loss_lv_bwd_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ noise,
+    const float* __restrict__ y_0, const float* __restrict__ level, const long long* __restrict__ t,
+    const float* __restrict__ tc1, const float* __restrict__ thi, const float* __restrict__ tlo,
+    const float* __restrict__ noise_hat, const float* __restrict__ var_hat, const float* __restrict__ gloss,
+    const float* __restrict__ sample_w, float* __restrict__ dout, int Cout, int HW, int weighting, float inv_nb,
+    float delta, int T, float lambda) {
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const float gs = gloss[0] * sample_w[b] * inv_nb;
+    const float lv = level[b];
+    float sa = 0.f, sb = 0.f;
+    if (PRED != VF_PRED_EPS) sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    const VlbSample s = vlb_sample<PRED>(t, tc1, thi, tlo, T, lv);
+    const float gvs = gloss[0] * lambda * inv_nb * (0.5f * (s.hi - s.lo));
+    const size_t vs = (size_t)Cout * HW;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
+        const float4 ob = *reinterpret_cast<const float4*>(var_hat + o);
+        const float4 tg = pred_target4<PRED>(noise, y_0, o, sa, sb);
+        const float r[4] = {nh.x - tg.x, nh.y - tg.y, nh.z - tg.z, nh.w - tg.w};
+        const float os[4] = {ob.x, ob.y, ob.z, ob.w};
+        const float4 g = make_float4(gs * vf_loss_drho<PEN>(r[0], delta), gs * vf_loss_drho<PEN>(r[1], delta),
+                                     gs * vf_loss_drho<PEN>(r[2], delta), gs * vf_loss_drho<PEN>(r[3], delta));
+        float gk[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            gk[j] = gvs * vf_vlb_dkl(vf_vlb_logvar(os[j], s.hi, s.lo), s.lo, vf_vlb_m2(s.c1, s.k2, r[j]));
+        const float4 gv = make_float4(gk[0], gk[1], gk[2], gk[3]);
+        if (!weighting) {
+            const float inv = 1.0f / (float)(v1 - v0);
+            const float4 d = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
+            const float4 dv = make_float4(gv.x * inv, gv.y * inv, gv.z * inv, gv.w * inv);
+            for (int v = v0; v < v1; ++v) {
+                float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
+                *reinterpret_cast<float4*>(dp) = d;
+                *reinterpret_cast<float4*>(dp + (size_t)3 * HW) = make_float4(0.f, 0.f, 0.f, 0.f);
+                *reinterpret_cast<float4*>(dp + (size_t)6 * HW) = dv;
+            }
+            continue;
+        }
+        float4 mx, inv;
+        (void)compose4(out, Cout, HW, v0, v1, c, p, 1, &mx, &inv);
+        for (int v = v0; v < v1; ++v) {
+            const float* ep = out + (size_t)v * vs + (size_t)c * HW + p;
+            const float4 e = *reinterpret_cast<const float4*>(ep);
+            const float4 l = *reinterpret_cast<const float4*>(ep + (size_t)3 * HW);
+            const float4 q = *reinterpret_cast<const float4*>(ep + (size_t)6 * HW);
+            const float4 w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
+                                         expf(l.w - mx.w) * inv.w);
+            float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
+            *reinterpret_cast<float4*>(dp) = make_float4(w.x * g.x, w.y * g.y, w.z * g.z, w.w * g.w);
+            *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
+                make_float4(w.x * (e.x - nh.x) * g.x + w.x * (q.x - ob.x) * gv.x,
+                            w.y * (e.y - nh.y) * g.y + w.y * (q.y - ob.y) * gv.y,
+                            w.z * (e.z - nh.z) * g.z + w.z * (q.z - ob.z) * gv.z,
+                            w.w * (e.w - nh.w) * g.w + w.w * (q.w - ob.w) * gv.w);
+            *reinterpret_cast<float4*>(dp + (size_t)6 * HW) = make_float4(w.x * gv.x, w.y * gv.y, w.z * gv.z, w.w * gv.w);
+        }
+    }
+}
+
+// sampler_step_kernel<CFG, false, RNG> on the "ddim", eta = 1 tables with a per-pixel noise scale: y0 and cy y + c0 y0
+// rounded as that kernel rounds them (y0_hat_as<false>, the guided combination and multistep_base as its instruction
+// stream has them), then, where sigma[k] != 0, r = fma(expf(0.5 lp), z, r) with lp from hi[k], lo[k] and o_b -- the
+// composition of the CONDITIONAL rows' channels 6..8 (the null row's are not read).  No history term: the tables' c1 is 0.
+// lp_out (nullable): lp of every element, whatever sigma[k] is (p_mean_variance).
+template <bool CFG, bool RNG>
+__global__ __launch_bounds__(256) void sampler_step_lv_kernel(
+    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ y_t,
+    const float* __restrict__ z, unsigned long long seed, const long long* __restrict__ ids,
+    const long long* __restrict__ kidx, const long long* __restrict__ tau, const float* __restrict__ ta,
+    const float* __restrict__ tb, const float* __restrict__ tcy, const float* __restrict__ tc0,
+    const float* __restrict__ tsigma, const float* __restrict__ thi, const float* __restrict__ tlo, float* y0_prev,
+    float* __restrict__ y_next, float* __restrict__ weights, float* __restrict__ lp_out, int Cout, int HW, int maxV,
+    int weighting, const float* __restrict__ gscale) {
+    const int b = blockIdx.y;
+    const EpsBuffer src{};
+    const TailSample s = tail_sample<CFG, false>(out, off, gscale, src, Cout, HW);
+    const int n4 = 3 * HW / 4;
+    const long long k = kidx[b];
+    const auto noise = tail_noise<RNG, false>(z, seed, ids, RNG ? (uint32_t)tau[k] : 0u);
+    const float a_k = ta[k], b_k = tb[k], cy = tcy[k], c0 = tc0[k], hi = thi[k], lo = tlo[k];
+    const bool noisy = tsigma[k] != 0.0f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        float4 mx = make_float4(0.f, 0.f, 0.f, 0.f), inv = mx;
+        float4 eps = compose4(out, Cout, HW, s.v0, s.v1, c, p, weighting, &mx, &inv);
+        const float4 ob = compose4_var(out, Cout, HW, s.v0, s.v1, c, p, weighting, mx, inv);
+        if constexpr (CFG) {
+            const float4 u = *reinterpret_cast<const float4*>(s.eu + (size_t)c * HW + p);
+            eps = make_float4(__builtin_fmaf(s.gm, u.x, mul_rn(s.g, eps.x)), __builtin_fmaf(s.gm, u.y, mul_rn(s.g, eps.y)),
+                              __builtin_fmaf(s.gm, u.z, mul_rn(s.g, eps.z)), __builtin_fmaf(s.gm, u.w, mul_rn(s.g, eps.w)));
+        }
+        const float4 y = *reinterpret_cast<const float4*>(y_t + o);
+        const float ys[4] = {y.x, y.y, y.z, y.w};
+        const float es[4] = {eps.x, eps.y, eps.z, eps.w};
+        const float os[4] = {ob.x, ob.y, ob.z, ob.w};
+        float y0[4], r[4], lp[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            y0[j] = fminf(fmaxf(y0_hat_as<false>(a_k, ys[j], b_k, es[j]), -1.0f), 1.0f);
+            r[j] = multistep_base<true>(cy, ys[j], c0, y0[j], j);
+            lp[j] = vf_vlb_logvar(os[j], hi, lo);
+        }
+        if (noisy) {
+            const float4 zz = noise(i, o);
+            const float zs[4] = {zz.x, zz.y, zz.z, zz.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) r[j] = __builtin_fmaf(expf(mul_rn(0.5f, lp[j])), zs[j], r[j]);
+        }
+        if (y0_prev) *reinterpret_cast<float4*>(y0_prev + o) = make_float4(y0[0], y0[1], y0[2], y0[3]);
+        *reinterpret_cast<float4*>(y_next + o) = make_float4(r[0], r[1], r[2], r[3]);
+        if (lp_out) *reinterpret_cast<float4*>(lp_out + o) = make_float4(lp[0], lp[1], lp[2], lp[3]);
+        if (weights && weighting) write_weights(out, weights, Cout, HW, maxV, s.v0, s.v1, c, p, i, mx, inv);
+    }
+}
+
+// the run-time (penalty, pred) -> the hybrid loss's kernel pair, as loss_kernels below
+struct LossLvKernels {
+    decltype(&compose_loss_lv_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) fwd;
+    decltype(&compose_loss_lv_bwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) bwd;
+};
+
+template <int PRED>
+LossLvKernels loss_lv_kernels_of(int penalty) {
+    if (penalty == VF_LOSS_L1)
+        return {compose_loss_lv_fwd_kernel<VF_LOSS_L1, PRED>, compose_loss_lv_bwd_kernel<VF_LOSS_L1, PRED>};
+    if (penalty == VF_LOSS_HUBER)
+        return {compose_loss_lv_fwd_kernel<VF_LOSS_HUBER, PRED>, compose_loss_lv_bwd_kernel<VF_LOSS_HUBER, PRED>};
+    return {compose_loss_lv_fwd_kernel<VF_LOSS_MSE, PRED>, compose_loss_lv_bwd_kernel<VF_LOSS_MSE, PRED>};
+}
+
+LossLvKernels loss_lv_kernels(int penalty, int pred) {
+    if (pred == VF_PRED_V) return loss_lv_kernels_of<VF_PRED_V>(penalty);
+    if (pred == VF_PRED_X0) return loss_lv_kernels_of<VF_PRED_X0>(penalty);
+    return loss_lv_kernels_of<VF_PRED_EPS>(penalty);
+}
+
+// the one launcher of the learned-variance tail behind its four entry points; it holds the argument check
+template <bool CFG, bool RNG>
+int sampler_step_lv(const float* unet_out, const int* off, const float* y_t, const float* z, unsigned long long seed,
+                    const long long* ids, const long long* kidx, const long long* tau, const float* a, const float* b,
+                    const float* cy, const float* c0, const float* sigma, const float* hi, const float* lo,
+                    float* y0_prev, float* y_next, float* weights, float* lp_out, int B, int Cout, int HW, int maxV,
+                    int weighting, const float* g, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || HW <= 0 || Cout < 9 || (CFG && !g) || (RNG && (!ids || !tau))) return (int)hipErrorInvalidValue;
+    if (!unet_out || !off || !y_t || !kidx || !a || !b || !cy || !c0 || !sigma || !hi || !lo || !y_next)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL((sampler_step_lv_kernel<CFG, RNG>), dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, y_t, z, seed, ids, kidx, tau, a, b, cy, c0, sigma, hi, lo,
+                       y0_prev, y_next, weights, lp_out, Cout, HW, maxV, weighting, g);
+    VF_RETURN_LAST_ERROR();
+}
+
 // ---- the loss family: the run-time (penalty, pred) -> the kernel pair (the launchers stand with the entry points) ----
 struct LossKernels {
     decltype(&compose_loss_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) fwd;
@@ -2120,6 +2450,107 @@ int vf_self_cond_draw_host(unsigned long long seed, const long long* ids, unsign
 int vf_self_cond_coeffs_host(const float* level, int pred, float* a, float* b, int n) {
     if (n < 0 || pred < VF_PRED_EPS || pred > VF_PRED_X0) return (int)hipErrorInvalidValue;
     for (int i = 0; i < n; ++i) vf_self_cond_coeffs(pred, level[i], &a[i], &b[i]);
+    return 0;
+}
+
+// ---- learned variance (the head of this file; vlb.h) ----
+// The hybrid loss: vf_compose_loss_pred_fwd / _bwd for every pred (0 eps: `noise` is the ready-made target and y_0 is not
+// read) on a nine-channel unet_out, plus t (DEVICE int64 [B]), the fp32 tables c1, hi, lo [T] and lambda.  var_hat
+// [B][3][HW] and vlb_part [B * 64] next to noise_hat and loss_part; sample_vlb [B].  No per-sample scale.  Two launches
+// forward, one backward.  Refused: what the family refuses, Cout < 9, pred outside 0..2, T < 1, a null pointer among
+// those read.
+int vf_compose_loss_lv_fwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                           const float* level, const long long* t, const float* c1, const float* hi, const float* lo,
+                           float* noise_hat, float* var_hat, float* loss_part, float* vlb_part, float* sample_loss,
+                           float* sample_w, float* sample_vlb, float* loss, float* bin_sum, int* bin_cnt, int B, int Cout,
+                           int HW, int weighting, int penalty, float delta, int weight_kind, float a, float b, int K,
+                           int pred, int T, float lambda, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(Cout, HW, weighting, penalty, delta) || Cout < 9 || T < 1 || HW <= 0)
+        return (int)hipErrorInvalidValue;
+    if (pred < VF_PRED_EPS || pred > VF_PRED_X0 || !noise && pred != VF_PRED_X0 || !y_0 && pred != VF_PRED_EPS)
+        return (int)hipErrorInvalidValue;
+    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
+    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
+    if (!unet_out || !off || !level || !t || !c1 || !hi || !lo || !noise_hat || !var_hat || !loss_part || !vlb_part ||
+        !sample_loss || !sample_w || !sample_vlb || !loss)
+        return (int)hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    const int ch = chunks_for(3 * HW / 4);
+    hipLaunchKernelGGL(loss_lv_kernels(penalty, pred).fwd, dim3(ch, B), dim3(256), 0, st, unet_out, off, noise, y_0, level,
+                       t, c1, hi, lo, noise_hat, var_hat, loss_part, vlb_part, Cout, HW, weighting, delta, T);
+    hipLaunchKernelGGL(compose_loss_lv_finish_kernel, dim3(1), dim3(64), 0, st, loss_part, vlb_part, level, sample_loss,
+                       sample_w, sample_vlb, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b,
+                       pred, lambda);
+    VF_RETURN_LAST_ERROR();
+}
+
+int vf_compose_loss_lv_bwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
+                           const float* level, const long long* t, const float* c1, const float* hi, const float* lo,
+                           const float* noise_hat, const float* var_hat, const float* gloss, const float* sample_w,
+                           float* dout, int B, int Cout, int HW, int weighting, int penalty, float delta, int pred, int T,
+                           float lambda, void* stream) {
+    if (B <= 0) return 0;
+    if (!loss_args_ok(Cout, HW, weighting, penalty, delta) || Cout < 9 || T < 1 || HW <= 0)
+        return (int)hipErrorInvalidValue;
+    if (pred < VF_PRED_EPS || pred > VF_PRED_X0 || !noise && pred != VF_PRED_X0 || !y_0 && pred != VF_PRED_EPS)
+        return (int)hipErrorInvalidValue;
+    if (!unet_out || !off || !level || !t || !c1 || !hi || !lo || !noise_hat || !var_hat || !gloss || !sample_w || !dout)
+        return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(loss_lv_kernels(penalty, pred).bwd, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+                       (hipStream_t)stream, unet_out, off, noise, y_0, level, t, c1, hi, lo, noise_hat, var_hat, gloss,
+                       sample_w, dout, Cout, HW, weighting, 1.0f / ((float)B * 3.0f * (float)HW), delta, T, lambda);
+    VF_RETURN_LAST_ERROR();
+}
+
+// The learned-variance tail: vf_sampler_step{, _rng, _cfg, _cfg_rng} without c1 and with the tables hi, lo [K] behind
+// sigma and lp_out ([B][3][HW] | NULL) behind weights.  unet_out has nine channels.
+int vf_sampler_step_lv(const float* unet_out, const int* off, const float* y_t, const float* z, const long long* kidx,
+                       const float* a, const float* b, const float* cy, const float* c0, const float* sigma,
+                       const float* hi, const float* lo, float* y0_prev, float* y_next, float* weights, float* lp_out,
+                       int B, int Cout, int HW, int maxV, int weighting, void* stream) {
+    return sampler_step_lv<false, false>(unet_out, off, y_t, z, 0, nullptr, kidx, nullptr, a, b, cy, c0, sigma, hi, lo,
+                                         y0_prev, y_next, weights, lp_out, B, Cout, HW, maxV, weighting, nullptr, stream);
+}
+
+int vf_sampler_step_lv_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                           const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                           const float* b, const float* cy, const float* c0, const float* sigma, const float* hi,
+                           const float* lo, float* y0_prev, float* y_next, float* weights, float* lp_out, int B, int Cout,
+                           int HW, int maxV, int weighting, void* stream) {
+    return sampler_step_lv<false, true>(unet_out, off, y_t, nullptr, seed, ids, kidx, tau, a, b, cy, c0, sigma, hi, lo,
+                                        y0_prev, y_next, weights, lp_out, B, Cout, HW, maxV, weighting, nullptr, stream);
+}
+
+int vf_sampler_step_lv_cfg(const float* unet_out, const int* off, const float* y_t, const float* z,
+                           const long long* kidx, const float* a, const float* b, const float* cy, const float* c0,
+                           const float* sigma, const float* hi, const float* lo, float* y0_prev, float* y_next,
+                           float* weights, float* lp_out, int B, int Cout, int HW, int maxV, int weighting, const float* g,
+                           void* stream) {
+    return sampler_step_lv<true, false>(unet_out, off, y_t, z, 0, nullptr, kidx, nullptr, a, b, cy, c0, sigma, hi, lo,
+                                        y0_prev, y_next, weights, lp_out, B, Cout, HW, maxV, weighting, g, stream);
+}
+
+int vf_sampler_step_lv_cfg_rng(const float* unet_out, const int* off, const float* y_t, unsigned long long seed,
+                               const long long* ids, const long long* kidx, const long long* tau, const float* a,
+                               const float* b, const float* cy, const float* c0, const float* sigma, const float* hi,
+                               const float* lo, float* y0_prev, float* y_next, float* weights, float* lp_out, int B,
+                               int Cout, int HW, int maxV, int weighting, const float* g, void* stream) {
+    return sampler_step_lv<true, true>(unet_out, off, y_t, nullptr, seed, ids, kidx, tau, a, b, cy, c0, sigma, hi, lo,
+                                       y0_prev, y_next, weights, lp_out, B, Cout, HW, maxV, weighting, g, stream);
+}
+
+// Host mirror of vlb.h (HOST pointers, no stream): per element i of n, lp = the log-variance of o[i] between hi[i] and
+// lo[i], kl and dkl = KL in bits and dKL/dlp at m^2 = c1[i]^2 kappa^2(level[i]) r[i]^2 for pred 0 | 1 | 2.
+int vf_vlb_terms_host(const float* o, const float* hi, const float* lo, const float* c1, const float* level,
+                      const float* r, int pred, float* lp, float* kl, float* dkl, int n) {
+    if (n < 0 || pred < VF_PRED_EPS || pred > VF_PRED_X0) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i) {
+        const float m2 = vf_vlb_m2(c1[i], vf_vlb_kappa2(pred, level[i]), r[i]);
+        lp[i] = vf_vlb_logvar(o[i], hi[i], lo[i]);
+        kl[i] = vf_vlb_kl(lp[i], lo[i], m2);
+        dkl[i] = vf_vlb_dkl(lp[i], lo[i], m2);
+    }
     return 0;
 }
 

@@ -131,7 +131,8 @@ def save_checkpoint(path, model, optimizer, **extra):
     reference's file layout, so either side can load the other's checkpoints.  distill=dict(steps=K) records the stage of
     a progressive distillation (load_checkpoint); the teacher's weights are not part of the file.
     self_cond=model.self_cond records the self-conditioning setting, which state_dict() does not hold (only the stem's
-    shape differs)."""
+    shape differs); learned_variance=model.learned_variance likewise records the vlb weight of a learned variance (only
+    the head's shape differs)."""
     out = dict(extra)
     if out.get("distill") is not None:
         _check_distill_extra(out["distill"])
@@ -153,7 +154,8 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     as the teacher) is a plain dict with an integer steps >= 1, checked (ValueError otherwise) and returned with the other
     extras: the caller builds the teacher and calls set_distill.  A "self_cond" entry (save_checkpoint(...,
     self_cond=model.self_cond): the self-conditioning probability, or None) must equal the model's own: ValueError
-    otherwise, before anything is loaded.  Files without the entry load as before."""
+    otherwise, before anything is loaded.  A "learned_variance" entry (save_checkpoint(...,
+    learned_variance=model.learned_variance): the vlb weight, or None) likewise.  Files without the entry load as before."""
     sd = torch.load(path, map_location=device, weights_only=False)
     if sd.get("distill") is not None:
         _check_distill_extra(sd["distill"])
@@ -164,6 +166,9 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     if "self_cond" in sd and sd["self_cond"] != getattr(model, "self_cond", None):
         raise ValueError(f"the checkpoint was trained with self-conditioning {sd['self_cond']!r}, the model is set to "
                          f"{getattr(model, 'self_cond', None)!r} (set_self_cond)")
+    if "learned_variance" in sd and sd["learned_variance"] != getattr(model, "learned_variance", None):
+        raise ValueError(f"the checkpoint was trained with a learned variance of vlb weight {sd['learned_variance']!r}, the "
+                         f"model is set to {getattr(model, 'learned_variance', None)!r} (set_learned_variance)")
     model.load_state_dict(sd["model"])
     if optimizer is not None and "optimizer" in sd and sd["optimizer"].get("state"):
         optimizer.load_state_dict(sd["optimizer"])

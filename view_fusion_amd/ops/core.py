@@ -80,6 +80,9 @@ _CALL_KIND = {"vf_wino44_pack_weights": "pack", "vf_wino44_pack_weights_multi": 
               "vf_sampler_step_eps": "diffusion", "vf_sampler_step_eps_rng": "diffusion",
               "vf_distill_begin": "diffusion", "vf_distill_target": "diffusion",
               "vf_stack_views_sc": "diffusion", "vf_draw_self_cond": "diffusion", "vf_self_cond_estimate": "diffusion",
+              "vf_compose_loss_lv_fwd": "diffusion", "vf_compose_loss_lv_bwd": "diffusion",
+              "vf_sampler_step_lv": "diffusion", "vf_sampler_step_lv_rng": "diffusion",
+              "vf_sampler_step_lv_cfg": "diffusion", "vf_sampler_step_lv_cfg_rng": "diffusion",
               "vf_grad_sumsq_multi": "adam", "vf_grad_norm_finish": "adam", "vf_adam_multi_ex": "adam",
               "vf_adam_multi_ex_dev": "adam", "vf_adam_set_scalars_ex": "adam", "vf_swap_multi": "adam", "vf_grad_accum_multi": "adam"}
 

@@ -368,7 +368,9 @@ class _ComposeLossFn(torch.autograd.Function):
         out, target, nh, off = ctx.saved_tensors
         S, Cout, H, W = out.shape
         gloss = _c(gloss.reshape(1).float())
-        dout = torch.empty_like(out)
+        # (the kernel writes channels 0..5; a wider output -- a learned-variance network trained without the vlb term --
+        # gets zeros behind them)
+        dout = torch.empty_like(out) if Cout <= 6 else torch.zeros_like(out)
         _call("vf_compose_mse_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(nh),
                   _ptr(gloss), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, _stream())
         return dout, None, None, None, None
@@ -431,7 +433,7 @@ class _ComposeLossOptFn(torch.autograd.Function):
         out, target, y_0, level, nh, off, sample_w = ctx.saved_tensors
         S, Cout, H, W = out.shape
         gloss = _c(gloss.reshape(1).float())
-        dout = torch.empty_like(out)
+        dout = torch.empty_like(out) if Cout <= 6 else torch.zeros_like(out)      # (as in _ComposeLossFn.backward)
         if ctx.pred:
             entry, front, back = "vf_compose_loss_pred_bwd", (_ptr(target), _ptr(y_0), _ptr(level)), (ctx.pred,)
         else:
@@ -439,6 +441,95 @@ class _ComposeLossOptFn(torch.autograd.Function):
         _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, _ptr(nh), _ptr(gloss), _ptr(sample_w), _ptr(dout),
               ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, *back, _stream())
         return (dout,) + (None,) * 15
+
+
+class _ComposeLossLvFn(torch.autograd.Function):
+    """_ComposeLossOptFn on a nine-channel output with the vlb term of a learned variance (csrc/diffusion.hip holds the
+    definition): loss = L_simple + lam mean_b vlb_b; the per-sample loss, the weight and the per-sample vlb (bits per
+    dimension) as non-differentiable outputs.  Two launches forward, one backward, which writes all nine channels."""
+
+    @staticmethod
+    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, pred, y_0, t, c1,
+                hi, lo, lam):
+        _check(out, target, y_0, level, bin_sum, c1, hi, lo)
+        S, Cout, H, W = out.shape
+        T = c1.numel()
+        K = 0
+        if bin_sum is not None:
+            K = bin_sum.numel()
+            if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
+                raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
+        nh = torch.empty(2, B, 3, H, W, device=out.device, dtype=torch.float32)      # composed prediction | composed o_b
+        buf = torch.empty(B * 131 + 1, device=out.device, dtype=torch.float32)       # partials x 2 | s | w | vlb | loss
+        vlb_part, sample_loss, sample_w = buf[B * 64:B * 128], buf[B * 128:B * 129], buf[B * 129:B * 130]
+        sample_vlb, loss = buf[B * 130:B * 131], buf[B * 131:]
+        _call("vf_compose_loss_lv_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(y_0), _ptr(level),
+              ctypes.c_void_p(t.data_ptr()), _ptr(c1), _ptr(hi), _ptr(lo), _ptr(nh[0]), _ptr(nh[1]), _ptr(buf),
+              _ptr(vlb_part), _ptr(sample_loss), _ptr(sample_w), _ptr(sample_vlb), _ptr(loss), _ptr(bin_sum),
+              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
+              delta, kind, a, b, K, pred, T, lam, _stream())
+        ctx.save_for_backward(out, target, y_0, level, nh, off, sample_w, t, c1, hi, lo)
+        ctx.B, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred, ctx.lam = B, int(weighting), penalty, delta, pred, lam
+        ctx.mark_non_differentiable(sample_loss, sample_w, sample_vlb)
+        return loss.reshape(()), sample_loss, sample_w, sample_vlb
+
+    @staticmethod
+    def backward(ctx, gloss, _gsample, _gweight, _gvlb):
+        out, target, y_0, level, nh, off, sample_w, t, c1, hi, lo = ctx.saved_tensors
+        S, Cout, H, W = out.shape
+        gloss = _c(gloss.reshape(1).float())
+        dout = torch.empty_like(out)
+        _call("vf_compose_loss_lv_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(y_0), _ptr(level),
+              ctypes.c_void_p(t.data_ptr()), _ptr(c1), _ptr(hi), _ptr(lo), _ptr(nh[0]), _ptr(nh[1]), _ptr(gloss),
+              _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred, c1.numel(),
+              ctx.lam, _stream())
+        return (dout,) + (None,) * 19
+
+
+def _check_nine(what, unet_out):
+    if unet_out.dim() != 4 or unet_out.shape[1] != 9:
+        raise ValueError(f"{what} needs a network output of 9 channels (prediction 0..2, logits 3..5, variance 6..8), "
+                         f"got {unet_out.shape[1] if unet_out.dim() == 4 else tuple(unet_out.shape)} instead of 9")
+
+
+def _compose_loss_lv(unet_out, target, off, B, weighting, level, penalty, delta, weight_kind, a, b, hist, prediction, y_0,
+                     vlb):
+    """The vlb= path of compose_loss: the checks, then _ComposeLossLvFn."""
+    if not isinstance(vlb, (tuple, list)) or len(vlb) != 5:
+        raise ValueError("vlb= takes (t, c1, hi, lo, weight)")
+    t, c1, hi, lo, lam = vlb
+    _check_nine("compose_loss(vlb=)", unet_out)
+    lam = float(lam)
+    if not math.isfinite(lam) or lam < 0:
+        raise ValueError(f"the vlb weight must be finite and >= 0, got {lam}")
+    _, _, H, W = unet_out.shape
+    if level.numel() != B:
+        raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
+    if tuple(target.shape) != (B, 3, H, W) or (y_0 is not None and tuple(y_0.shape) != (B, 3, H, W)):
+        raise ValueError(f"compose_loss needs a target / noise and y_0 of shape {(B, 3, H, W)}")
+    if not (c1.numel() == hi.numel() == lo.numel()) or c1.numel() < 1:
+        raise ValueError(f"vlb= needs c1, hi and lo of one length T, got {c1.numel()}, {hi.numel()} and {lo.numel()}")
+    _check_i64("vlb's t", t, B)
+    bin_sum, bin_cnt = hist if hist is not None else (None, None)
+    return _ComposeLossLvFn.apply(unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty],
+                                  float(delta), WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt,
+                                  PREDICTIONS[prediction], None if y_0 is None else _c(y_0), t, _c(c1), _c(hi), _c(lo), lam)
+
+
+def vlb_terms_host(o, hi, lo, c1, level, r, prediction="eps"):
+    """The host mirror of csrc/vlb.h: float tensors / sequences of one length -> (lp, kl, dkl) float32 CPU tensors: the
+    log-variance, KL in bits and dKL/dlp per element, m^2 = c1^2 kappa^2(level) r^2.  No GPU."""
+    check_prediction(prediction)
+    arrs = [torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1).contiguous() for v in (o, hi, lo, c1, level, r)]
+    n = arrs[0].numel()
+    if any(v.numel() != n for v in arrs):
+        raise ValueError("vlb_terms_host needs six inputs of one length")
+    outs = [torch.empty(n, dtype=torch.float32) for _ in range(3)]
+    rc = _lib.load().vf_vlb_terms_host(*(ctypes.c_void_p(v.data_ptr()) for v in arrs), PREDICTIONS[prediction],
+                                       *(ctypes.c_void_p(v.data_ptr()) for v in outs), n)
+    if rc != 0:
+        raise _lib.VFHipError(f"vf_vlb_terms_host failed with {rc}")
+    return tuple(outs)
 
 
 # ---- prediction (csrc/diffusion.hip holds the definition): what channels 0..2 of the network mean ----
@@ -468,7 +559,7 @@ def loss_weights_pred_host(level, prediction="eps", weight_kind=None, a=0.0, b=0
 
 
 def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delta=1.0, weight_kind=None, a=0.0, b=0.0,
-                 hist=None, sample_scale=None, want_weight=False, prediction="eps", y_0=None):
+                 hist=None, sample_scale=None, want_weight=False, prediction="eps", y_0=None, vlb=None):
     """compose_mse_loss with options: -> (loss, sample_loss).  d = compose(unet_out) - target;
     penalty "mse" d^2 | "l1" |d| | "huber" (F.huber_loss with `delta`);  sample_loss[b] = mean_i rho(d_bi) (B,), detached;
     weight_kind None | "min_snr" (w = min(1, a (1 - g) / g)) | "p2" (w = (a + g / (1 - g))^-b) | "trunc_snr"
@@ -482,7 +573,13 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
     prediction "eps" (the default: everything above, launch for launch) | "v" | "x0" (csrc/diffusion.hip holds the
     definition): `target` is then the NOISE and y_0 (B, 3, H, W) is required; d = compose(unet_out) - the prediction's
     own target (v: sqrt(g) noise - sqrt(1 - g) y_0; x0: y_0), formed inside the loss kernels from noise, y_0 and level --
-    no target buffer, the same launch count -- and w the prediction's native weight (csrc/loss_weight.h)."""
+    no target buffer, the same launch count -- and w the prediction's native weight (csrc/loss_weight.h).
+    vlb=(t, c1, hi, lo, weight) (default None: everything above, launch for launch): the hybrid objective of a learned
+    variance (csrc/diffusion.hip holds the definition) on a NINE-channel unet_out -- loss = the loss above + weight
+    mean_b vlb_b, vlb_b the mean over the sample's elements of KL(posterior || model) in bits, with the model's
+    log-variance between lo[t] and hi[t] by the composed channels 6..8 and the residual d a constant inside it.  t: device
+    int64 (B,); c1 (posterior_mean_coef1), hi, lo: device fp32 (T,) (schedule.variance_tables).  -> (loss, sample_loss,
+    [w,] sample_vlb); the same launch count; the backward writes all nine channels.  No sample_scale."""
     if penalty not in PENALTIES:
         raise ValueError(f"unknown penalty {penalty!r}: one of {sorted(PENALTIES)}")
     if weight_kind not in WEIGHT_KINDS:
@@ -492,6 +589,12 @@ def compose_loss(unet_out, target, off, B, weighting, level, penalty="mse", delt
         raise ValueError(f"prediction {prediction!r} forms its target from the noise and y_0: y_0= is required")
     if prediction == "eps" and y_0 is not None:
         raise ValueError("y_0= belongs to prediction 'v' / 'x0' (with 'eps' the target is handed over ready-made)")
+    if vlb is not None:
+        if sample_scale is not None:
+            raise ValueError("vlb= takes no sample_scale= (a level sampler with a learned variance is not built)")
+        loss, sample_loss, weight, sample_vlb = _compose_loss_lv(unet_out, target, off, B, weighting, level, penalty, delta,
+                                                                 weight_kind, a, b, hist, prediction, y_0, vlb)
+        return (loss, sample_loss, weight, sample_vlb) if want_weight else (loss, sample_loss, sample_vlb)
     bin_sum, bin_cnt = hist if hist is not None else (None, None)
     if sample_scale is not None:
         sample_scale = _c(sample_scale.reshape(-1))
@@ -722,7 +825,7 @@ def p_sample_tail(unet_out, off, y_t, z, t, sched, B, max_views, weighting, clip
 
 def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_prev=None, want_weights=True,
                  inplace=False, seed=None, ids=None, guidance=None, S=None, threshold=None, threshold_max=None,
-                 guidance_rescale=None, scratch=None):
+                 guidance_rescale=None, scratch=None, variance=None, want_logvar=False):
     """One step of a few-step sampler (strided DDIM / DPM-Solver++ 2M), fused like p_sample_tail:
     compose -> y0 = clamp(a[k] y - b[k] eps) -> y_new = cy[k] y + c0[k] y0 + c1[k] y0_prev + sigma[k] z, k = kidx[b].
     tables: the fp32 device tables a, b, cy, c0, c1, sigma (K,) and tau (K,) int64 (ViewFusion._sampler_plan).
@@ -730,8 +833,18 @@ def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_
     Returns (y_next, weights | None).  seed= (with z=None): z is drawn inside the kernel from
     (seed, ids[b], tau[k], element); where sigma[k] == 0 no z is loaded or drawn at all.
     guidance (device fp32 (B,)) with S=: the guided tail, as in p_sample_tail.
-    threshold / threshold_max / guidance_rescale / scratch: as in p_sample_tail; y0_prev receives the thresholded y0."""
+    threshold / threshold_max / guidance_rescale / scratch: as in p_sample_tail; y0_prev receives the thresholded y0.
+    variance=(hi, lo) (default None: everything above, launch for launch): the learned-variance step (csrc/diffusion.hip
+    holds the definition) on a NINE-channel unet_out and the "ddim", eta = 1 tables -- where sigma[k] != 0 the noise
+    scale is expf(0.5 lp) per element, lp between lo[k] and hi[k] (device fp32 (K,), schedule.variance_tables) by the
+    composed channels 6..8 of the conditional rows; no history term and no threshold / rescale flavour.
+    want_logvar=True (with variance=): -> (y_next, weights | None, lp (B,3,H,W))."""
     q, cmax, phi = threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None)
+    if variance is not None:
+        return _sampler_step_lv(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_prev, want_weights, inplace,
+                                seed, ids, guidance, S, q is not None or phi > 0.0, variance, want_logvar)
+    if want_logvar:
+        raise ValueError("want_logvar= belongs to the learned-variance step: it needs variance=(hi, lo)")
     _check(unet_out, y, z, y0_prev, *(tables[n] for n in ("a", "b", "cy", "c0", "c1", "sigma")))
     if guidance is not None:
         _check_guidance(guidance, unet_out, B, S)
@@ -763,6 +876,50 @@ def sampler_step(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_
     _call(f"vf_sampler_step{eps}{rng}", *src, _ptr(y), *noise, *idx, *(_ptr(tab) for tab in tabs), _ptr(y0_prev),
           _ptr(y_next), *sizes, _stream())
     return y_next, wts
+
+
+def _sampler_step_lv(unet_out, off, y, z, kidx, tables, B, max_views, weighting, y0_prev, want_weights, inplace, seed, ids,
+                     guidance, S, dynamic, variance, want_logvar):
+    """The variance= path of sampler_step: the checks, then one of the four vf_sampler_step_lv* entries."""
+    if not isinstance(variance, (tuple, list)) or len(variance) != 2:
+        raise ValueError("variance= takes (hi, lo)")
+    if dynamic:
+        raise ValueError("threshold= / guidance_rescale= with a learned variance are not built: the tails on the eps "
+                         "buffer carry no variance")
+    hi, lo = variance
+    tabs = [tables[n] for n in ("a", "b", "cy", "c0", "sigma")]
+    _check(unet_out, y, z, y0_prev, hi, lo, *tabs)
+    _check_nine("sampler_step(variance=)", unet_out)
+    K = tabs[0].numel()
+    if any(tab.numel() != K for tab in tabs) or hi.numel() != K or lo.numel() != K:
+        raise ValueError(f"variance= needs hi and lo of the chain's length {K}, got {hi.numel()} and {lo.numel()}")
+    if "c1" in tables and bool(tables.get("multistep", False)):
+        raise ValueError("the learned-variance step has no history term: it runs on the 'ddim' tables")
+    if guidance is not None:
+        _check_guidance(guidance, unet_out, B, S)
+    if seed is not None and z is not None:
+        raise ValueError("sampler_step takes either z or seed=, not both")
+    _, Cout, H, W = unet_out.shape
+    if tuple(y.shape) != (B, 3, H, W):
+        raise ValueError(f"sampler_step needs y of shape {(B, 3, H, W)}, got {tuple(y.shape)}")
+    kidx = _c(kidx.to(torch.int64))
+    y_next = y if inplace else torch.empty_like(y)
+    wts = None
+    if weighting and want_weights:
+        wts = torch.empty(B, max_views, 3, H, W, device=y.device, dtype=torch.float32)
+    lp = torch.empty_like(y) if want_logvar else None
+    rng, noise = _tail_noise(z, seed, ids, y.device, B)
+    idx = (ctypes.c_void_p(kidx.data_ptr()),)
+    if rng:
+        tau = tables["tau"]
+        if not tau.is_cuda or tau.dtype != torch.int64 or not tau.is_contiguous() or tau.numel() != K:
+            raise _lib.VFHipError(f"tables['tau'] must be a contiguous device int64 tensor of {K} elements")
+        idx += (ctypes.c_void_p(tau.data_ptr()),)
+    cfg = "" if guidance is None else "_cfg"
+    _call(f"vf_sampler_step_lv{cfg}{rng}", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y), *noise, *idx,
+          *(_ptr(tab) for tab in tabs), _ptr(hi), _ptr(lo), _ptr(y0_prev), _ptr(y_next), _ptr(wts), _ptr(lp), B, Cout,
+          H * W, max_views, int(weighting), *(() if guidance is None else (_ptr(guidance),)), _stream())
+    return (y_next, wts, lp) if want_logvar else (y_next, wts)
 
 
 # ---- progressive distillation (csrc/diffusion.hip holds the definition) ----

@@ -181,6 +181,29 @@ def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps"):
     return out
 
 
+# ---- learned variance: the two log-variances a reverse step interpolates between (csrc/diffusion.hip) ---------------
+def variance_tables(betas, tau=None):
+    """float64 betas (T,), tau (K,) (default 0..T-1) -> (hi, lo), float64 (K,) each (rounded to fp32 once, by the caller).
+    With gt = gammas[tau[k]], gp = gammas[tau[k-1]] (1 at k = 0): hi[k] = log(1 - gt/gp), the log of the chain's own beta,
+    and lo[k] = log(max((1 - gt/gp)(1 - gp)/(1 - gt), 1e-20)), the log of its posterior variance, clipped as
+    posterior_log_variance_clipped is: on the full schedule hi = log(betas) and lo equals that buffer value for value."""
+    betas = np.asarray(betas, dtype=np.float64)
+    if tau is None or np.array_equal(np.asarray(tau), np.arange(betas.shape[0])):
+        # the schedule's own steps: schedule_tensors' very expressions
+        gammas = np.cumprod(1.0 - betas, axis=0)
+        prev = np.append(1.0, gammas[:-1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            var = betas * (1.0 - prev) / (1.0 - gammas)
+            return np.log(betas), np.log(np.maximum(var, 1e-20))
+    tau = np.asarray(tau, dtype=np.int64)
+    gammas = np.cumprod(1.0 - betas, axis=0)
+    gt = gammas[tau]
+    gp = np.append(1.0, gt[:-1])
+    beta = 1.0 - gt / gp
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.log(beta), np.log(np.maximum(beta * (1.0 - gp) / (1.0 - gt), 1e-20))
+
+
 # ---- progressive distillation: the grids and the target weights of a K-step student of a 2K-step teacher ------------
 def distill_tables(betas, K, teacher_prediction="eps"):
     """float64 betas (T,), K student steps -> {tau_s (K,), tau_t (2K,) int64; w1, w2 float64 (K,); teacher, student: the two

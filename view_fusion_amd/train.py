@@ -136,7 +136,7 @@ class _StepGraph:
     """One captured training iteration (forward, backward, Adam) for one batch geometry -- or, with accum_steps > 1, one
     captured micro-batch (forward, backward, the accumulate launch)."""
     __slots__ = ("graph", "inputs", "view_count", "off", "vc", "loss", "adam", "keep", "seen", "grads", "accum", "sample", "drop",
-                 "level")
+                 "level", "vlb")
 
     def __init__(self):
         self.graph, self.seen, self.accum = None, 0, None
@@ -212,6 +212,11 @@ class Trainer:
     graph inputs: a captured step holds the second pass alone.  With seed= a sample's coin is a function of (seed,
     sample id), the same under accum_steps and graph replay.  `model.last_self_cond` = (keep, x^) of the last first pass.
     Multi-rank: the phase has no collective; nothing else is built for it.
+
+    A learned variance (`model.set_learned_variance(vlb_weight)`, csrc/diffusion.hip; default None: nothing above
+    changes) is the model's as well, and the weight is part of the same key.  The hybrid step has the default step's
+    launch count, so every launch mode, seed=, accum_steps, loss_bins, max_grad_norm and the EMA take it unchanged;
+    in graph mode `model.last_sample_vlb` is a static buffer of the captured step, like `last_sample_loss`.
 
     Residual-block Dropout (`UNet(dropout=p)`) needs no argument here: with seed= every mask is a function of (seed,
     sample id, view index, layer, element) drawn inside the Dropout kernel and drawn again by its backward
@@ -558,8 +563,10 @@ class Trainer:
         # the loss-option kernels' per-sample outputs are static buffers of this graph (None on the default path)
         e.sample = None
         if getattr(self.module, "_loss", None) is not None or getattr(self.module, "loss_hist", None) is not None or \
-                getattr(self.module, "_level_spec", None) is not None:
+                getattr(self.module, "_level_spec", None) is not None or \
+                getattr(self.module, "_lv_weight", None) is not None:
             e.sample = (self.module.last_sample_loss, self.module.last_level)
+        e.vlb = getattr(self.module, "last_sample_vlb", None)      # a learned variance: the step's per-sample vlb, likewise
         e.drop = getattr(self.module, "last_cond_drop", None)      # conditioning dropout: the step's mask, likewise
         e.level = (getattr(self.module, "last_t", None), getattr(self.module, "last_importance_weight", None))
         e.grads = list(grads)
@@ -581,6 +588,8 @@ class Trainer:
             self.module.last_sample_loss, self.module.last_level = e.sample
         if hasattr(self.module, "last_cond_drop"):
             self.module.last_cond_drop = e.drop
+        if e.vlb is not None:
+            self.module.last_sample_vlb = e.vlb
         if hasattr(self.module, "last_t"):             # the level sampler's draw: static buffers of the graph, likewise
             self.module.last_t, self.module.last_importance_weight = e.level
         if accum is not None:                          # a micro-batch: its gradient goes into the accumulators, which

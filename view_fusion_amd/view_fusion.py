@@ -49,6 +49,11 @@ there in one step of its own K-step chain.  csrc/diffusion.hip holds the definit
 `set_self_cond(p)` (default None: every launch and every bit as before) shows the network -- built with three more input
 channels -- its own previous estimate of the clean image: in training the estimate of one extra no-grad forward, kept
 with probability p; in sampling the y0 the previous reverse step computed anyway.  csrc/diffusion.hip holds the definition.
+
+`set_learned_variance(vlb_weight)` (default None: every launch and every bit as before) trains a network built with three
+more output channels to predict, per pixel, the log-variance of a reverse step between log beta~ and log beta (Improved
+DDPM): forward() takes L_simple + vlb_weight L_vlb in the same launch count, and the stochastic few-step sampler (ddim,
+eta = 1) draws its noise at that scale.  csrc/diffusion.hip holds the definition, csrc/vlb.h the arithmetic.
 """
 import torch
 from torch import nn
@@ -88,6 +93,98 @@ class ViewFusion(nn.Module):
         # plain attributes too
         self._self_cond_p = None
         self.last_self_cond = None
+        # a learned variance (set_learned_variance): the vlb weight (None: off), the last training forward's per-sample
+        # vlb and the device tables (c1, hi, lo), made on demand: plain attributes too
+        self._lv_weight = None
+        self.last_sample_vlb = None
+        self._lv_tabs = None
+
+    # -- a learned variance -------------------------------------------------------------------
+    def set_learned_variance(self, vlb_weight=1e-3):
+        """A learned reverse-process variance (Nichol & Dhariwal, "Improved DDPM"; csrc/diffusion.hip holds the definition).
+        set_learned_variance(None), the default: off -- every launch and every bit as before.
+
+        The network -- UNet(out_channel=9) -- also predicts, in channels 6..8, where between log beta~ and log beta the
+        log-variance of a reverse step lies, per pixel.  Training: forward() takes the hybrid objective L_simple +
+        vlb_weight L_vlb -- L_simple is today's objective with every set_loss / set_prediction / loss_bins option, L_vlb
+        the KL of the step's posterior from the model's Gaussian, in bits per dimension, with the mean held constant -- in
+        the same launch count; `last_sample_vlb` (B,) is the per-sample vlb of the last training forward (a device tensor,
+        no sync).  Sampling: generate() with solver "ddim" and eta = 1 -- which is what sample_steps=None runs, as
+        sample_steps=T -- draws every step's noise at the learned per-pixel scale; every other (solver, eta) has no
+        posterior-variance noise to replace and runs the existing kernels, which ignore channels 6..8.  p_sample takes the
+        learned step, p_mean_variance returns the per-pixel log-variance, and the logits handed back are channels 3..5.
+        A plain attribute (`learned_variance` reads it back): no buffer, no parameter -- save it as
+        save_checkpoint(..., learned_variance=model.learned_variance).  A Trainer drops its captured steps when it changes.
+        Refused with ValueError (DESIGN 8): together with set_distill (on either model), set_self_cond or a level sampler;
+        threshold= / guidance_rescale=; and, when it runs, a CPU model or a network whose output is not 9 channels."""
+        if vlb_weight is None:
+            self._lv_weight = None
+            self.last_sample_vlb = None
+            return
+        import math
+        w = float(vlb_weight)
+        if not math.isfinite(w) or w < 0:
+            raise ValueError(f"the vlb weight must be finite and >= 0, got {vlb_weight}")
+        if self._distill is not None:
+            raise ValueError("a learned variance on a distillation student is not built (DESIGN 8): set_distill(None) first")
+        if self._self_cond_p is not None:
+            raise ValueError("a learned variance together with self-conditioning is not built (DESIGN 8): "
+                             "set_self_cond(None) first")
+        if self._level_spec is not None:
+            raise ValueError("a learned variance together with a level sampler is not built (DESIGN 8): "
+                             "set_level_sampler(None) first")
+        self._lv_weight = w
+
+    @property
+    def learned_variance(self):
+        """The vlb weight of set_learned_variance, None while it is off."""
+        return self._lv_weight
+
+    @staticmethod
+    def _out_channels(net):
+        last = None
+        for m in net.modules():
+            if isinstance(m, nn.Conv2d):
+                last = m
+        return None if last is None else last.out_channels
+
+    def _check_lv(self, dev, threshold=None, guidance_rescale=None):
+        """ValueError, before any launch, where a learned-variance pass cannot run."""
+        if self._distill is not None or self._self_cond_p is not None or self._level_spec is not None:
+            raise ValueError("a learned variance with distillation, self-conditioning or a level sampler is not built "
+                             "(DESIGN 8)")
+        if threshold is not None or (guidance_rescale is not None and float(guidance_rescale) > 0):
+            raise ValueError("threshold= / guidance_rescale= with a learned variance are not built (DESIGN 8): the tails on "
+                             "the eps buffer carry no variance")
+        have = self._out_channels(self.denoise_fn)
+        if have is not None and have != 9:
+            raise ValueError(f"a learned-variance model reads 3 prediction + 3 logit + 3 variance channels = 9, the "
+                             f"network gives out_channel = {have}")
+        if torch.device(dev).type != "cuda":
+            raise ValueError("a learned variance runs on the GPU only (its loss and its reverse step are HIP kernels): "
+                             "move the model and the batch there")
+
+    def _lv_tables(self):
+        """The device tables of the hybrid loss on the full schedule: (posterior_mean_coef1, hi, lo), fp32 (T,)."""
+        dev = self.gammas.device
+        if self._lv_tabs is None or self._lv_tabs[0] != dev:
+            hi, lo = _schedule.variance_tables(self.betas64)
+            self._lv_tabs = (dev, torch.tensor(hi, dtype=torch.float32, device=dev),
+                             torch.tensor(lo, dtype=torch.float32, device=dev))
+        return self.posterior_mean_coef1, self._lv_tabs[1], self._lv_tabs[2]
+
+    def _lv_plan(self, tau, dev):
+        """The "ddim", eta = 1 plan of a chain with its variance tables (hi, lo) next to it."""
+        plan = self._sampler_plan(tau, "ddim", 1.0, dev)
+        if "hi" not in plan:
+            hi, lo = _schedule.variance_tables(self.betas64, tau)
+            plan["hi"] = torch.tensor(hi, dtype=torch.float32, device=dev)
+            plan["lo"] = torch.tensor(lo, dtype=torch.float32, device=dev)
+        return plan
+
+    def _logits(self, out, S):
+        """The view logits handed back: channels 3.. of the S conditional rows, 3..5 on a learned-variance model."""
+        return out[:S, 3:6, ...] if self._lv_weight is not None else out[:S, 3:, ...]
 
     # -- training objective -------------------------------------------------------------------
     def set_loss(self, penalty="mse", delta=1.0, weighting=None, snr_gamma=5.0, p2_k=1.0, p2_gamma=1.0):
@@ -160,6 +257,9 @@ class ViewFusion(nn.Module):
         if kind is not None and self._self_cond_p is not None:
             raise ValueError("a level sampler together with self-conditioning is not built (DESIGN 8): "
                              "set_self_cond(None) first")
+        if kind is not None and self._lv_weight is not None:
+            raise ValueError("a level sampler together with a learned variance is not built (DESIGN 8): "
+                             "set_learned_variance(None) first")
         self._level_gen += 1
         if kind is None:
             self._level_spec = self.level_sampler = None
@@ -230,6 +330,9 @@ class ViewFusion(nn.Module):
         if self._self_cond_p is not None or teacher._self_cond_p is not None:
             raise ValueError("distillation on or with a self-conditioned model is not built (DESIGN 8): "
                              "set_self_cond(None) on the student and the teacher first")
+        if self._lv_weight is not None or teacher._lv_weight is not None:
+            raise ValueError("distillation on or with a learned-variance model is not built (DESIGN 8): "
+                             "set_learned_variance(None) on the student and the teacher first")
         if getattr(self, "betas64", None) is None or getattr(teacher, "betas64", None) is None:
             raise ValueError("set_distill needs the noise schedule of both models: call set_new_noise_schedule first")
         import numpy as np
@@ -356,6 +459,9 @@ class ViewFusion(nn.Module):
         if self._level_spec is not None:
             raise ValueError("self-conditioning together with a level sampler is not built (DESIGN 8): "
                              "set_level_sampler(None) first")
+        if self._lv_weight is not None:
+            raise ValueError("self-conditioning together with a learned variance is not built (DESIGN 8): "
+                             "set_learned_variance(None) first")
         self._self_cond_p = p
 
     @property
@@ -451,11 +557,12 @@ class ViewFusion(nn.Module):
     def loss_key(self):
         """What a captured training step depends on besides its inputs: the objective, the attached histogram, the
         conditioning-dropout probability, the level sampler (every set_level_sampler call counts), the prediction, the
-        distillation settings (every set_distill call counts) and the self-conditioning probability."""
+        distillation settings (every set_distill call counts), the self-conditioning probability and the vlb weight of a
+        learned variance."""
         h = self.loss_hist
         return (None if self._loss is None else tuple(sorted(self._loss.items(), key=lambda kv: kv[0])),
                 None if h is None else (h[0].data_ptr(), h[1].data_ptr(), h[0].numel()), self._cond_drop_p,
-                self._level_gen, self.prediction, self._distill_gen, self._self_cond_p)
+                self._level_gen, self.prediction, self._distill_gen, self._self_cond_p, self._lv_weight)
 
     # -- schedule ---------------------------------------------------------------------------
     def set_new_noise_schedule(self, device=torch.device("cuda"), phase="train"):
@@ -464,6 +571,7 @@ class ViewFusion(nn.Module):
         self.betas64 = betas                   # float64, for the few-step sampler tables; not a buffer (state_dict)
         self._plan = None
         self._pred_tabs = None
+        self._lv_tabs = None
         for name, val in _schedule.schedule_tensors(betas, device).items():
             if name in self._buffers:
                 self._buffers[name] = val
@@ -555,12 +663,21 @@ class ViewFusion(nn.Module):
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
         self._check_samplable()
+        if self._lv_weight is not None:
+            self._check_lv(y_t.device, threshold, guidance_rescale)
+            if not clip_denoised:
+                raise ValueError("the learned-variance step clamps y0_hat: clip_denoised=False is not built")
         sc = self._sc_step(y_t, y_cond, self_cond)
         dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
         off, S, max_v = ops.view_offsets(view_count, y_t.device)
         _, out = self._denoise(y_t, y_cond, angle, t, off, S, null_rows=gs is not None, sc=sc)
         w_on = bool(self.weighting_inference)
+        if self._lv_weight is not None:   # the learned step without noise is the mean; its log-variance is per pixel
+            plan = self._lv_plan(list(range(self.num_timesteps)), y_t.device)
+            mean, weights, lp = ops.sampler_step(out, off, y_t, None, t, plan, y_t.shape[0], max_v, w_on, guidance=gs, S=S,
+                                                 variance=(plan["hi"], plan["lo"]), want_logvar=True)
+            return mean, lp, (self._logits(out, S) if w_on else None), weights
         _, mean, weights = ops.p_sample_tail(out, off, y_t, None, t, self._sched(), y_t.shape[0], max_v, w_on,
                                              clip=clip_denoised, want_mean=True, guidance=gs, S=S, **dyn)
         logits = out[:S, 3:, ...] if w_on else None
@@ -573,6 +690,10 @@ class ViewFusion(nn.Module):
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
         self._check_samplable()
+        if self._lv_weight is not None:
+            self._check_lv(y_t.device, threshold, guidance_rescale)
+            if not clip_denoised:
+                raise ValueError("the learned-variance step clamps y0_hat: clip_denoised=False is not built")
         sc = self._sc_step(y_t, y_cond, self_cond)
         dyn = dict(threshold=threshold, threshold_max=threshold_max, guidance_rescale=guidance_rescale)
         gs = None if guidance is None else ops.guidance_scales(y_t.device, y_t.shape[0], guidance)
@@ -583,6 +704,11 @@ class ViewFusion(nn.Module):
         elif not bool((t > 0).any()):
             z = None
         w_on = bool(self.weighting_inference)
+        if self._lv_weight is not None:   # sigma[0] == 0: the tail reads no z at t = 0 (one t for the batch, as generate)
+            plan = self._lv_plan(list(range(self.num_timesteps)), y_t.device)
+            y, weights = ops.sampler_step(out, off, y_t, z, t, plan, y_t.shape[0], max_v, w_on, guidance=gs, S=S,
+                                          variance=(plan["hi"], plan["lo"]))
+            return y, (self._logits(out, S) if w_on else None), weights
         y, _, weights = ops.p_sample_tail(out, off, y_t, z, t, self._sched(), y_t.shape[0], max_v, w_on,
                                           clip=clip_denoised, guidance=gs, S=S, **dyn)
         return y, (out[:S, 3:, ...] if w_on else None), weights
@@ -635,6 +761,11 @@ class ViewFusion(nn.Module):
         dyn = {}
         plan = tau = None
         self._check_samplable()
+        lv_on = self._lv_weight is not None
+        if lv_on:                                         # only the table-driven tail has the learned-variance flavour
+            self._check_lv(y_cond.device, threshold, guidance_rescale)
+            if sample_steps is None:
+                sample_steps, solver, eta = self.num_timesteps, "ddim", 1.0
         sc_on = self._self_cond_p is not None
         if sc_on:                                         # only the table-driven tail hands y0 back
             self._check_self_cond(y_cond.shape[2], y_cond.device)
@@ -666,7 +797,9 @@ class ViewFusion(nn.Module):
         z = None if z_seed is not None else torch.zeros_like(y)
         levels, hist = self.gammas, None
         if tau is not None:
-            plan = self._sampler_plan(tau, solver, eta, dev)
+            lv_step = lv_on and solver == "ddim" and float(eta) == 1.0
+            plan = self._lv_plan(tau, dev) if lv_step else self._sampler_plan(tau, solver, eta, dev)
+            lv = dict(variance=(plan["hi"], plan["lo"])) if lv_step else {}
             levels = plan["level"]
             # y0 of the step before; the multistep tail never reads it first ...
             hist = self._history_buffer(y) if plan["multistep"] or sc_on else None
@@ -689,7 +822,7 @@ class ViewFusion(nn.Module):
                                    sc=sc)
             if plan is not None:
                 _, weights = ops.sampler_step(out, off, y, z, t, plan, b, max_v, w_on, y0_prev=hist, inplace=True,
-                                              seed=z_seed, ids=ids, guidance=gs, S=S, **dyn)
+                                              seed=z_seed, ids=ids, guidance=gs, S=S, **dyn, **lv)
                 return out, weights
             _, _, weights = ops.p_sample_tail(out, off, y, z, t, sched, b, max_v, w_on, inplace=True, seed=z_seed,
                                               ids=ids, guidance=gs, S=S, **dyn)
@@ -728,7 +861,7 @@ class ViewFusion(nn.Module):
                 out, weights = step()
             if i % every == 0:
                 ret.append(y.clone())
-                logit_arr.append(out[:S, 3:, ...].clone() if w_on else None)
+                logit_arr.append(self._logits(out, S).clone() if w_on else None)
                 weight_arr.append(weights.clone() if w_on else None)
         ret = torch.stack(ret, dim=1)
         samples = ret[:, -1, ...]
@@ -753,6 +886,11 @@ class ViewFusion(nn.Module):
         b = y_0.shape[0]
         dev = y_0.device
         level = None
+        if self._lv_weight is not None:
+            self._check_lv(dev)
+            if distill_z is not None or self_cond is not None:
+                raise ValueError("a distillation or self-conditioned step on a learned-variance model is not built "
+                                 "(DESIGN 8)")
         if distill_z is not None or (self._distill is not None and self.training):
             # progressive distillation (set_distill): the teacher phase -- or its four outputs, injected -- then the
             # student's ordinary stacking of z_t at its level, the UNet and the ordinary objective on (eps~, x~)
@@ -855,10 +993,19 @@ class ViewFusion(nn.Module):
         loss-option kernels (set_loss, loss_hist, a level sampler, a prediction other than "eps")."""
         from . import ops
         self.last_t, self.last_importance_weight = (None, None) if smp is None else (t, iw)
-        if self._loss is None and self.loss_hist is None and smp is None and self.prediction == "eps":
+        if self._loss is None and self.loss_hist is None and smp is None and self.prediction == "eps" and \
+                self._lv_weight is None:
             return ops.compose_mse_loss(out, noise, off, b, bool(self.weighting_train))
         # "v" / "x0": the loss kernels form the target themselves, from the noise and y_0
         pred = {} if self.prediction == "eps" else dict(prediction=self.prediction, y_0=y_0)
+        if self._lv_weight is not None:   # the hybrid objective: the same launch count, one more per-sample output
+            loss, sample_loss, _, vlb = ops.compose_loss(
+                out, noise, off, b, bool(self.weighting_train), level, **(self._loss or {}), hist=self.loss_hist,
+                want_weight=True, vlb=(t.reshape(-1).to(torch.int64).contiguous(), *self._lv_tables(), self._lv_weight),
+                **pred)
+            self.last_sample_loss, self.last_level = sample_loss.detach(), level.detach()
+            self.last_sample_vlb = vlb.detach()
+            return loss
         loss, sample_loss, weight = ops.compose_loss(out, noise, off, b, bool(self.weighting_train), level,
                                                      **(self._loss or {}), hist=self.loss_hist, sample_scale=iw,
                                                      want_weight=True, **pred)
