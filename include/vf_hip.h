@@ -573,7 +573,8 @@ int vf_rng_host_train_scalars(unsigned long long seed, const long long* ids, int
 /* vf_draw_cond_drop on the CPU */
 int vf_cond_drop_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* drop /*[B]*/, int B);
 /* ---- self-conditioning (csrc/diffusion.hip holds the definition): the network also sees its own previous estimate of
- *      the clean image, as three more input channels.  Siblings of the kernels above, which are untouched. ---- */
+ *      the clean image, as three more input channels.  The stacking is the guided kernel's SC instantiation; the other two
+ *      are siblings of the kernels above. ---- */
 /* vf_stack_views_cfg plus the third part: x [S (+ B)][Cc+6][HW], row v = [ cond | target | sc[b] ]; sc (DEVICE
  * [B][3][HW] | NULL: zeros).  drop / null_rows / copy_cond as there; copy_cond == 0 rewrites the target and sc parts only. */
 int vf_stack_views_sc(const float* y_cond, const float* y_t, const float* noise /*|NULL*/, const float* level,
@@ -595,7 +596,8 @@ int vf_self_cond_estimate(const float* unet_out, const int* off, const float* le
 int vf_self_cond_draw_host(unsigned long long seed, const long long* ids, unsigned thr, unsigned char* out /*[B]*/, int B);
 int vf_self_cond_coeffs_host(const float* level, int pred, float* a /*[n]*/, float* b /*[n]*/, int n);
 /* ---- learned variance (csrc/diffusion.hip holds the definition, csrc/vlb.h the arithmetic): unet_out has nine channels,
- *      0..2 the prediction, 3..5 the view logits, 6..8 the raw variance output.  Siblings of the entries above. ---- */
+ *      0..2 the prediction, 3..5 the view logits, 6..8 the raw variance output.  The loss entries run the LV instantiations
+ *      of the loss family's kernels, the tail entries a sibling of the few-step tail. ---- */
 /* The hybrid loss L_simple + lambda L_vlb: vf_compose_loss_pred_fwd / _bwd for pred 0 | 1 | 2 (0: noise is the ready-made
  * target, y_0 not read) plus t (DEVICE int64 [B], clamped into [0, T - 1]), the fp32 tables c1 (posterior_mean_coef1), hi,
  * lo [T], var_hat [B][3][HW] (the composed channels 6..8), vlb_part [B * 64], sample_vlb [B] (bits per dimension).  No

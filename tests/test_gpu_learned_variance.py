@@ -1,5 +1,6 @@
 """A learned variance on the GPU (ViewFusion.set_learned_variance, ops.compose_loss(vlb=), ops.sampler_step(variance=);
-the compose_loss_lv_fwd / _finish / _bwd kernels and sampler_step_lv_kernel<CFG, RNG> of csrc/diffusion.hip; definition
+the LV instantiations of the loss family -- compose_loss_fwd_kernel / _bwd_kernel<PEN, PRED, true> and the vlb operands of
+compose_loss_finish_kernel -- and sampler_step_lv_kernel<CFG, RNG> of csrc/diffusion.hip; definition
 at the head of that file, arithmetic in csrc/vlb.h) against the float64 restatement tests/vlb_ref.py.
 
   1. the hybrid loss against float64: softmax and mean; eps, v and x0; mse and huber (+ min_snr); t in {1, 7, T-1} on the

@@ -1,4 +1,5 @@
-"""tools/loss_bits.py's compare logic on synthetic JSON (no GPU): equal runs, a changed digest, a case on one side only."""
+"""tools/loss_bits.py's compare logic on synthetic JSON (no GPU): equal runs, a changed digest, a case on one side only;
+the same on the keys of the hybrid-loss and stacking grids, whose cases carry other digest names."""
 import importlib.util
 import json
 import os
@@ -34,3 +35,29 @@ def test_compare_finds_a_changed_digest_and_a_missing_case(tmp_path, capsys):
     assert lb.main(["--compare", old, write(tmp_path, "changed.json", changed)]) == 1
     out = capsys.readouterr().out
     assert "1 of 3 cases differ" in out and "'grad': '!='" in out and "'loss': '='" in out
+
+
+RUN_LV = {"12x20/vlb/v/huber/lam0.001/w1/hist1": dict(loss="aa", sample_loss="bb", weight="cc", sample_vlb="dd", grad="ee",
+                                                     bin_sum="ff", bin_cnt="00"),
+          "12x20/vlb/eps/mse/lam0.0/w0/hist0": dict(loss="ab", sample_loss="bc", weight="cd", sample_vlb="de", grad="ef",
+                                                   bin_sum=None, bin_cnt=None),
+          "8x8/stack/cc6/drop1/null1/sc_given/noise0/copy0": dict(x="11", level_s="22", angle_s="33"),
+          "8x8/stack/cc3/drop0/null0/sc_none/noise1/copy1": dict(x="12", level_s="23", angle_s="34")}
+
+
+def test_compare_on_the_hybrid_loss_and_stacking_keys(tmp_path, capsys):
+    assert lb.compare(RUN_LV, json.loads(json.dumps(RUN_LV))) == []
+    changed = json.loads(json.dumps(RUN_LV))
+    changed["12x20/vlb/v/huber/lam0.001/w1/hist1"]["sample_vlb"] = "0d"
+    changed["8x8/stack/cc6/drop1/null1/sc_given/noise0/copy0"]["x"] = "10"
+    assert lb.compare(changed, RUN_LV) == ["12x20/vlb/v/huber/lam0.001/w1/hist1",
+                                           "8x8/stack/cc6/drop1/null1/sc_given/noise0/copy0"]
+    fewer = {k: v for k, v in RUN_LV.items() if "/stack/" not in k}
+    assert lb.compare(fewer, RUN_LV) == lb.compare(RUN_LV, fewer) == sorted(k for k in RUN_LV if "/stack/" in k)
+
+    old = write(tmp_path, "old.json", RUN_LV)
+    assert lb.main(["--compare", old, write(tmp_path, "same.json", RUN_LV)]) == 0
+    assert "0 of 4 cases differ" in capsys.readouterr().out
+    assert lb.main(["--compare", old, write(tmp_path, "changed.json", changed)]) == 1
+    out = capsys.readouterr().out
+    assert "2 of 4 cases differ" in out and "'sample_vlb': '!='" in out and "'x': '!='" in out and "'angle_s': '='" in out

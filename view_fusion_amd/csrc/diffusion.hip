@@ -7,9 +7,11 @@
 // sync: ragged view counts come in as a device prefix-sum array `off[B+1]`.
 //
 // A map of this file, in the order of the file:
-//   stacking        stack_views_kernel (on the training step) and stack_views_cfg_kernel, the same kernel with
-//                   conditioning dropout and null rows -- two kernels on purpose: behind a shared body the compiler
-//                   generates other code for the plain one (profiles/tail_templates.md); draw_cond_drop_kernel.
+//   stacking        stack_views_kernel (on the training step) and stack_views_cfg_kernel<SC>, the same kernel with
+//                   conditioning dropout and null rows, and with SC the third part of self-conditioning -- the plain one
+//                   stands apart on purpose: behind a shared body the compiler generates other code for it
+//                   (profiles/tail_templates.md; the two guided flavours as one template: profiles/loss_lv_templates.md);
+//                   draw_cond_drop_kernel.
 //   composition     compose4 (softmax over the views, or the mean), guide4, write_weights (the softmax weights handed
 //                   back by the tails; compose_fwd_kernel and compose_eps_kernel keep that loop written out, for the
 //                   same reason).
@@ -18,15 +20,17 @@
 //                   function shared with the family, that kernel's code changes (SGPR 47 -> 45, s_add_u32 / s_addc_u32
 //                   4 -> 3: scalar address arithmetic associated differently; profiles/loss_templates.md), and the three
 //                   kernels of the benchmarked step keep their code.
-//   the loss family pred_target4, compose_loss_fwd_kernel<PEN, PRED> -> compose_loss_finish_kernel, and
-//                   compose_loss_bwd_kernel<PEN, PRED>: every other objective.  PEN: the penalty (mse / l1 / huber);
+//   the loss family pred_target4, compose_loss_fwd_kernel<PEN, PRED, LV> -> compose_loss_finish_kernel, and
+//                   compose_loss_bwd_kernel<PEN, PRED, LV>: every other objective.  PEN: the penalty (mse / l1 / huber);
 //                   PRED: what channels 0..2 mean -- eps (the target handed over ready-made), v, x0 (the target formed in
-//                   registers from noise, y_0 and level); nine instantiations of each.  The finish kernel takes the
-//                   prediction's native noise-level weight (none / min-SNR / P2 / truncated SNR) at run time, an optional
-//                   per-sample scale (the importance weight of a level-sampler draw), and writes the per-sample loss and an
-//                   optional loss-by-level histogram.  Same launch count as the MSE pair, no atomics; loss_weight.h holds
-//                   the specification.  The tails have no such switch: another parameterisation is another (a, b) table
-//                   pair.
+//                   registers from noise, y_0 and level); LV: the hybrid loss of a learned variance -- three variance
+//                   channels and a KL term taken in registers on the same residual (compose4_var, VlbArgs, vlb_sample in
+//                   front of the family; vlb.h holds the arithmetic); eighteen instantiations of each.  The finish kernel
+//                   takes the prediction's native noise-level weight (none / min-SNR / P2 / truncated SNR) at run time, an
+//                   optional per-sample scale (the importance weight of a level-sampler draw) or, never both, the vlb
+//                   partials and lambda, and writes the per-sample loss and an optional loss-by-level histogram.  Same
+//                   launch count as the MSE pair, no atomics; loss_weight.h holds the specification.  The tails have no
+//                   such switch: another parameterisation is another (a, b) table pair.
 //   step arithmetic y0_hat, y0_hat_as, posterior_update, multistep_base / _add: how each product and sum of a reverse
 //                   step is rounded, and why it is written operation by operation; EpsBound / EpsBuffer: what a tail on
 //                   the eps buffer knows about its sample.
@@ -44,17 +48,16 @@
 //                   selection on a plain buffer: abs_quantile_kernel) -> an EPS tail: the thresholded / rescaled step.
 //   distillation    distill_begin_kernel (the draw of i, z_t) and distill_target_kernel<CFG> (the second teacher step's tail:
 //                   x2, x~, eps~), siblings of draw_train / stack_views and of sampler_step_kernel.
-//   self-conditioning  stack_views_sc_kernel (stack_views_cfg_kernel plus the third part), self_cond_estimate_kernel<PRED>
-//                   (the first pass's clamped x0 estimate) and draw_self_cond_kernel: siblings, behind the distillation pair.
-//   learned variance  compose4_var, compose_loss_lv_fwd_kernel<PEN, PRED> -> compose_loss_lv_finish_kernel,
-//                   compose_loss_lv_bwd_kernel<PEN, PRED> (the hybrid loss: the family plus three variance channels and a KL
-//                   term taken in registers) and sampler_step_lv_kernel<CFG, RNG> (the few-step tail with a per-pixel noise
-//                   scale): siblings, behind the self-conditioning kernels; vlb.h holds the arithmetic.
+//   self-conditioning  self_cond_estimate_kernel<PRED> (the first pass's clamped x0 estimate) and draw_self_cond_kernel:
+//                   siblings, behind the distillation pair; its stacking is stack_views_cfg_kernel<true>, above.
+//   learned variance  sampler_step_lv_kernel<CFG, RNG> (the few-step tail with a per-pixel noise scale; it rounds the guided
+//                   combination and the base otherwise than sampler_step_kernel and has no history term, so it stays a
+//                   sibling), behind the self-conditioning kernels; the hybrid loss is the loss family's LV switch, above.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
-//                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The five
-//                   vf_compose_loss_* entries likewise forward to loss_fwd / loss_bwd; loss_kernels turns the run-time
-//                   (penalty, pred) into the instantiation.
+//                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The seven
+//                   vf_compose_loss_* entries (the two _lv_ ones among them) likewise forward to loss_fwd / loss_bwd;
+//                   loss_kernels<LV> turns the run-time (penalty, pred) into the instantiation.
 // With every option off a path runs the launches and the bits it ran before the option existed.
 //
 // Classifier-free guidance (Ho & Salimans, "Classifier-Free Diffusion Guidance").  This comment is the ONE written
@@ -148,11 +151,12 @@
 //   memory: a captured phase replays for every step.  No EPS / threshold / rescale flavour.
 //
 // Self-conditioning (Chen et al., "Analog Bits", 2.2): the network is also shown its own previous estimate of the clean
-// image.  This comment is the ONE written definition; tests/selfcond_ref.py restates it.  Opt-in: three sibling kernels
-// (stack_views_sc_kernel, self_cond_estimate_kernel<PRED>, draw_self_cond_kernel), everything above is untouched.
+// image.  This comment is the ONE written definition; tests/selfcond_ref.py restates it.  Opt-in: the SC instantiation of
+// the guided stacking kernel (stack_views_cfg_kernel<true>) and two sibling kernels (self_cond_estimate_kernel<PRED>,
+// draw_self_cond_kernel); every path without it runs the code it ran before.
 //   Input.  UNet(in_channel = Cc + 6): row v of sample b is [ cond (Cc) | noisy target (3) | sc_b (3) ], Cc = 3 or 6 as
 //     before; sc_b is the same in all the sample's rows; under guidance the null row S + b is [ 0 | y_b | sc_b ];
-//     sc_b = 0 means "no estimate".  The first Cc + 3 channels are stack_views_cfg_kernel's expressions.
+//     sc_b = 0 means "no estimate".  The first Cc + 3 channels are stack_views_cfg_kernel<false>'s expressions.
 //   Estimate (training; g = level[b], the sample's continuous level; out_b = the composition over the sample's views of
 //     channels 0..2 under weighting_train: compose4, softmax of channels 3..5 or the mean):
 //       x^_b = keep_b clamp(a(g) y_t - b(g) out_b, -1, 1)
@@ -178,8 +182,9 @@
 // Learned variance (Nichol & Dhariwal, "Improved DDPM", 3.1 and 4): the network also predicts, per pixel, where between
 // log beta~ and log beta the log-variance of a reverse step lies, and is trained with L_simple + lambda L_vlb.  This
 // comment is the ONE written definition (the arithmetic, operation by operation: vlb.h); tests/vlb_ref.py restates it.
-// Opt-in: sibling kernels (compose_loss_lv_fwd / _finish / _bwd, sampler_step_lv_kernel<CFG, RNG>), everything above is
-// untouched.
+// Opt-in: the LV instantiations of the loss family (compose_loss_fwd_kernel / _bwd_kernel<PEN, PRED, true>, the vlb
+// operands of compose_loss_finish_kernel) and a sibling tail (sampler_step_lv_kernel<CFG, RNG>); every path without it runs
+// the code it ran before.
 //   Network.  UNet(out_channel = 9): channels 0..2 the prediction (eps, v or x0) and 3..5 the view logits as before, 6..8
 //     the raw variance output o.  o_b = the composition over the sample's real views of channels 6..8 under the weights of
 //     channels 0..2 (the softmax of 3..5, or the mean).  v = 0.5 o_b + 0.5, unconstrained;  lp = v hi + (1 - v) lo, every
@@ -261,16 +266,19 @@ __global__ void stack_views_kernel(const float4* __restrict__ y_cond, const floa
     }
 }
 
-// stack_views_kernel with conditioning dropout and null rows (classifier-free guidance, see the head of this file).
+// stack_views_kernel with conditioning dropout and null rows (classifier-free guidance, see the head of this file), and
+// with SC the third part of self-conditioning: row v = [ cond (nc4) | target (n4) | sc_b (n4) ], sc (B,3,HW) | null = zeros.
 // drop (uint8[B] | null): the conditioning half of every row of a sample with drop[b] != 0 is zeros; y_cond is not read
-// for it.  grid (chunks, rows): rows = S, or S + B with null rows -- row S + b is [ 0 | y_t[b] ] with level[b], angle[b].
-// The target half is stack_views_kernel's expression, so equal inputs give equal bits.
+// for it.  grid (chunks, rows): rows = S, or S + B with null rows -- row S + b is [ 0 | y_t[b] (| sc_b) ] with level[b],
+// angle[b].  The target half is stack_views_kernel's expression, so equal inputs give equal bits, with or without SC.
+// copy_cond == 0 rewrites the target (and sc) part only (the per-step re-stack of generate).
+template <bool SC>
 __global__ void stack_views_cfg_kernel(const float4* __restrict__ y_cond, const float4* __restrict__ y_t,
                                        const float4* __restrict__ noise, const float* __restrict__ level,
                                        const float* __restrict__ angle, const int* __restrict__ off,
                                        const unsigned char* __restrict__ drop, float4* __restrict__ x,
                                        float* __restrict__ level_s, float* __restrict__ angle_s, int B, int Nmax, int nc4,
-                                       int n4, int copy_cond, int S) {
+                                       int n4, int copy_cond, int S, const float4* __restrict__ sc) {
     const int v = blockIdx.y;
     const bool null_row = v >= S;
     const int b = null_row ? v - S : sample_of_view(off, B, v);
@@ -285,7 +293,8 @@ __global__ void stack_views_cfg_kernel(const float4* __restrict__ y_cond, const 
     const float4* c = y_cond + ((size_t)b * Nmax + j) * nc4;
     const float4* t = y_t + (size_t)b * n4;
     const float4* z = noise ? noise + (size_t)b * n4 : nullptr;
-    float4* o = x + (size_t)v * (nc4 + n4);
+    const float4* s = SC && sc ? sc + (size_t)b * n4 : nullptr;
+    float4* o = SC ? x + (size_t)v * (nc4 + 2 * (size_t)n4) : x + (size_t)v * (nc4 + n4);
     if (copy_cond) {
         if (zero)
             for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x)
@@ -303,6 +312,7 @@ __global__ void stack_views_cfg_kernel(const float4* __restrict__ y_cond, const 
             y.w = sa * y.w + sb * e.w;
         }
         o[nc4 + i] = y;
+        if constexpr (SC) o[nc4 + n4 + i] = s ? s[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 
@@ -831,10 +841,69 @@ __device__ __forceinline__ float4 pred_target4(const float* __restrict__ noise, 
                        __builtin_fmaf(sa, n.z, -mul_rn(sb, y.z)), __builtin_fmaf(sa, n.w, -mul_rn(sb, y.w)));
 }
 
+// ---- learned variance inside the family (the head of this file holds the definition, vlb.h the arithmetic) ----
+// o_b of one float4 (c, p): channel 6 + c composed under the weights of channel c -- the softmax of channel 3 + c with
+// the (mx, inv) compose4 handed back, or the mean.
+__device__ __forceinline__ float4 compose4_var(const float* __restrict__ out, int Cout, int HW, int v0, int v1, int c,
+                                               int p, int weighting, const float4& mx, const float4& inv) {
+    const size_t vs = (size_t)Cout * HW;
+    const float* l0 = out + (size_t)v0 * vs + (size_t)(3 + c) * HW + p;
+    const float* o0 = l0 + (size_t)3 * HW;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!weighting) {
+        for (int v = v0; v < v1; ++v) {
+            const float4 o = *reinterpret_cast<const float4*>(o0 + (size_t)(v - v0) * vs);
+            acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
+        }
+        const float n = 1.0f / (float)(v1 - v0);
+        return make_float4(acc.x * n, acc.y * n, acc.z * n, acc.w * n);
+    }
+    for (int v = v0; v < v1; ++v) {
+        const float4 l = *reinterpret_cast<const float4*>(l0 + (size_t)(v - v0) * vs);
+        const float4 o = *reinterpret_cast<const float4*>(o0 + (size_t)(v - v0) * vs);
+        acc.x += expf(l.x - mx.x) * o.x; acc.y += expf(l.y - mx.y) * o.y;
+        acc.z += expf(l.z - mx.z) * o.z; acc.w += expf(l.w - mx.w) * o.w;
+    }
+    return make_float4(acc.x * inv.x, acc.y * inv.y, acc.z * inv.z, acc.w * inv.w);
+}
+
+// What only the LV instantiations read, handed over by value behind the family's own operands: t (int64 [B]), the fp32
+// tables c1, hi, lo [T] and the weight of the vlb term.  The others take it empty and do not look at it.
+struct VlbArgs {
+    const long long* t;
+    const float *c1, *hi, *lo;
+    int T;
+    float lambda;
+};
+
+// The operands of the three kernels that exist with LV alone, by value at the END of the argument list.  Without LV the
+// struct is empty: the argument list, and so the code, of those instantiations is what it was before the switch existed
+// (a run-time null check in the finish kernel and 56 / 48 unused kernarg bytes in the other two were measured: the non-LV
+// forward + backward pairs came out 1 - 1.7 % slower; profiles/loss_lv_templates.md).
+template <bool LV> struct VlbFwd {};
+template <> struct VlbFwd<true> { VlbArgs vlb; float* var_hat; float* vlb_part; };
+template <bool LV> struct VlbBwd {};
+template <> struct VlbBwd<true> { VlbArgs vlb; const float* var_hat; };
+template <bool LV> struct VlbFinish {};
+template <> struct VlbFinish<true> { const float* vlb_part; float* sample_vlb; float lambda; };
+
+// What a workgroup of the hybrid loss knows about its sample: the tables at t[b] (clamped into [0, T - 1] before any
+// table is read) and kappa^2 of its level.
+struct VlbSample {
+    float c1, hi, lo, k2;
+};
+template <int PRED>
+__device__ __forceinline__ VlbSample vlb_sample(const VlbArgs& a, float g) {
+    long long tb = a.t[blockIdx.y];
+    tb = tb < 0 ? 0 : (tb > a.T - 1 ? a.T - 1 : tb);
+    return VlbSample{a.c1[tb], a.hi[tb], a.lo[tb], vf_vlb_kappa2(PRED, g)};
+}
+
 // compose_fwd_kernel with a penalty and a prediction: the same composition and the same (b, chunk) partial sums, of
 // rho(noise_hat - target).  noise_hat receives the composed output in the network's own parameterisation (what the
-// backward kernel reads back).
-template <int PEN, int PRED>
+// backward kernel reads back).  LV: plus the variance channels -- next to those partial sums the partial sums of
+// KL(r, o_b) in bits, on the same residual r, and var_hat receives the composed o_b.
+template <int PEN, int PRED, bool LV>
 __global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __restrict__ out,
                                                                const int* __restrict__ off,
                                                                const float* __restrict__ noise,
@@ -842,28 +911,44 @@ __global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __re
                                                                const float* __restrict__ level,
                                                                float* __restrict__ noise_hat,
                                                                float* __restrict__ loss_part, int Cout, int HW,
-                                                               int weighting, float delta) {
+                                                               int weighting, float delta, VlbFwd<LV> vo) {
     __shared__ float red[4];
     const int b = blockIdx.y;
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
-    float sa = 0.f, sb = 0.f;
-    if (PRED != VF_PRED_EPS) {
-        const float g = level[b];
-        sa = sqrtf(g), sb = sqrtf(1.0f - g);
-    }
-    float acc = 0.f;
+    float g = 0.f, sa = 0.f, sb = 0.f;
+    if (LV || PRED != VF_PRED_EPS) g = level[b];
+    if (PRED != VF_PRED_EPS) sa = sqrtf(g), sb = sqrtf(1.0f - g);
+    VlbSample s{};
+    if constexpr (LV) s = vlb_sample<PRED>(vo.vlb, g);
+    float acc = 0.f, kl = 0.f;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
+        float4 mx = make_float4(0.f, 0.f, 0.f, 0.f), inv = mx, ob = mx;
+        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, LV ? &mx : nullptr, LV ? &inv : nullptr);
+        if constexpr (LV) ob = compose4_var(out, Cout, HW, v0, v1, c, p, weighting, mx, inv);
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
         *reinterpret_cast<float4*>(noise_hat + o) = nh;
+        if constexpr (LV) *reinterpret_cast<float4*>(vo.var_hat + o) = ob;
         const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
-        acc += (vf_loss_rho<PEN>(nh.x - t.x, delta) + vf_loss_rho<PEN>(nh.y - t.y, delta)) +
-               (vf_loss_rho<PEN>(nh.z - t.z, delta) + vf_loss_rho<PEN>(nh.w - t.w, delta));
+        const float r[4] = {nh.x - t.x, nh.y - t.y, nh.z - t.z, nh.w - t.w};
+        acc += (vf_loss_rho<PEN>(r[0], delta) + vf_loss_rho<PEN>(r[1], delta)) +
+               (vf_loss_rho<PEN>(r[2], delta) + vf_loss_rho<PEN>(r[3], delta));
+        if constexpr (LV) {
+            const float os[4] = {ob.x, ob.y, ob.z, ob.w};
+            float k[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                k[j] = vf_vlb_kl(vf_vlb_logvar(os[j], s.hi, s.lo), s.lo, vf_vlb_m2(s.c1, s.k2, r[j]));
+            kl += (k[0] + k[1]) + (k[2] + k[3]);
+        }
     }
     acc = block_sum<256>(acc, red);
-    if (threadIdx.x == 0) loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+    if constexpr (LV) kl = block_sum<256>(kl, red);
+    if (threadIdx.x == 0) {
+        loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+        if constexpr (LV) vo.vlb_part[blockIdx.y * gridDim.x + blockIdx.x] = kl;
+    }
 }
 
 // One workgroup.  Per sample (one thread each): s_b = its `ch` partials in index order / n, w_b = the native weight of
@@ -871,8 +956,12 @@ __global__ __launch_bounds__(256) void compose_loss_fwd_kernel(const float* __re
 // index order (one thread); then, with a histogram attached, one thread per bin walks the samples in index order and adds
 // the UNWEIGHTED s_b of its own bin into the persistent accumulators.  scale (nullable; the importance weight of a
 // level-sampler draw): with it sample_w holds 2 B floats -- w_s scale[s], what the loss and the backward kernel use, then
-// w_s alone, what level_stats_kernel reads; without, B floats.  Every address is written by exactly one thread: no
-// atomics, the same bits on every run.
+// w_s alone, what level_stats_kernel reads; without, B floats.  LV (vlb_part, sample_vlb and lambda in `vo`; never
+// with scale: a level sampler is refused with a learned variance): sample_vlb[s] = its `ch` partials in index order / n,
+// and loss = sum_s sample_w[s] sample_loss[s] / B + lambda sum_s sample_vlb[s] / B, each sum in index order by one
+// thread; the histogram stays L_simple's alone.  Every address is written by exactly one thread: no atomics, the same
+// bits on every run.
+template <bool LV>
 __global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __restrict__ part,
                                                                  const float* __restrict__ level,
                                                                  const float* __restrict__ scale,
@@ -880,13 +969,18 @@ __global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __
                                                                  float* __restrict__ sample_w, float* __restrict__ loss,
                                                                  float* __restrict__ bin_sum, int* __restrict__ bin_cnt,
                                                                  int B, int ch, int K, float inv_n, int kind, float a,
-                                                                 float b, int pred) {
+                                                                 float b, int pred, VlbFinish<LV> vo) {
     for (int s = threadIdx.x; s < B; s += 64) {
         float acc = 0.f;
         for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
         sample_loss[s] = acc * inv_n;
+        if constexpr (LV) {
+            float kl = 0.f;
+            for (int c = 0; c < ch; ++c) kl += vo.vlb_part[s * ch + c];
+            vo.sample_vlb[s] = kl * inv_n;
+        }
         const float w = vf_loss_weight_pred(pred, kind, a, b, level[s]);
-        if (scale != nullptr) {
+        if (!LV && scale != nullptr) {      // (never both: the LV instantiation holds no scale path)
             sample_w[s] = w * scale[s];
             sample_w[B + s] = w;
         } else {
@@ -897,7 +991,13 @@ __global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __
     if (threadIdx.x == 0) {
         float acc = 0.f;
         for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
-        *loss = acc / (float)B;
+        if constexpr (LV) {
+            float kl = 0.f;
+            for (int s = 0; s < B; ++s) kl += vo.sample_vlb[s];
+            *loss = acc / (float)B + vo.lambda * (kl / (float)B);
+        } else {
+            *loss = acc / (float)B;
+        }
     }
     if (bin_sum == nullptr) return;
     for (int k = threadIdx.x; k < K; k += 64) {
@@ -919,7 +1019,13 @@ __global__ __launch_bounds__(64) void compose_loss_finish_kernel(const float* __
 // compose_mse_bwd_kernel with a penalty and a prediction: the forward kernel's target formed again, g = gloss
 // sample_w[b] rho'(noise_hat - target) / (n B), then the same softmax / mean chain rule (d eps_v = w_v g;
 // d logit_v = w_v (eps_v - nh) g;  mean ablation: d eps_v = g / count, logits zero).
-template <int PEN, int PRED>
+// LV: into nine channels.  g stays L_simple's gradient on the composed prediction; gv = gloss lambda / (n B) dKL/dlp
+// 0.5 (hi - lo) is the vlb term's gradient on o_b, with the residual a constant.  Then
+//   channels 0..2  w_v g                                     (mean: g / count)
+//   channels 3..5  w_v (e_v - nh) g + w_v (o_v - o_b) gv     (mean: 0)
+//   channels 6..8  w_v gv                                    (mean: gv / count)
+// every address of dout's nine channels written exactly once.
+template <int PEN, int PRED, bool LV>
 __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __restrict__ out,
                                                                const int* __restrict__ off,
                                                                const float* __restrict__ noise,
@@ -929,32 +1035,55 @@ __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __re
                                                                const float* __restrict__ gloss,
                                                                const float* __restrict__ sample_w,
                                                                float* __restrict__ dout, int Cout, int HW,
-                                                               int weighting, float inv_nb, float delta) {
+                                                               int weighting, float inv_nb, float delta, VlbBwd<LV> vo) {
     const int b = blockIdx.y;
     const int v0 = off[b], v1 = off[b + 1];
     const int n4 = 3 * HW / 4;
     const float gs = gloss[0] * sample_w[b] * inv_nb;
-    float sa = 0.f, sb = 0.f;
-    if (PRED != VF_PRED_EPS) {
-        const float lv = level[b];
-        sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
+    float g_b = 0.f, sa = 0.f, sb = 0.f;
+    if (LV || PRED != VF_PRED_EPS) g_b = level[b];
+    if (PRED != VF_PRED_EPS) sa = sqrtf(g_b), sb = sqrtf(1.0f - g_b);
+    VlbSample s{};
+    float gvs = 0.f;
+    if constexpr (LV) {
+        s = vlb_sample<PRED>(vo.vlb, g_b);
+        gvs = gloss[0] * vo.vlb.lambda * inv_nb * (0.5f * (s.hi - s.lo));
     }
     const size_t vs = (size_t)Cout * HW;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
         const int c = (4 * i) / HW, p = 4 * i - c * HW;
         const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
         const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
+        float4 ob = make_float4(0.f, 0.f, 0.f, 0.f), gv = ob;
+        if constexpr (LV) ob = *reinterpret_cast<const float4*>(vo.var_hat + o);
         const float4 t = pred_target4<PRED>(noise, y_0, o, sa, sb);
-        const float4 g = make_float4(gs * vf_loss_drho<PEN>(nh.x - t.x, delta), gs * vf_loss_drho<PEN>(nh.y - t.y, delta),
-                                     gs * vf_loss_drho<PEN>(nh.z - t.z, delta), gs * vf_loss_drho<PEN>(nh.w - t.w, delta));
+        const float r[4] = {nh.x - t.x, nh.y - t.y, nh.z - t.z, nh.w - t.w};
+        const float4 g = make_float4(gs * vf_loss_drho<PEN>(r[0], delta), gs * vf_loss_drho<PEN>(r[1], delta),
+                                     gs * vf_loss_drho<PEN>(r[2], delta), gs * vf_loss_drho<PEN>(r[3], delta));
+        if constexpr (LV) {
+            const float os[4] = {ob.x, ob.y, ob.z, ob.w};
+            float gk[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                gk[j] = gvs * vf_vlb_dkl(vf_vlb_logvar(os[j], s.hi, s.lo), s.lo, vf_vlb_m2(s.c1, s.k2, r[j]));
+            gv = make_float4(gk[0], gk[1], gk[2], gk[3]);
+        }
         if (!weighting) {
             const float inv = 1.0f / (float)(v1 - v0);
             const float4 d = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
+            const float4 dv = make_float4(gv.x * inv, gv.y * inv, gv.z * inv, gv.w * inv);
             for (int v = v0; v < v1; ++v) {
-                *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)c * HW + p) = d;
-                if (Cout > 3)
-                    *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)(3 + c) * HW + p) =
-                        make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (LV) {
+                    float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
+                    *reinterpret_cast<float4*>(dp) = d;
+                    *reinterpret_cast<float4*>(dp + (size_t)3 * HW) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    *reinterpret_cast<float4*>(dp + (size_t)6 * HW) = dv;
+                } else {            // (written out: behind a shared base pointer these instantiations' code changes)
+                    *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)c * HW + p) = d;
+                    if (Cout > 3)
+                        *reinterpret_cast<float4*>(dout + (size_t)v * vs + (size_t)(3 + c) * HW + p) =
+                            make_float4(0.f, 0.f, 0.f, 0.f);
+                }
             }
             continue;
         }
@@ -968,9 +1097,19 @@ __global__ __launch_bounds__(256) void compose_loss_bwd_kernel(const float* __re
                                          expf(l.w - mx.w) * inv.w);
             float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
             *reinterpret_cast<float4*>(dp) = make_float4(w.x * g.x, w.y * g.y, w.z * g.z, w.w * g.w);
-            *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
-                make_float4(w.x * (e.x - nh.x) * g.x, w.y * (e.y - nh.y) * g.y, w.z * (e.z - nh.z) * g.z,
-                            w.w * (e.w - nh.w) * g.w);
+            if constexpr (LV) {
+                const float4 q = *reinterpret_cast<const float4*>(ep + (size_t)6 * HW);
+                *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
+                    make_float4(w.x * (e.x - nh.x) * g.x + w.x * (q.x - ob.x) * gv.x,
+                                w.y * (e.y - nh.y) * g.y + w.y * (q.y - ob.y) * gv.y,
+                                w.z * (e.z - nh.z) * g.z + w.z * (q.z - ob.z) * gv.z,
+                                w.w * (e.w - nh.w) * g.w + w.w * (q.w - ob.w) * gv.w);
+                *reinterpret_cast<float4*>(dp + (size_t)6 * HW) = make_float4(w.x * gv.x, w.y * gv.y, w.z * gv.z, w.w * gv.w);
+            } else {
+                *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
+                    make_float4(w.x * (e.x - nh.x) * g.x, w.y * (e.y - nh.y) * g.y, w.z * (e.z - nh.z) * g.z,
+                                w.w * (e.w - nh.w) * g.w);
+            }
         }
     }
 }
@@ -1411,52 +1550,6 @@ __global__ __launch_bounds__(256) void distill_target_kernel(
 }
 
 // ---- self-conditioning (the head of this file) ----
-// stack_views_cfg_kernel plus the third part: row v = [ cond (nc4) | target (n4) | sc_b (n4) ], sc (B,3,HW) | null = zeros.
-// grid (chunks, rows), rows = S or S + B; the first two parts are that kernel's expressions, so equal inputs give equal
-// bits.  copy_cond == 0 rewrites the target and sc parts only (the per-step re-stack of generate).
-__global__ void stack_views_sc_kernel(const float4* __restrict__ y_cond, const float4* __restrict__ y_t,
-                                      const float4* __restrict__ noise, const float* __restrict__ level,
-                                      const float* __restrict__ angle, const int* __restrict__ off,
-                                      const unsigned char* __restrict__ drop, const float4* __restrict__ sc,
-                                      float4* __restrict__ x, float* __restrict__ level_s, float* __restrict__ angle_s,
-                                      int B, int Nmax, int nc4, int n4, int copy_cond, int S) {
-    const int v = blockIdx.y;
-    const bool null_row = v >= S;
-    const int b = null_row ? v - S : sample_of_view(off, B, v);
-    const int j = null_row ? 0 : v - off[b];
-    const bool zero = null_row || (drop != nullptr && drop[b] != 0);
-    const float lv = level[b];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        level_s[v] = lv;
-        angle_s[v] = angle[b];
-    }
-    const float sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
-    const float4* c = y_cond + ((size_t)b * Nmax + j) * nc4;
-    const float4* t = y_t + (size_t)b * n4;
-    const float4* z = noise ? noise + (size_t)b * n4 : nullptr;
-    const float4* s = sc ? sc + (size_t)b * n4 : nullptr;
-    float4* o = x + (size_t)v * (nc4 + 2 * (size_t)n4);
-    if (copy_cond) {
-        if (zero)
-            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x)
-                o[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        else
-            for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < nc4; i += gridDim.x * blockDim.x) o[i] = c[i];
-    }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += gridDim.x * blockDim.x) {
-        float4 y = t[i];
-        if (z) {
-            const float4 e = z[i];
-            y.x = sa * y.x + sb * e.x;
-            y.y = sa * y.y + sb * e.y;
-            y.z = sa * y.z + sb * e.z;
-            y.w = sa * y.w + sb * e.w;
-        }
-        o[nc4 + i] = y;
-        o[nc4 + n4 + i] = s ? s[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-}
-
 // keep[b] = the self-conditioning coin of sample ids[b] (rng.h: word 3 of the training-scalar call against thr)
 __global__ void draw_self_cond_kernel(unsigned long long seed, const long long* __restrict__ ids, unsigned thr,
                                       unsigned char* __restrict__ keep, int B) {
@@ -1520,204 +1613,8 @@ __global__ __launch_bounds__(256) void self_cond_estimate_kernel(
     }
 }
 
-// ---- learned variance (the head of this file holds the definition, vlb.h the arithmetic) ----
-// o_b of one float4 (c, p): channel 6 + c composed under the weights of channel c -- the softmax of channel 3 + c with
-// the (mx, inv) compose4 handed back, or the mean.
-__device__ __forceinline__ float4 compose4_var(const float* __restrict__ out, int Cout, int HW, int v0, int v1, int c,
-                                               int p, int weighting, const float4& mx, const float4& inv) {
-    const size_t vs = (size_t)Cout * HW;
-    const float* l0 = out + (size_t)v0 * vs + (size_t)(3 + c) * HW + p;
-    const float* o0 = l0 + (size_t)3 * HW;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!weighting) {
-        for (int v = v0; v < v1; ++v) {
-            const float4 o = *reinterpret_cast<const float4*>(o0 + (size_t)(v - v0) * vs);
-            acc.x += o.x; acc.y += o.y; acc.z += o.z; acc.w += o.w;
-        }
-        const float n = 1.0f / (float)(v1 - v0);
-        return make_float4(acc.x * n, acc.y * n, acc.z * n, acc.w * n);
-    }
-    for (int v = v0; v < v1; ++v) {
-        const float4 l = *reinterpret_cast<const float4*>(l0 + (size_t)(v - v0) * vs);
-        const float4 o = *reinterpret_cast<const float4*>(o0 + (size_t)(v - v0) * vs);
-        acc.x += expf(l.x - mx.x) * o.x; acc.y += expf(l.y - mx.y) * o.y;
-        acc.z += expf(l.z - mx.z) * o.z; acc.w += expf(l.w - mx.w) * o.w;
-    }
-    return make_float4(acc.x * inv.x, acc.y * inv.y, acc.z * inv.z, acc.w * inv.w);
-}
-
-// What a workgroup of the hybrid loss knows about its sample: the tables at t[b] (clamped into [0, T - 1] before any
-// table is read) and kappa^2 of its level.
-struct VlbSample {
-    float c1, hi, lo, k2;
-};
-template <int PRED>
-__device__ __forceinline__ VlbSample vlb_sample(const long long* __restrict__ t, const float* __restrict__ tc1,
-                                                const float* __restrict__ thi, const float* __restrict__ tlo, int T,
-                                                float g) {
-    long long tb = t[blockIdx.y];
-    tb = tb < 0 ? 0 : (tb > T - 1 ? T - 1 : tb);
-    return VlbSample{tc1[tb], thi[tb], tlo[tb], vf_vlb_kappa2(PRED, g)};
-}
-
-// compose_loss_fwd_kernel plus the variance channels: the same composition, residual and (b, chunk) partial sums of
-// rho(r), and next to them the partial sums of KL(r, o_b) in bits.  noise_hat and var_hat receive the composed prediction
-// and the composed o_b (what the backward kernel reads back).
-template <int PEN, int PRED>
-__global__ __launch_bounds__(256) void compose_loss_lv_fwd_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ noise,
-    const float* __restrict__ y_0, const float* __restrict__ level, const long long* __restrict__ t,
-    const float* __restrict__ tc1, const float* __restrict__ thi, const float* __restrict__ tlo,
-    float* __restrict__ noise_hat, float* __restrict__ var_hat, float* __restrict__ loss_part,
-    float* __restrict__ vlb_part, int Cout, int HW, int weighting, float delta, int T) {
-    __shared__ float red[4];
-    const int b = blockIdx.y;
-    const int v0 = off[b], v1 = off[b + 1];
-    const int n4 = 3 * HW / 4;
-    const float g = level[b];
-    float sa = 0.f, sb = 0.f;
-    if (PRED != VF_PRED_EPS) sa = sqrtf(g), sb = sqrtf(1.0f - g);
-    const VlbSample s = vlb_sample<PRED>(t, tc1, thi, tlo, T, g);
-    float acc = 0.f, kl = 0.f;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        float4 mx = make_float4(0.f, 0.f, 0.f, 0.f), inv = mx;
-        const float4 nh = compose4(out, Cout, HW, v0, v1, c, p, weighting, &mx, &inv);
-        const float4 ob = compose4_var(out, Cout, HW, v0, v1, c, p, weighting, mx, inv);
-        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
-        *reinterpret_cast<float4*>(noise_hat + o) = nh;
-        *reinterpret_cast<float4*>(var_hat + o) = ob;
-        const float4 tg = pred_target4<PRED>(noise, y_0, o, sa, sb);
-        const float r[4] = {nh.x - tg.x, nh.y - tg.y, nh.z - tg.z, nh.w - tg.w};
-        const float os[4] = {ob.x, ob.y, ob.z, ob.w};
-        acc += (vf_loss_rho<PEN>(r[0], delta) + vf_loss_rho<PEN>(r[1], delta)) +
-               (vf_loss_rho<PEN>(r[2], delta) + vf_loss_rho<PEN>(r[3], delta));
-        float k[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            k[j] = vf_vlb_kl(vf_vlb_logvar(os[j], s.hi, s.lo), s.lo, vf_vlb_m2(s.c1, s.k2, r[j]));
-        kl += (k[0] + k[1]) + (k[2] + k[3]);
-    }
-    acc = block_sum<256>(acc, red);
-    kl = block_sum<256>(kl, red);
-    if (threadIdx.x == 0) {
-        loss_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
-        vlb_part[blockIdx.y * gridDim.x + blockIdx.x] = kl;
-    }
-}
-
-// compose_loss_finish_kernel with the vlb term and without a per-sample scale (a level sampler is refused with a
-// learned variance): sample_vlb[s] = its `ch` partials in index order / n; loss = sum_s sample_w[s] sample_loss[s] / B +
-// lambda sum_s sample_vlb[s] / B, each sum in index order by one thread.  The histogram is the family's: L_simple alone.
-__global__ __launch_bounds__(64) void compose_loss_lv_finish_kernel(
-    const float* __restrict__ part, const float* __restrict__ vlb_part, const float* __restrict__ level,
-    float* __restrict__ sample_loss, float* __restrict__ sample_w, float* __restrict__ sample_vlb,
-    float* __restrict__ loss, float* __restrict__ bin_sum, int* __restrict__ bin_cnt, int B, int ch, int K, float inv_n,
-    int kind, float a, float b, int pred, float lambda) {
-    for (int s = threadIdx.x; s < B; s += 64) {
-        float acc = 0.f, kl = 0.f;
-        for (int c = 0; c < ch; ++c) acc += part[s * ch + c];
-        for (int c = 0; c < ch; ++c) kl += vlb_part[s * ch + c];
-        sample_loss[s] = acc * inv_n;
-        sample_vlb[s] = kl * inv_n;
-        sample_w[s] = vf_loss_weight_pred(pred, kind, a, b, level[s]);
-    }
-    __syncthreads();                        // (also makes the workgroup's global stores above visible to it)
-    if (threadIdx.x == 0) {
-        float acc = 0.f, kl = 0.f;
-        for (int s = 0; s < B; ++s) acc += sample_w[s] * sample_loss[s];
-        for (int s = 0; s < B; ++s) kl += sample_vlb[s];
-        *loss = acc / (float)B + lambda * (kl / (float)B);
-    }
-    if (bin_sum == nullptr) return;
-    for (int k = threadIdx.x; k < K; k += 64) {
-        float sum = 0.f;
-        int cnt = 0;
-        for (int s = 0; s < B; ++s) {
-            int bin = (int)(level[s] * (float)K);
-            bin = bin > K - 1 ? K - 1 : bin;
-            if (bin == k) {
-                sum += sample_loss[s];
-                ++cnt;
-            }
-        }
-        bin_sum[k] += sum;
-        bin_cnt[k] += cnt;
-    }
-}
-
-// compose_loss_bwd_kernel into nine channels.  g: L_simple's gradient on the composed prediction, the family's expression;
-// gv = gloss lambda / (n B) dKL/dlp 0.5 (hi - lo): the vlb term's gradient on o_b, with the residual a constant.  Then
-//   channels 0..2  w_v g                                     (mean: g / count)
-//   channels 3..5  w_v (e_v - nh) g + w_v (o_v - o_b) gv     (mean: 0)
-//   channels 6..8  w_v gv                                    (mean: gv / count)
-// every address of dout's nine channels written exactly once.
-template <int PEN, int PRED>
-__global__ __launch_bounds__(256) void compose_loss_lv_bwd_kernel(
-    const float* __restrict__ out, const int* __restrict__ off, const float* __restrict__ noise,
-    const float* __restrict__ y_0, const float* __restrict__ level, const long long* __restrict__ t,
-    const float* __restrict__ tc1, const float* __restrict__ thi, const float* __restrict__ tlo,
-    const float* __restrict__ noise_hat, const float* __restrict__ var_hat, const float* __restrict__ gloss,
-    const float* __restrict__ sample_w, float* __restrict__ dout, int Cout, int HW, int weighting, float inv_nb,
-    float delta, int T, float lambda) {
-    const int b = blockIdx.y;
-    const int v0 = off[b], v1 = off[b + 1];
-    const int n4 = 3 * HW / 4;
-    const float gs = gloss[0] * sample_w[b] * inv_nb;
-    const float lv = level[b];
-    float sa = 0.f, sb = 0.f;
-    if (PRED != VF_PRED_EPS) sa = sqrtf(lv), sb = sqrtf(1.0f - lv);
-    const VlbSample s = vlb_sample<PRED>(t, tc1, thi, tlo, T, lv);
-    const float gvs = gloss[0] * lambda * inv_nb * (0.5f * (s.hi - s.lo));
-    const size_t vs = (size_t)Cout * HW;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const int c = (4 * i) / HW, p = 4 * i - c * HW;
-        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
-        const float4 nh = *reinterpret_cast<const float4*>(noise_hat + o);
-        const float4 ob = *reinterpret_cast<const float4*>(var_hat + o);
-        const float4 tg = pred_target4<PRED>(noise, y_0, o, sa, sb);
-        const float r[4] = {nh.x - tg.x, nh.y - tg.y, nh.z - tg.z, nh.w - tg.w};
-        const float os[4] = {ob.x, ob.y, ob.z, ob.w};
-        const float4 g = make_float4(gs * vf_loss_drho<PEN>(r[0], delta), gs * vf_loss_drho<PEN>(r[1], delta),
-                                     gs * vf_loss_drho<PEN>(r[2], delta), gs * vf_loss_drho<PEN>(r[3], delta));
-        float gk[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            gk[j] = gvs * vf_vlb_dkl(vf_vlb_logvar(os[j], s.hi, s.lo), s.lo, vf_vlb_m2(s.c1, s.k2, r[j]));
-        const float4 gv = make_float4(gk[0], gk[1], gk[2], gk[3]);
-        if (!weighting) {
-            const float inv = 1.0f / (float)(v1 - v0);
-            const float4 d = make_float4(g.x * inv, g.y * inv, g.z * inv, g.w * inv);
-            const float4 dv = make_float4(gv.x * inv, gv.y * inv, gv.z * inv, gv.w * inv);
-            for (int v = v0; v < v1; ++v) {
-                float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
-                *reinterpret_cast<float4*>(dp) = d;
-                *reinterpret_cast<float4*>(dp + (size_t)3 * HW) = make_float4(0.f, 0.f, 0.f, 0.f);
-                *reinterpret_cast<float4*>(dp + (size_t)6 * HW) = dv;
-            }
-            continue;
-        }
-        float4 mx, inv;
-        (void)compose4(out, Cout, HW, v0, v1, c, p, 1, &mx, &inv);
-        for (int v = v0; v < v1; ++v) {
-            const float* ep = out + (size_t)v * vs + (size_t)c * HW + p;
-            const float4 e = *reinterpret_cast<const float4*>(ep);
-            const float4 l = *reinterpret_cast<const float4*>(ep + (size_t)3 * HW);
-            const float4 q = *reinterpret_cast<const float4*>(ep + (size_t)6 * HW);
-            const float4 w = make_float4(expf(l.x - mx.x) * inv.x, expf(l.y - mx.y) * inv.y, expf(l.z - mx.z) * inv.z,
-                                         expf(l.w - mx.w) * inv.w);
-            float* dp = dout + (size_t)v * vs + (size_t)c * HW + p;
-            *reinterpret_cast<float4*>(dp) = make_float4(w.x * g.x, w.y * g.y, w.z * g.z, w.w * g.w);
-            *reinterpret_cast<float4*>(dp + (size_t)3 * HW) =
-                make_float4(w.x * (e.x - nh.x) * g.x + w.x * (q.x - ob.x) * gv.x,
-                            w.y * (e.y - nh.y) * g.y + w.y * (q.y - ob.y) * gv.y,
-                            w.z * (e.z - nh.z) * g.z + w.z * (q.z - ob.z) * gv.z,
-                            w.w * (e.w - nh.w) * g.w + w.w * (q.w - ob.w) * gv.w);
-            *reinterpret_cast<float4*>(dp + (size_t)6 * HW) = make_float4(w.x * gv.x, w.y * gv.y, w.z * gv.z, w.w * gv.w);
-        }
-    }
-}
-
+// ---- learned variance (the head of this file): the few-step tail with a per-pixel noise scale; the hybrid loss is the
+// loss family's LV switch ----
 // sampler_step_kernel<CFG, false, RNG> on the "ddim", eta = 1 tables with a per-pixel noise scale: y0 and cy y + c0 y0
 // rounded as that kernel rounds them (y0_hat_as<false>, the guided combination and multistep_base as its instruction
 // stream has them), then, where sigma[k] != 0, r = fma(expf(0.5 lp), z, r) with lp from hi[k], lo[k] and o_b -- the
@@ -1775,27 +1672,6 @@ __global__ __launch_bounds__(256) void sampler_step_lv_kernel(
     }
 }
 
-// the run-time (penalty, pred) -> the hybrid loss's kernel pair, as loss_kernels below
-struct LossLvKernels {
-    decltype(&compose_loss_lv_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) fwd;
-    decltype(&compose_loss_lv_bwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) bwd;
-};
-
-template <int PRED>
-LossLvKernels loss_lv_kernels_of(int penalty) {
-    if (penalty == VF_LOSS_L1)
-        return {compose_loss_lv_fwd_kernel<VF_LOSS_L1, PRED>, compose_loss_lv_bwd_kernel<VF_LOSS_L1, PRED>};
-    if (penalty == VF_LOSS_HUBER)
-        return {compose_loss_lv_fwd_kernel<VF_LOSS_HUBER, PRED>, compose_loss_lv_bwd_kernel<VF_LOSS_HUBER, PRED>};
-    return {compose_loss_lv_fwd_kernel<VF_LOSS_MSE, PRED>, compose_loss_lv_bwd_kernel<VF_LOSS_MSE, PRED>};
-}
-
-LossLvKernels loss_lv_kernels(int penalty, int pred) {
-    if (pred == VF_PRED_V) return loss_lv_kernels_of<VF_PRED_V>(penalty);
-    if (pred == VF_PRED_X0) return loss_lv_kernels_of<VF_PRED_X0>(penalty);
-    return loss_lv_kernels_of<VF_PRED_EPS>(penalty);
-}
-
 // the one launcher of the learned-variance tail behind its four entry points; it holds the argument check
 template <bool CFG, bool RNG>
 int sampler_step_lv(const float* unet_out, const int* off, const float* y_t, const float* z, unsigned long long seed,
@@ -1813,26 +1689,29 @@ int sampler_step_lv(const float* unet_out, const int* off, const float* y_t, con
     VF_RETURN_LAST_ERROR();
 }
 
-// ---- the loss family: the run-time (penalty, pred) -> the kernel pair (the launchers stand with the entry points) ----
+// ---- the loss family: LV and the run-time (penalty, pred) -> the kernel pair (the launchers stand with the entry
+// points) ----
+template <bool LV>
 struct LossKernels {
-    decltype(&compose_loss_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) fwd;
-    decltype(&compose_loss_bwd_kernel<VF_LOSS_MSE, VF_PRED_EPS>) bwd;
+    decltype(&compose_loss_fwd_kernel<VF_LOSS_MSE, VF_PRED_EPS, LV>) fwd;
+    decltype(&compose_loss_bwd_kernel<VF_LOSS_MSE, VF_PRED_EPS, LV>) bwd;
 };
 
-template <int PRED>
-LossKernels loss_kernels_of(int penalty) {
+template <int PRED, bool LV>
+LossKernels<LV> loss_kernels_of(int penalty) {
     if (penalty == VF_LOSS_L1)
-        return {compose_loss_fwd_kernel<VF_LOSS_L1, PRED>, compose_loss_bwd_kernel<VF_LOSS_L1, PRED>};
+        return {compose_loss_fwd_kernel<VF_LOSS_L1, PRED, LV>, compose_loss_bwd_kernel<VF_LOSS_L1, PRED, LV>};
     if (penalty == VF_LOSS_HUBER)
-        return {compose_loss_fwd_kernel<VF_LOSS_HUBER, PRED>, compose_loss_bwd_kernel<VF_LOSS_HUBER, PRED>};
-    return {compose_loss_fwd_kernel<VF_LOSS_MSE, PRED>, compose_loss_bwd_kernel<VF_LOSS_MSE, PRED>};
+        return {compose_loss_fwd_kernel<VF_LOSS_HUBER, PRED, LV>, compose_loss_bwd_kernel<VF_LOSS_HUBER, PRED, LV>};
+    return {compose_loss_fwd_kernel<VF_LOSS_MSE, PRED, LV>, compose_loss_bwd_kernel<VF_LOSS_MSE, PRED, LV>};
 }
 
-// the run-time (penalty, pred) -> the instantiation: the one place that names the nine of each
-LossKernels loss_kernels(int penalty, int pred) {
-    if (pred == VF_PRED_V) return loss_kernels_of<VF_PRED_V>(penalty);
-    if (pred == VF_PRED_X0) return loss_kernels_of<VF_PRED_X0>(penalty);
-    return loss_kernels_of<VF_PRED_EPS>(penalty);
+// the run-time (penalty, pred) -> the instantiation: the one place that names the eighteen of each
+template <bool LV>
+LossKernels<LV> loss_kernels(int penalty, int pred) {
+    if (pred == VF_PRED_V) return loss_kernels_of<VF_PRED_V, LV>(penalty);
+    if (pred == VF_PRED_X0) return loss_kernels_of<VF_PRED_X0, LV>(penalty);
+    return loss_kernels_of<VF_PRED_EPS, LV>(penalty);
 }
 
 }  // namespace
@@ -1894,7 +1773,8 @@ int vf_compose_mse_bwd(const float* unet_out, const int* off, const float* targe
 
 // ---- the loss family (loss_weight.h): vf_compose_fwd with a target / vf_compose_mse_bwd with a penalty, a prediction, a
 // per-sample weight of `level` (times a per-sample scale), the per-sample loss and an optional histogram.  Two launches
-// forward, one backward, as those.  Five entry points in front of one forward and one backward launcher:
+// forward, one backward, as those.  Five entry points in front of one forward and one backward launcher (and the two of
+// the hybrid loss, vf_compose_loss_lv_fwd / _bwd, which stand with the learned-variance entries further down):
 //   vf_compose_loss_fwd          eps, the target ready-made;
 //   vf_compose_loss_fwd_scaled   + scale (DEVICE float [B], the importance weight of level_sampler.h): sample_w then holds
 //                                2 B floats, w_b scale_b (what the loss and the backward use) and then w_b alone;
@@ -1919,11 +1799,15 @@ static inline bool pred_args_ok(int pred, const float* noise, const float* y_0) 
     return (pred == VF_PRED_V || pred == VF_PRED_X0) && y_0 && (pred == VF_PRED_X0 || noise);
 }
 
-// noise: the ready-made target for pred 0 (y_0 is then not read).
+// noise: the ready-made target for pred 0 (y_0 is then not read).  LV: the hybrid loss -- its operands for the forward
+// and the finish kernel (checked by its entry), and scale is null; the five older entries call loss_fwd<false>.
+extern "C++" {          // (templates, in the middle of the C entry points they serve)
+template <bool LV = false>
 static int loss_fwd(int pred, const float* unet_out, const int* off, const float* noise, const float* y_0,
                     const float* level, const float* scale, float* noise_hat, float* loss_part, float* sample_loss,
                     float* sample_w, float* loss, float* bin_sum, int* bin_cnt, int B, int Cout, int HW, int weighting,
-                    int penalty, float delta, int weight_kind, float a, float b, int K, void* stream) {
+                    int penalty, float delta, int weight_kind, float a, float b, int K, void* stream,
+                    VlbFwd<LV> fwd_vo = {}, VlbFinish<LV> fin_vo = {}) {
     if (B <= 0) return 0;
     if (!loss_args_ok(Cout, HW, weighting, penalty, delta)) return (int)hipErrorInvalidValue;
     if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
@@ -1931,23 +1815,27 @@ static int loss_fwd(int pred, const float* unet_out, const int* off, const float
     if (!level || !noise_hat || !loss_part || !sample_loss || !sample_w || !loss) return (int)hipErrorInvalidValue;
     hipStream_t st = (hipStream_t)stream;
     const int ch = chunks_for(3 * HW / 4);
-    hipLaunchKernelGGL(loss_kernels(penalty, pred).fwd, dim3(ch, B), dim3(256), 0, st, unet_out, off, noise, y_0, level,
-                       noise_hat, loss_part, Cout, HW, weighting, delta);
-    hipLaunchKernelGGL(compose_loss_finish_kernel, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
-                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b, pred);
+    hipLaunchKernelGGL(loss_kernels<LV>(penalty, pred).fwd, dim3(ch, B), dim3(256), 0, st, unet_out, off, noise, y_0,
+                       level, noise_hat, loss_part, Cout, HW, weighting, delta, fwd_vo);
+    hipLaunchKernelGGL(compose_loss_finish_kernel<LV>, dim3(1), dim3(64), 0, st, loss_part, level, scale, sample_loss,
+                       sample_w, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b, pred,
+                       fin_vo);
     VF_RETURN_LAST_ERROR();
 }
 
+template <bool LV = false>
 static int loss_bwd(int pred, const float* unet_out, const int* off, const float* noise, const float* y_0,
                     const float* level, const float* noise_hat, const float* gloss, const float* sample_w, float* dout,
-                    int B, int Cout, int HW, int weighting, int penalty, float delta, void* stream) {
+                    int B, int Cout, int HW, int weighting, int penalty, float delta, void* stream,
+                    VlbBwd<LV> vo = {}) {
     if (B <= 0) return 0;
     if (!loss_args_ok(Cout, HW, weighting, penalty, delta) || !sample_w) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(loss_kernels(penalty, pred).bwd, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
+    hipLaunchKernelGGL(loss_kernels<LV>(penalty, pred).bwd, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
                        (hipStream_t)stream, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout, Cout, HW,
-                       weighting, 1.0f / ((float)B * 3.0f * (float)HW), delta);
+                       weighting, 1.0f / ((float)B * 3.0f * (float)HW), delta, vo);
     VF_RETURN_LAST_ERROR();
 }
+}  // extern "C++"
 
 int vf_compose_loss_fwd(const float* unet_out, const int* off, const float* target, const float* level,
                         float* noise_hat, float* loss_part, float* sample_loss, float* sample_w, float* loss,
@@ -2108,9 +1996,9 @@ int vf_stack_views_cfg(const float* y_cond, const float* y_t, const float* noise
     const int rows = null_rows ? S + B : S;
     if (rows > 65535) return (int)hipErrorInvalidValue;
     const int n4 = 3 * HW / 4, nc4 = Cc * HW / 4;
-    hipLaunchKernelGGL(stack_views_cfg_kernel, dim3(chunks_for(nc4 > n4 ? nc4 : n4), rows), dim3(256), 0,
+    hipLaunchKernelGGL(stack_views_cfg_kernel<false>, dim3(chunks_for(nc4 > n4 ? nc4 : n4), rows), dim3(256), 0,
                        (hipStream_t)stream, (const float4*)y_cond, (const float4*)y_t, (const float4*)noise, level, angle,
-                       off, drop, (float4*)x, level_s, angle_s, B, Nmax, nc4, n4, copy_cond, S);
+                       off, drop, (float4*)x, level_s, angle_s, B, Nmax, nc4, n4, copy_cond, S, (const float4*)nullptr);
     VF_RETURN_LAST_ERROR();
 }
 
@@ -2399,9 +2287,9 @@ int vf_stack_views_sc(const float* y_cond, const float* y_t, const float* noise,
     const int rows = null_rows ? S + B : S;
     if (rows > 65535) return (int)hipErrorInvalidValue;
     const int n4 = 3 * HW / 4, nc4 = Cc * HW / 4;
-    hipLaunchKernelGGL(stack_views_sc_kernel, dim3(chunks_for(nc4 > n4 ? nc4 : n4), rows), dim3(256), 0,
+    hipLaunchKernelGGL(stack_views_cfg_kernel<true>, dim3(chunks_for(nc4 > n4 ? nc4 : n4), rows), dim3(256), 0,
                        (hipStream_t)stream, (const float4*)y_cond, (const float4*)y_t, (const float4*)noise, level, angle,
-                       off, drop, (const float4*)sc, (float4*)x, level_s, angle_s, B, Nmax, nc4, n4, copy_cond, S);
+                       off, drop, (float4*)x, level_s, angle_s, B, Nmax, nc4, n4, copy_cond, S, (const float4*)sc);
     VF_RETURN_LAST_ERROR();
 }
 
@@ -2457,8 +2345,15 @@ int vf_self_cond_coeffs_host(const float* level, int pred, float* a, float* b, i
 // The hybrid loss: vf_compose_loss_pred_fwd / _bwd for every pred (0 eps: `noise` is the ready-made target and y_0 is not
 // read) on a nine-channel unet_out, plus t (DEVICE int64 [B]), the fp32 tables c1, hi, lo [T] and lambda.  var_hat
 // [B][3][HW] and vlb_part [B * 64] next to noise_hat and loss_part; sample_vlb [B].  No per-sample scale.  Two launches
-// forward, one backward.  Refused: what the family refuses, Cout < 9, pred outside 0..2, T < 1, a null pointer among
-// those read.
+// forward, one backward, through loss_fwd / loss_bwd with the LV instantiations.  Refused, as before: what the family's
+// launcher of that direction refuses; by both entries (lv_args_ok) Cout < 9, T < 1, HW <= 0, pred outside 0..2, a null
+// noise unless x0, a null y_0 unless eps, a null unet_out, off, t, c1, hi, lo or var_hat; by the forward entry also a null
+// vlb_part or sample_vlb; by the backward entry also a null level, noise_hat, gloss or dout.  B <= 0 returns 0 first.
+static inline bool lv_args_ok(int Cout, int HW, int T, int pred, const float* noise, const float* y_0) {
+    if (Cout < 9 || T < 1 || HW <= 0 || pred < VF_PRED_EPS || pred > VF_PRED_X0) return false;
+    return (noise || pred == VF_PRED_X0) && (y_0 || pred == VF_PRED_EPS);
+}
+
 int vf_compose_loss_lv_fwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
                            const float* level, const long long* t, const float* c1, const float* hi, const float* lo,
                            float* noise_hat, float* var_hat, float* loss_part, float* vlb_part, float* sample_loss,
@@ -2466,23 +2361,12 @@ int vf_compose_loss_lv_fwd(const float* unet_out, const int* off, const float* n
                            int HW, int weighting, int penalty, float delta, int weight_kind, float a, float b, int K,
                            int pred, int T, float lambda, void* stream) {
     if (B <= 0) return 0;
-    if (!loss_args_ok(Cout, HW, weighting, penalty, delta) || Cout < 9 || T < 1 || HW <= 0)
+    if (!lv_args_ok(Cout, HW, T, pred, noise, y_0) || !unet_out || !off || !t || !c1 || !hi || !lo || !var_hat ||
+        !vlb_part || !sample_vlb)
         return (int)hipErrorInvalidValue;
-    if (pred < VF_PRED_EPS || pred > VF_PRED_X0 || !noise && pred != VF_PRED_X0 || !y_0 && pred != VF_PRED_EPS)
-        return (int)hipErrorInvalidValue;
-    if (weight_kind < VF_LOSS_W_NONE || weight_kind > VF_LOSS_W_LAST) return (int)hipErrorInvalidValue;
-    if ((bin_sum == nullptr) != (bin_cnt == nullptr) || (bin_sum && K < 1)) return (int)hipErrorInvalidValue;
-    if (!unet_out || !off || !level || !t || !c1 || !hi || !lo || !noise_hat || !var_hat || !loss_part || !vlb_part ||
-        !sample_loss || !sample_w || !sample_vlb || !loss)
-        return (int)hipErrorInvalidValue;
-    hipStream_t st = (hipStream_t)stream;
-    const int ch = chunks_for(3 * HW / 4);
-    hipLaunchKernelGGL(loss_lv_kernels(penalty, pred).fwd, dim3(ch, B), dim3(256), 0, st, unet_out, off, noise, y_0, level,
-                       t, c1, hi, lo, noise_hat, var_hat, loss_part, vlb_part, Cout, HW, weighting, delta, T);
-    hipLaunchKernelGGL(compose_loss_lv_finish_kernel, dim3(1), dim3(64), 0, st, loss_part, vlb_part, level, sample_loss,
-                       sample_w, sample_vlb, loss, bin_sum, bin_cnt, B, ch, K, 1.0f / (3.0f * (float)HW), weight_kind, a, b,
-                       pred, lambda);
-    VF_RETURN_LAST_ERROR();
+    return loss_fwd<true>(pred, unet_out, off, noise, y_0, level, nullptr, noise_hat, loss_part, sample_loss, sample_w,
+                          loss, bin_sum, bin_cnt, B, Cout, HW, weighting, penalty, delta, weight_kind, a, b, K, stream,
+                          {VlbArgs{t, c1, hi, lo, T, lambda}, var_hat, vlb_part}, {vlb_part, sample_vlb, lambda});
 }
 
 int vf_compose_loss_lv_bwd(const float* unet_out, const int* off, const float* noise, const float* y_0,
@@ -2491,16 +2375,11 @@ int vf_compose_loss_lv_bwd(const float* unet_out, const int* off, const float* n
                            float* dout, int B, int Cout, int HW, int weighting, int penalty, float delta, int pred, int T,
                            float lambda, void* stream) {
     if (B <= 0) return 0;
-    if (!loss_args_ok(Cout, HW, weighting, penalty, delta) || Cout < 9 || T < 1 || HW <= 0)
+    if (!lv_args_ok(Cout, HW, T, pred, noise, y_0) || !unet_out || !off || !level || !t || !c1 || !hi || !lo ||
+        !noise_hat || !var_hat || !gloss || !dout)
         return (int)hipErrorInvalidValue;
-    if (pred < VF_PRED_EPS || pred > VF_PRED_X0 || !noise && pred != VF_PRED_X0 || !y_0 && pred != VF_PRED_EPS)
-        return (int)hipErrorInvalidValue;
-    if (!unet_out || !off || !level || !t || !c1 || !hi || !lo || !noise_hat || !var_hat || !gloss || !sample_w || !dout)
-        return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(loss_lv_kernels(penalty, pred).bwd, dim3(chunks_for(3 * HW / 4), B), dim3(256), 0,
-                       (hipStream_t)stream, unet_out, off, noise, y_0, level, t, c1, hi, lo, noise_hat, var_hat, gloss,
-                       sample_w, dout, Cout, HW, weighting, 1.0f / ((float)B * 3.0f * (float)HW), delta, T, lambda);
-    VF_RETURN_LAST_ERROR();
+    return loss_bwd<true>(pred, unet_out, off, noise, y_0, level, noise_hat, gloss, sample_w, dout, B, Cout, HW,
+                          weighting, penalty, delta, stream, {VlbArgs{t, c1, hi, lo, T, lambda}, var_hat});
 }
 
 // The learned-variance tail: vf_sampler_step{, _rng, _cfg, _cfg_rng} without c1 and with the tables hi, lo [K] behind

@@ -134,7 +134,7 @@ def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True
     Classifier-free guidance (csrc/diffusion.hip), through a sibling kernel taken only when one of the two is used:
     drop (device bool / uint8 (B,)): the conditioning half of every row of a sample with drop[b] != 0 is zeros;
     null_rows=True: S + B rows come back, row S + b = [ 0 | y_t[b] ] with the sample's own level and angle.
-    Self-conditioning (csrc/diffusion.hip), through a third sibling taken only when asked for: self_cond (B,3,H,W) --
+    Self-conditioning (csrc/diffusion.hip), the guided kernel's SC instantiation, taken only when asked for: self_cond (B,3,H,W) --
     x is (rows,Cc+6,H,W) and every row of sample b (its null row too) ends with self_cond[b]; sc_channels=True with
     self_cond=None writes zeros there ("no estimate").  The first Cc + 3 channels carry the bits of the call without it."""
     y_cond, y_t = _c(y_cond), _c(y_t)
@@ -163,23 +163,18 @@ def stack_views(y_cond, y_t, noise, level, angle, off, S, x=None, copy_cond=True
             raise ValueError(f"stack_views needs y_t (and noise) of shape {(B, 3, H, W)} and one level and angle per sample")
         if off.dtype != torch.int32 or off.numel() != B + 1 or rows > 65535:
             raise ValueError(f"off must be the int32 offsets table of {B} samples (ops.view_offsets), at most 65535 rows")
-        if drop is not None:
-            drop = _drop_mask(drop, B, y_cond.device)
-        _call("vf_stack_views_sc", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
-              ctypes.c_void_p(off.data_ptr()), None if drop is None else ctypes.c_void_p(drop.data_ptr()),
-              _ptr(self_cond), _ptr(x), _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond),
-              int(bool(null_rows)), _stream())
-        return x, ls, as_
-    if drop is None and not null_rows:
+    elif drop is None and not null_rows:
         _call("vf_stack_views", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
               ctypes.c_void_p(off.data_ptr()), _ptr(x), _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond),
               _stream())
         return x, ls, as_
     if drop is not None:
         drop = _drop_mask(drop, B, y_cond.device)
-    _call("vf_stack_views_cfg", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level), _ptr(angle),
-          ctypes.c_void_p(off.data_ptr()), None if drop is None else ctypes.c_void_p(drop.data_ptr()), _ptr(x),
-          _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond), int(bool(null_rows)), _stream())
+    # the guided kernel, with or without the third part: vf_stack_views_sc takes self_cond in front of x
+    _call("vf_stack_views_sc" if sc_on else "vf_stack_views_cfg", _ptr(y_cond), _ptr(y_t), _ptr(noise), _ptr(level),
+          _ptr(angle), ctypes.c_void_p(off.data_ptr()), None if drop is None else ctypes.c_void_p(drop.data_ptr()),
+          *((_ptr(self_cond),) if sc_on else ()), _ptr(x), _ptr(ls), _ptr(as_), B, Nmax, Cc, H * W, S, int(copy_cond),
+          int(bool(null_rows)), _stream())
     return x, ls, as_
 
 
@@ -389,12 +384,16 @@ class _ComposeLossOptFn(torch.autograd.Function):
     """_ComposeLossFn with a penalty, a prediction, a per-sample weight of the noise level (times a per-sample scale) and
     the per-sample loss as a second (non-differentiable) output: the same two launches forward and one backward.
     pred 0 (eps): `target` is the ready-made target; pred 1 (v) | 2 (x0): it is the noise, and the kernels form the target
-    from it, y_0 and level themselves -- no target buffer."""
+    from it, y_0 and level themselves -- no target buffer.
+    vlb = (t, c1, hi, lo, lam) | None: the hybrid objective of a learned variance on a nine-channel output
+    (csrc/diffusion.hip holds the definition), for every pred: loss = L_simple + lam mean_b vlb_b, the per-sample vlb
+    (bits per dimension) a fourth non-differentiable output, and the backward writes all nine channels."""
 
     @staticmethod
     def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, scale=None,
-                pred=0, y_0=None):
-        _check(out, target, y_0, level, bin_sum, scale)
+                pred=0, y_0=None, vlb=None):
+        t, c1, hi, lo, lam = vlb if vlb is not None else (None,) * 5
+        _check(out, target, y_0, level, bin_sum, scale, c1, hi, lo)
         S, Cout, H, W = out.shape
         if level.numel() != B:
             raise ValueError(f"compose_loss needs one level per sample: {level.numel()} levels for a batch of {B}")
@@ -408,82 +407,60 @@ class _ComposeLossOptFn(torch.autograd.Function):
                 raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
         if scale is not None and scale.numel() != B:
             raise ValueError(f"compose_loss needs one scale per sample: {scale.numel()} for a batch of {B}")
-        nh = torch.empty(B, 3, H, W, device=out.device, dtype=torch.float32)
-        nw = 1 if scale is None else 2           # partials | sample_loss | w (scale) | [w] | loss  (csrc/level_sampler.h)
-        buf = torch.empty(B * (65 + nw) + 1, device=out.device, dtype=torch.float32)
-        sample_loss, sample_w, loss = buf[B * 64:B * 65], buf[B * 65:B * 66], buf[B * (65 + nw):]
-        weight = sample_w if scale is None else buf[B * 66:B * 67]
+        # nh: the composed prediction [| the composed o_b];  buf: partials [| vlb partials] | sample_loss | w (scale) |
+        # [w] | [sample_vlb] | loss  (csrc/level_sampler.h; a scale and a vlb term never come together).  In floats:
+        #   plain        nh (1,B,3,H,W)  buf 66 B + 1:   [0, 64B) | 64B | 65B | loss at 66B
+        #   with scale   nh (1,B,3,H,W)  buf 67 B + 1:   [0, 64B) | 64B | 65B (w scale) | 66B (w) | loss at 67B
+        #   with vlb     nh (2,B,3,H,W)  buf 131 B + 1:  [0, 64B) | [64B, 128B) | 128B | 129B | 130B (vlb) | loss at 131B
+        # (nh always has the leading axis, so that the backward hands over one pointer per part)
+        nv = 0 if vlb is None else 1
+        nh = torch.empty(1 + nv, B, 3, H, W, device=out.device, dtype=torch.float32)
+        s0 = B * 64 * (1 + nv)
+        nw = 1 if scale is None else 2
+        buf = torch.empty(s0 + B * (1 + nw + nv) + 1, device=out.device, dtype=torch.float32)
+        sample_loss, sample_w, loss = buf[s0:s0 + B], buf[s0 + B:s0 + 2 * B], buf[s0 + B * (1 + nw + nv):]
+        weight = sample_w if scale is None else buf[s0 + 2 * B:s0 + 3 * B]
+        extra = ()
         # one entry point per path (the kernel log names them): each takes what its path has, in this order
-        if pred:
-            entry, front, back = "vf_compose_loss_pred_fwd", (_ptr(target), _ptr(y_0), _ptr(level), _ptr(scale)), (pred,)
-        elif scale is not None:
-            entry, front, back = "vf_compose_loss_fwd_scaled", (_ptr(target), _ptr(level), _ptr(scale)), ()
+        if vlb is not None:
+            vlb_part, sample_vlb = buf[B * 64:s0], buf[s0 + 2 * B:s0 + 3 * B]
+            tables = (ctypes.c_void_p(t.data_ptr()), _ptr(c1), _ptr(hi), _ptr(lo))
+            entry, front, back = "vf_compose_loss_lv_fwd", (_ptr(target), _ptr(y_0), _ptr(level)) + tables, (pred, c1.numel(), lam)
+            outs = (_ptr(nh[0]), _ptr(nh[1]), _ptr(buf), _ptr(vlb_part), _ptr(sample_loss), _ptr(sample_w), _ptr(sample_vlb))
+            extra = (sample_vlb,)
         else:
-            entry, front, back = "vf_compose_loss_fwd", (_ptr(target), _ptr(level)), ()
-        _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, _ptr(nh), _ptr(buf), _ptr(sample_loss),
-              _ptr(sample_w), _ptr(loss), _ptr(bin_sum), None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()),
+            outs = (_ptr(nh), _ptr(buf), _ptr(sample_loss), _ptr(sample_w))
+            if pred:
+                entry, front, back = "vf_compose_loss_pred_fwd", (_ptr(target), _ptr(y_0), _ptr(level), _ptr(scale)), (pred,)
+            elif scale is not None:
+                entry, front, back = "vf_compose_loss_fwd_scaled", (_ptr(target), _ptr(level), _ptr(scale)), ()
+            else:
+                entry, front, back = "vf_compose_loss_fwd", (_ptr(target), _ptr(level)), ()
+        _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, *outs, _ptr(loss), _ptr(bin_sum),
+              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()),
               B, Cout, H * W, int(weighting), penalty, delta, kind, a, b, K, *back, _stream())
-        ctx.save_for_backward(out, target, y_0, level, nh, off, sample_w)
-        ctx.B, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred = B, int(weighting), penalty, delta, pred
-        ctx.mark_non_differentiable(sample_loss, weight)
-        return loss.reshape(()), sample_loss, weight
-
-    @staticmethod
-    def backward(ctx, gloss, _gsample, _gweight):
-        out, target, y_0, level, nh, off, sample_w = ctx.saved_tensors
-        S, Cout, H, W = out.shape
-        gloss = _c(gloss.reshape(1).float())
-        dout = torch.empty_like(out) if Cout <= 6 else torch.zeros_like(out)      # (as in _ComposeLossFn.backward)
-        if ctx.pred:
-            entry, front, back = "vf_compose_loss_pred_bwd", (_ptr(target), _ptr(y_0), _ptr(level)), (ctx.pred,)
-        else:
-            entry, front, back = "vf_compose_loss_bwd", (_ptr(target),), ()
-        _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, _ptr(nh), _ptr(gloss), _ptr(sample_w), _ptr(dout),
-              ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, *back, _stream())
-        return (dout,) + (None,) * 15
-
-
-class _ComposeLossLvFn(torch.autograd.Function):
-    """_ComposeLossOptFn on a nine-channel output with the vlb term of a learned variance (csrc/diffusion.hip holds the
-    definition): loss = L_simple + lam mean_b vlb_b; the per-sample loss, the weight and the per-sample vlb (bits per
-    dimension) as non-differentiable outputs.  Two launches forward, one backward, which writes all nine channels."""
-
-    @staticmethod
-    def forward(ctx, out, target, off, B, weighting, level, penalty, delta, kind, a, b, bin_sum, bin_cnt, pred, y_0, t, c1,
-                hi, lo, lam):
-        _check(out, target, y_0, level, bin_sum, c1, hi, lo)
-        S, Cout, H, W = out.shape
-        T = c1.numel()
-        K = 0
-        if bin_sum is not None:
-            K = bin_sum.numel()
-            if not bin_cnt.is_cuda or bin_cnt.dtype != torch.int32 or not bin_cnt.is_contiguous() or bin_cnt.numel() != K:
-                raise _lib.VFHipError("hist must be (float32 [K], int32 [K]) contiguous device tensors")
-        nh = torch.empty(2, B, 3, H, W, device=out.device, dtype=torch.float32)      # composed prediction | composed o_b
-        buf = torch.empty(B * 131 + 1, device=out.device, dtype=torch.float32)       # partials x 2 | s | w | vlb | loss
-        vlb_part, sample_loss, sample_w = buf[B * 64:B * 128], buf[B * 128:B * 129], buf[B * 129:B * 130]
-        sample_vlb, loss = buf[B * 130:B * 131], buf[B * 131:]
-        _call("vf_compose_loss_lv_fwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(y_0), _ptr(level),
-              ctypes.c_void_p(t.data_ptr()), _ptr(c1), _ptr(hi), _ptr(lo), _ptr(nh[0]), _ptr(nh[1]), _ptr(buf),
-              _ptr(vlb_part), _ptr(sample_loss), _ptr(sample_w), _ptr(sample_vlb), _ptr(loss), _ptr(bin_sum),
-              None if bin_cnt is None else ctypes.c_void_p(bin_cnt.data_ptr()), B, Cout, H * W, int(weighting), penalty,
-              delta, kind, a, b, K, pred, T, lam, _stream())
         ctx.save_for_backward(out, target, y_0, level, nh, off, sample_w, t, c1, hi, lo)
         ctx.B, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred, ctx.lam = B, int(weighting), penalty, delta, pred, lam
-        ctx.mark_non_differentiable(sample_loss, sample_w, sample_vlb)
-        return loss.reshape(()), sample_loss, sample_w, sample_vlb
+        ctx.mark_non_differentiable(sample_loss, weight, *extra)
+        return (loss.reshape(()), sample_loss, weight) + extra
 
     @staticmethod
-    def backward(ctx, gloss, _gsample, _gweight, _gvlb):
+    def backward(ctx, gloss, *_):
         out, target, y_0, level, nh, off, sample_w, t, c1, hi, lo = ctx.saved_tensors
         S, Cout, H, W = out.shape
         gloss = _c(gloss.reshape(1).float())
-        dout = torch.empty_like(out)
-        _call("vf_compose_loss_lv_bwd", _ptr(out), ctypes.c_void_p(off.data_ptr()), _ptr(target), _ptr(y_0), _ptr(level),
-              ctypes.c_void_p(t.data_ptr()), _ptr(c1), _ptr(hi), _ptr(lo), _ptr(nh[0]), _ptr(nh[1]), _ptr(gloss),
-              _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, ctx.pred, c1.numel(),
-              ctx.lam, _stream())
-        return (dout,) + (None,) * 19
+        # (without the vlb term the kernel writes channels 0..5, as in _ComposeLossFn.backward; with it all nine)
+        dout = torch.empty_like(out) if Cout <= 6 or t is not None else torch.zeros_like(out)
+        if t is not None:
+            tables = (ctypes.c_void_p(t.data_ptr()), _ptr(c1), _ptr(hi), _ptr(lo))
+            entry, front, back = "vf_compose_loss_lv_bwd", (_ptr(target), _ptr(y_0), _ptr(level)) + tables, (ctx.pred, c1.numel(), ctx.lam)
+        elif ctx.pred:
+            entry, front, back = "vf_compose_loss_pred_bwd", (_ptr(target), _ptr(y_0), _ptr(level)), (ctx.pred,)
+        else:
+            entry, front, back = "vf_compose_loss_bwd", (_ptr(target),), ()
+        _call(entry, _ptr(out), ctypes.c_void_p(off.data_ptr()), *front, *(_ptr(h) for h in nh), _ptr(gloss),
+              _ptr(sample_w), _ptr(dout), ctx.B, Cout, H * W, ctx.weighting, ctx.penalty, ctx.delta, *back, _stream())
+        return (dout,) + (None,) * 16
 
 
 def _check_nine(what, unet_out):
@@ -494,7 +471,7 @@ def _check_nine(what, unet_out):
 
 def _compose_loss_lv(unet_out, target, off, B, weighting, level, penalty, delta, weight_kind, a, b, hist, prediction, y_0,
                      vlb):
-    """The vlb= path of compose_loss: the checks, then _ComposeLossLvFn."""
+    """The vlb= path of compose_loss: the checks, then _ComposeLossOptFn with the vlb tuple."""
     if not isinstance(vlb, (tuple, list)) or len(vlb) != 5:
         raise ValueError("vlb= takes (t, c1, hi, lo, weight)")
     t, c1, hi, lo, lam = vlb
@@ -511,9 +488,10 @@ def _compose_loss_lv(unet_out, target, off, B, weighting, level, penalty, delta,
         raise ValueError(f"vlb= needs c1, hi and lo of one length T, got {c1.numel()}, {hi.numel()} and {lo.numel()}")
     _check_i64("vlb's t", t, B)
     bin_sum, bin_cnt = hist if hist is not None else (None, None)
-    return _ComposeLossLvFn.apply(unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty],
-                                  float(delta), WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt,
-                                  PREDICTIONS[prediction], None if y_0 is None else _c(y_0), t, _c(c1), _c(hi), _c(lo), lam)
+    return _ComposeLossOptFn.apply(unet_out, _c(target), off, B, weighting, _c(level.reshape(-1)), PENALTIES[penalty],
+                                   float(delta), WEIGHT_KINDS[weight_kind], float(a), float(b), bin_sum, bin_cnt, None,
+                                   PREDICTIONS[prediction], None if y_0 is None else _c(y_0),
+                                   (t, _c(c1), _c(hi), _c(lo), lam))
 
 
 def vlb_terms_host(o, hi, lo, c1, level, r, prediction="eps"):
