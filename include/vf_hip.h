@@ -640,6 +640,28 @@ int vf_sampler_step_lv_cfg_rng(const float* unet_out, const int* off, const floa
 /* Host mirror of csrc/vlb.h (HOST pointers, no stream): per element lp, KL in bits and dKL/dlp */
 int vf_vlb_terms_host(const float* o, const float* hi, const float* lo, const float* c1, const float* level,
                       const float* r, int pred, float* lp, float* kl, float* dkl, int n);
+/* ---- the variational bound in bits per dimension (csrc/diffusion.hip holds the definition, csrc/vlb.h the arithmetic):
+ *      evaluation only, new kernels only.  kidx: DEVICE int64 [B], the step of every sample, clamped into [0, K - 1];
+ *      the fp32 tables a, b, c0, hi, lo [K] are schedule.nll_tables'. ---- */
+/* y_k [B][3][HW] = sqrt(g) y_0 + sqrt(1 - g) n, g = gammas[tau[k]]: n from noise [B][K][3][HW] at (b, k), or, with noise
+ * NULL, drawn from (seed, ids[b], kind 6, tau[k], float4 index) */
+int vf_nll_noisy(const float* y_0, const float* noise /*|NULL*/, unsigned long long seed, const long long* ids /*|NULL*/,
+                 const long long* kidx, const long long* tau /*[K]*/, const float* gammas /*[T]*/, float* y_k, int B,
+                 int HW, int K, int T, void* stream);
+/* column k of vb [B][K] (the term in bits, the mean over 3 HW elements) and of x0_mse [B][K] (the mean of (y0 - y_0)^2);
+ * lv: nine channels, lp by the composed channels 6..8; else lp = hi[k] where large, lo[k] otherwise; dec: the decoder
+ * likelihood (k == 0) instead of the KL; vb_part, sq_part: [B * 64] scratch.  Two launches, no atomics. */
+int vf_nll_terms(const float* unet_out, const int* off, const float* y_k, const float* y_0, const long long* kidx,
+                 const float* a, const float* b, const float* c0, const float* hi, const float* lo, float* vb_part,
+                 float* sq_part, float* vb, float* x0_mse, int B, int Cout, int HW, int K, int weighting, int clip, int lv,
+                 int dec, int large, void* stream);
+/* prior [B]: L_T from y_0 and gammas[T - 1]; part: [B * 64] scratch */
+int vf_nll_prior(const float* y_0, const float* gammas, float* part, float* prior, int B, int HW, int T, void* stream);
+/* Host mirror of one term (HOST pointers, no stream): per element i of n its own composed out, raw variance o (lv alone,
+ * else NULL), y_k, y_0 and table row -> term[i] in bits and sq[i] = (y0 - y_0)^2 */
+int vf_nll_terms_host(const float* out, const float* o, const float* y_k, const float* y_0, const float* a,
+                      const float* b, const float* c0, const float* hi, const float* lo, int lv, int dec, int large,
+                      int clip, float* term, float* sq, int n);
 
 /* ---- batch assembly from a device-resident view store (csrc/batch.hip; data.ViewStore): the reference loader's
  *      process_sample + collate + H2D, data/nmr_dataset.py:10-52, as one launch.  store: planar uint8 [N][24][3][H][W],

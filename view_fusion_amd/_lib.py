@@ -190,6 +190,10 @@ SIGNATURES = {
     "vf_sampler_step_lv_cfg": [_P] * 16 + [_I, _I, _I, _I, _I, _P, _P],
     "vf_sampler_step_lv_cfg_rng": [_P, _P, _P, _U64] + [_P] * 14 + [_I, _I, _I, _I, _I, _P, _P],
     "vf_vlb_terms_host": [_P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I],
+    "vf_nll_noisy": [_P, _P, _U64, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "vf_nll_terms": [_P] * 14 + [_I] * 9 + [_P],
+    "vf_nll_prior": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "vf_nll_terms_host": [_P] * 9 + [_I, _I, _I, _I, _P, _P, _I],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

@@ -53,6 +53,8 @@
 //   learned variance  sampler_step_lv_kernel<CFG, RNG> (the few-step tail with a per-pixel noise scale; it rounds the guided
 //                   combination and the base otherwise than sampler_step_kernel and has no history term, so it stays a
 //                   sibling), behind the self-conditioning kernels; the hybrid loss is the loss family's LV switch, above.
+//   the bound       nll_noisy_kernel<RNG>, nll_term_kernel<LV, DEC>, nll_prior_kernel, nll_finish_kernel: the terms of the
+//                   variational bound in bits per dimension (evaluation only), behind the loss family's launch tables.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
 //                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The seven
@@ -201,7 +203,8 @@
 //       loss = L_simple + lambda (1/B) sum_b vlb_b.
 //     L_simple is the loss family's objective, unchanged: penalties, the noise-level weight, the per-sample loss and the
 //     histogram, all on r.  The vlb term takes no SNR weight.  t is never 0 in training (draw_train gives 1..T-1), so the
-//     discretised decoder likelihood of t = 0 is not needed and not built.
+//     discretised decoder likelihood of t = 0 takes no part in training; the evaluation of the bound builds it
+//     ("Variational bound", below).
 //   Gradient.  dloss/dlp = (lambda / (n B)) 0.5 (1 - exp(lo - lp) - m^2 exp(-lp)) / ln 2;  dlp/do_b = 0.5 (hi - lo);
 //     channels 6..8 get w_v g, the logits 3..5 get w_v (o_v - o_b) g ADDED to L_simple's logit gradient, channels 0..2 get
 //     L_simple's gradient only; mean ablation: channels 6..8 get g / count, the logits 0.
@@ -211,6 +214,38 @@
 //     y0_prev <- y0 when a history buffer is passed.  Weights, logits and the draw of z (step = tau[k]) are that kernel's.
 //     Guided: `out` is guided as before; o_b comes from the CONDITIONAL rows only, the null row's channels 6..8 are
 //     ignored (GLIDE).  No EPS / threshold / rescale flavour.
+//
+// Variational bound (Ho et al., DDPM, eq. 5; Nichol & Dhariwal, "Improved DDPM", 2.3 and calc_bpd_loop): the bound on
+// -log2 p(y_0) of held-out targets, in bits per dimension, term by term.  This comment is the ONE written definition (the
+// arithmetic, operation by operation: vlb.h and nll_element below); tests/nll_ref.py restates it.  Opt-in and additive:
+// new kernels only (nll_noisy_kernel<RNG>, nll_term_kernel<LV, DEC>, nll_prior_kernel, nll_finish_kernel), behind the
+// loss family's launch tables; nothing above changes.
+//   Chain.  tau of K steps (default 0..T-1; schedule.sample_timesteps otherwise), gt = gammas[tau[k]], gp = gammas[tau[k-1]]
+//     (1 at k = 0).
+//   Noisy target.  Per sample b and step k one Monte-Carlo draw: y_k = sqrt(gt) y_0 + sqrt(1 - gt) n with the fp32 buffer
+//     value gt, both products rounded, then added.  n is injected ((B, K, 3, H, W)), or drawn: Philox kind 6 (rng.h),
+//     step = tau[k], block = the float4 index, keyed by (seed, sample id).  The network runs on the inference path at
+//     the discrete level gt, its rows stacked as generate() stacks them.
+//   Model distribution (the sampler's own).  y0 = clamp(a[k] y_k - b[k] out_b, -1, 1) (no clamp under
+//     clip_denoised=False); (a, b) = schedule.prediction_tables at tau for eps, v or x0; out_b = compose4 over the sample's
+//     real views.  The model's mean minus the true posterior mean is c0[k] (y0 - y_0) with
+//     c0[k] = sqrt(gp) (1 - gt/gp) / (1 - gt) (posterior_mean_coef1 on the full chain, value for value): m^2 = c0^2 (y0 - y_0)^2.
+//   Log-variance lp.  A nine-channel model with a learned variance: vf_vlb_logvar(o_b, hi[k], lo[k]), o_b = compose4_var.
+//     A fixed variance: lp = lo[k] ("small", what the ancestral sampler uses) or hi[k] ("large").
+//   Terms.  k >= 1: L_k = the mean over the 3 H W elements of vf_vlb_kl(lp, lo[k], m^2), in bits.  k = 0, the decoder:
+//     L_0 = the mean of vf_nll_decoder(y_0, y0, lp): Improved DDPM's discretised Gaussian likelihood with bins of +-1/255,
+//     the tanh approximation of Phi, the open-ended bins below -0.999 and above 0.999, every log argument clamped at 1e-12.
+//     Its variance row is not lo[0] = log 1e-20 (the clipping the buffers carry, under which the term degenerates):
+//     hi_dec = log(1 - gammas[tau[0]]), lo_dec = the log posterior variance of step 1 of the chain (Improved DDPM's
+//     posterior_log_variance_clipped[0]; also the row the network has seen at that level, training draws t >= 1); a
+//     one-step chain has lo_dec = hi_dec; "large" uses lo_dec at k = 0 as well, as the paper does.
+//     Prior: L_T = the mean of 0.5 (-1 - log(1 - gT) + (1 - gT) + gT y_0^2) / ln 2, gT = gammas[T-1]: exactly 0 at gT = 0.
+//     total_bpd_b = L_T + sum_k L_k.
+//   Diagnostic.  x0_mse[b, k] = the mean of (y0 - y_0)^2; the error of the recovered noise is x0_mse gt / (1 - gt)
+//     identically, formed by the driver: no noise buffer reaches the term kernel.
+//   Reduction.  Two partial sums per (b, chunk) by block_sum<256>, then one thread per sample adds its partials in index
+//     order: no atomics, the same bits on every run and for every batch the sample stands in.
+//   Not built: a captured K-step loop, a guided bound, level resampling on L_vlb.
 #include "common.h"
 #include "level_sampler.h"
 #include "loss_weight.h"
@@ -1714,6 +1749,159 @@ LossKernels<LV> loss_kernels(int penalty, int pred) {
     return loss_kernels_of<VF_PRED_EPS, LV>(penalty);
 }
 
+// ---- the variational bound (the head of this file holds the definition, vlb.h the arithmetic) ----
+// One element of one term: y0 = clamp(a y - b out) (both products rounded, then subtracted, as the few-step tails form
+// it), d = y0 - x, sq = d d, and the term in bits -- the decoder likelihood of x under N(y0, exp(lp)) with DEC, else the
+// KL of vlb.h at m^2 = c0^2 d^2.  The kernel and the host mirror (vf_nll_terms_host) both run this very function.
+struct NllRow {
+    float a, b, c0, hi, lo;
+};
+template <bool DEC>
+__host__ __device__ inline float nll_element(const NllRow& r, float out, float lp, float y, float x, int clip,
+                                             float* sq) {
+#pragma clang fp contract(off)
+    const float ay = r.a * y;
+    const float bo = r.b * out;
+    float y0 = ay - bo;
+    if (clip) y0 = fminf(fmaxf(y0, -1.0f), 1.0f);
+    const float d = y0 - x;
+    *sq = d * d;
+    if (DEC) return vf_nll_decoder(x, y0, lp);
+    return vf_vlb_kl(lp, r.lo, vf_vlb_m2(r.c0, 1.0f, d));
+}
+
+// The step index of a sample, clamped into the chain before any table is read.
+__device__ __forceinline__ long long nll_step(const long long* __restrict__ kidx, int b, int K) {
+    const long long k = kidx[b];
+    return k < 0 ? 0 : (k > K - 1 ? K - 1 : k);
+}
+
+// The noisy target of step k = kidx[b]: y_k = sqrt(g) y_0 + sqrt(1 - g) n, g = gammas[tau[k]], both products rounded, then
+// added.  RNG: n is drawn here, kind 6, step = tau[k], block = the float4 index, keyed by the sample's id; else loaded
+// from noise[B][K][3][HW] at (b, k).  grid (chunks, B).
+template <bool RNG>
+__global__ __launch_bounds__(256) void nll_noisy_kernel(const float* __restrict__ y_0, const float* __restrict__ noise,
+                                                        unsigned long long seed, const long long* __restrict__ ids,
+                                                        const long long* __restrict__ kidx,
+                                                        const long long* __restrict__ tau,
+                                                        const float* __restrict__ gammas, float* __restrict__ y_k,
+                                                        int HW, int K, int T) {
+    const int b = blockIdx.y;
+    const int n4 = 3 * HW / 4;
+    const long long k = nll_step(kidx, b, K);
+    long long t = tau[k];
+    t = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
+    const float g = gammas[t];
+    const float sa = sqrtf(g), sb = sqrtf(1.0f - g);
+    unsigned long long id = 0;
+    if constexpr (RNG) id = (unsigned long long)ids[b];
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        const float4 x = *reinterpret_cast<const float4*>(y_0 + o);
+        float n[4];
+        if constexpr (RNG) {
+            vf_rng_normal4(seed, id, VF_RNG_NLL_NOISE, (uint32_t)t, (uint32_t)i, n);
+        } else {
+            const float4 z = *reinterpret_cast<const float4*>(noise + ((size_t)b * K + (size_t)k) * 3 * HW +
+                                                              4 * (size_t)i);
+            n[0] = z.x; n[1] = z.y; n[2] = z.z; n[3] = z.w;
+        }
+        *reinterpret_cast<float4*>(y_k + o) =
+            make_float4(add_rn(mul_rn(sa, x.x), mul_rn(sb, n[0])), add_rn(mul_rn(sa, x.y), mul_rn(sb, n[1])),
+                        add_rn(mul_rn(sa, x.z), mul_rn(sb, n[2])), add_rn(mul_rn(sa, x.w), mul_rn(sb, n[3])));
+    }
+}
+
+// One term of the bound per (b, chunk): compose_loss_fwd_kernel's geometry and composition, the row k = kidx[b] of the
+// tables, the term and (y0 - y_0)^2 in registers, two partial sums.  LV: lp between lo[k] and hi[k] by the composed
+// channels 6..8; else lp = hi[k] where `large`, lo[k] otherwise.  DEC: the decoder likelihood (the launcher's k == 0).
+template <bool LV, bool DEC>
+__global__ __launch_bounds__(256) void nll_term_kernel(const float* __restrict__ out, const int* __restrict__ off,
+                                                       const float* __restrict__ y_k, const float* __restrict__ y_0,
+                                                       const long long* __restrict__ kidx, const float* __restrict__ ta,
+                                                       const float* __restrict__ tb, const float* __restrict__ tc0,
+                                                       const float* __restrict__ thi, const float* __restrict__ tlo,
+                                                       float* __restrict__ vb_part, float* __restrict__ sq_part,
+                                                       int Cout, int HW, int K, int weighting, int clip, int large) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const long long k = nll_step(kidx, b, K);
+    const NllRow row{ta[k], tb[k], tc0[k], thi[k], tlo[k]};
+    const float lp_fixed = large ? row.hi : row.lo;
+    float acc = 0.f, sq = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        float4 mx = make_float4(0.f, 0.f, 0.f, 0.f), inv = mx, ob = mx;
+        const float4 e = compose4(out, Cout, HW, v0, v1, c, p, weighting, LV ? &mx : nullptr, LV ? &inv : nullptr);
+        if constexpr (LV) ob = compose4_var(out, Cout, HW, v0, v1, c, p, weighting, mx, inv);
+        const size_t o = (size_t)b * 3 * HW + 4 * (size_t)i;
+        const float4 y = *reinterpret_cast<const float4*>(y_k + o);
+        const float4 x = *reinterpret_cast<const float4*>(y_0 + o);
+        const float es[4] = {e.x, e.y, e.z, e.w}, os[4] = {ob.x, ob.y, ob.z, ob.w};
+        const float ys[4] = {y.x, y.y, y.z, y.w}, xs[4] = {x.x, x.y, x.z, x.w};
+        float t[4], s[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float lp = LV ? vf_vlb_logvar(os[j], row.hi, row.lo) : lp_fixed;
+            t[j] = nll_element<DEC>(row, es[j], lp, ys[j], xs[j], clip, &s[j]);
+        }
+        acc += (t[0] + t[1]) + (t[2] + t[3]);
+        sq += (s[0] + s[1]) + (s[2] + s[3]);
+    }
+    acc = block_sum<256>(acc, red);
+    sq = block_sum<256>(sq, red);
+    if (threadIdx.x == 0) {
+        vb_part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+        sq_part[blockIdx.y * gridDim.x + blockIdx.x] = sq;
+    }
+}
+
+// The prior term per (b, chunk): 0.5 (-1 - log(1 - gT) + (1 - gT) + gT y_0^2) / ln 2 with gT = gammas[T - 1]; gT == 0
+// gives 0 exactly.
+__global__ __launch_bounds__(256) void nll_prior_kernel(const float* __restrict__ y_0, const float* __restrict__ gammas,
+                                                        float* __restrict__ part, int HW, int T) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int n4 = 3 * HW / 4;
+    const float gT = gammas[T - 1];
+    const float om = 1.0f - gT;
+    const float base = add_rn(add_rn(-1.0f, -logf(om)), om);
+    float acc = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const float4 x = *reinterpret_cast<const float4*>(y_0 + (size_t)b * 3 * HW + 4 * (size_t)i);
+        const float xs[4] = {x.x, x.y, x.z, x.w};
+        float t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            t[j] = mul_rn(mul_rn(0.5f, add_rn(base, mul_rn(gT, mul_rn(xs[j], xs[j])))), VF_VLB_INV_LN2);
+        acc += (t[0] + t[1]) + (t[2] + t[3]);
+    }
+    acc = block_sum<256>(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// One thread per sample: its `ch` partials in index order, / n, into column k = kidx[b] of the (B, K) tables (kidx null:
+// column 0; sq_part / x0_mse null: the one table).  Every address is written by exactly one thread: the same bits on
+// every run, whatever the batch.
+__global__ __launch_bounds__(64) void nll_finish_kernel(const float* __restrict__ vb_part,
+                                                        const float* __restrict__ sq_part,
+                                                        const long long* __restrict__ kidx, float* __restrict__ vb,
+                                                        float* __restrict__ x0_mse, int B, int ch, int K, float inv_n) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= B) return;
+    const long long k = kidx ? nll_step(kidx, s, K) : 0;
+    float acc = 0.f;
+    for (int c = 0; c < ch; ++c) acc += vb_part[s * ch + c];
+    vb[(size_t)s * K + k] = acc * inv_n;
+    if (sq_part != nullptr) {
+        float sq = 0.f;
+        for (int c = 0; c < ch; ++c) sq += sq_part[s * ch + c];
+        x0_mse[(size_t)s * K + k] = sq * inv_n;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1954,7 +2142,11 @@ int vf_loss_weights_pred_host(const float* level, int B, int pred, int kind, flo
 }
 
 // ---- seeded draws (rng.h) ----
-static inline bool rng_args_ok(int kind, int step) { return kind >= 0 && kind <= 3 && step >= 0 && step < (1 << 28); }
+// (kinds 0..3, and 6 -- the noisy targets of the variational bound -- whose layout these two launches share; 4 and 5 have
+// launches of their own)
+static inline bool rng_args_ok(int kind, int step) {
+    return ((kind >= 0 && kind <= 3) || kind == VF_RNG_NLL_NOISE) && step >= 0 && step < (1 << 28);
+}
 
 int vf_draw_train(unsigned long long seed, const long long* ids, const float* gammas, int T, long long* t, float* u,
                   float* level, int B, void* stream) {
@@ -2429,6 +2621,88 @@ int vf_vlb_terms_host(const float* o, const float* hi, const float* lo, const fl
         lp[i] = vf_vlb_logvar(o[i], hi[i], lo[i]);
         kl[i] = vf_vlb_kl(lp[i], lo[i], m2);
         dkl[i] = vf_vlb_dkl(lp[i], lo[i], m2);
+    }
+    return 0;
+}
+
+// ---- the variational bound (the head of this file; vlb.h) ----
+// The noisy targets of step k = kidx[b] (DEVICE int64 [B]) of the chain tau (DEVICE int64 [K]) on the fp32 gammas [T]:
+// y_k [B][3][HW] = sqrt(g) y_0 + sqrt(1 - g) n, g = gammas[tau[k]].  noise (DEVICE [B][K][3][HW]) wins; with noise NULL
+// n is drawn from (seed, ids[b], kind 6, tau[k], float4 index).  Refused: a null y_0, kidx, tau, gammas or y_k, both noise
+// and ids null, HW % 4, HW <= 0, K < 1, T < 1 or T > 2^28.  B <= 0 returns 0 first.
+int vf_nll_noisy(const float* y_0, const float* noise, unsigned long long seed, const long long* ids,
+                 const long long* kidx, const long long* tau, const float* gammas, float* y_k, int B, int HW, int K,
+                 int T, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || HW <= 0 || K < 1 || T < 1 || T > (1 << 28) || !y_0 || !kidx || !tau || !gammas || !y_k ||
+        (!noise && !ids))
+        return (int)hipErrorInvalidValue;
+    const dim3 grid(chunks_for(3 * HW / 4), B), block(256);
+    if (noise)
+        hipLaunchKernelGGL(nll_noisy_kernel<false>, grid, block, 0, (hipStream_t)stream, y_0, noise, seed, ids, kidx, tau,
+                           gammas, y_k, HW, K, T);
+    else
+        hipLaunchKernelGGL(nll_noisy_kernel<true>, grid, block, 0, (hipStream_t)stream, y_0, noise, seed, ids, kidx, tau,
+                           gammas, y_k, HW, K, T);
+    VF_RETURN_LAST_ERROR();
+}
+
+// One term of the bound for every sample, at step k = kidx[b] (DEVICE int64 [B], clamped into [0, K - 1]) of the fp32
+// tables a, b, c0, hi, lo [K] (schedule.nll_tables): vb [B][K] and x0_mse [B][K] receive column k -- the mean over the
+// sample's 3 HW elements of the term in bits and of (y0 - y_0)^2.  lv: unet_out has nine channels and lp lies between
+// lo[k] and hi[k] by the composed channels 6..8; else lp = hi[k] where `large`, lo[k] otherwise.  dec: the decoder
+// likelihood instead of the KL (the caller's k == 0).  clip: y0 is clamped to [-1, 1].  vb_part, sq_part: [B * 64]
+// scratch.  Two launches, no atomics.  Refused: a null pointer, HW % 4, HW <= 0, K < 1, Cout < 3 (6 with weighting, 9
+// with lv), lv together with large.  B <= 0 returns 0 first.
+int vf_nll_terms(const float* unet_out, const int* off, const float* y_k, const float* y_0, const long long* kidx,
+                 const float* a, const float* b, const float* c0, const float* hi, const float* lo, float* vb_part,
+                 float* sq_part, float* vb, float* x0_mse, int B, int Cout, int HW, int K, int weighting, int clip, int lv,
+                 int dec, int large, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || HW <= 0 || K < 1 || Cout < (lv ? 9 : (weighting ? 6 : 3)) || (lv && large))
+        return (int)hipErrorInvalidValue;
+    if (!unet_out || !off || !y_k || !y_0 || !kidx || !a || !b || !c0 || !hi || !lo || !vb_part || !sq_part || !vb ||
+        !x0_mse)
+        return (int)hipErrorInvalidValue;
+    const int ch = chunks_for(3 * HW / 4);
+    auto kern = lv ? (dec ? nll_term_kernel<true, true> : nll_term_kernel<true, false>)
+                   : (dec ? nll_term_kernel<false, true> : nll_term_kernel<false, false>);
+    hipLaunchKernelGGL(kern, dim3(ch, B), dim3(256), 0, (hipStream_t)stream, unet_out, off, y_k, y_0, kidx, a, b, c0, hi,
+                       lo, vb_part, sq_part, Cout, HW, K, weighting, clip, large);
+    hipLaunchKernelGGL(nll_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream,
+                       (const float*)vb_part, (const float*)sq_part, kidx, vb, x0_mse, B, ch, K,
+                       1.0f / (float)(3 * HW));
+    VF_RETURN_LAST_ERROR();
+}
+
+// The prior term L_T of every sample, prior [B] in bits per dimension, from y_0 and gammas[T - 1]; part: [B * 64] scratch.
+// Refused: a null pointer, HW % 4, HW <= 0, T < 1.  B <= 0 returns 0 first.
+int vf_nll_prior(const float* y_0, const float* gammas, float* part, float* prior, int B, int HW, int T, void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || HW <= 0 || T < 1 || !y_0 || !gammas || !part || !prior) return (int)hipErrorInvalidValue;
+    const int ch = chunks_for(3 * HW / 4);
+    hipLaunchKernelGGL(nll_prior_kernel, dim3(ch, B), dim3(256), 0, (hipStream_t)stream, y_0, gammas, part, HW, T);
+    hipLaunchKernelGGL(nll_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)part,
+                       (const float*)nullptr, (const long long*)nullptr, prior, (float*)nullptr, B, ch, 1,
+                       1.0f / (float)(3 * HW));
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirror of one term (HOST pointers, no stream): element i of n has its own composed prediction out[i], raw variance
+// o[i] (read with lv alone; NULL otherwise), y_k[i], y_0[i] and table row (a, b, c0, hi, lo)[i]; term[i] in bits and
+// sq[i] = (y0 - y_0)^2 by the very function the kernel runs.  Refused: n < 0, lv together with large, and with n > 0 a null
+// pointer (o only with lv).
+int vf_nll_terms_host(const float* out, const float* o, const float* y_k, const float* y_0, const float* a,
+                      const float* b, const float* c0, const float* hi, const float* lo, int lv, int dec, int large,
+                      int clip, float* term, float* sq, int n) {
+    if (n < 0 || (lv && large)) return (int)hipErrorInvalidValue;
+    if (n > 0 && (!out || (lv && !o) || !y_k || !y_0 || !a || !b || !c0 || !hi || !lo || !term || !sq))
+        return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i) {
+        const NllRow row{a[i], b[i], c0[i], hi[i], lo[i]};
+        const float lp = lv ? vf_vlb_logvar(o[i], row.hi, row.lo) : (large ? row.hi : row.lo);
+        term[i] = dec ? nll_element<true>(row, out[i], lp, y_k[i], y_0[i], clip, &sq[i])
+                      : nll_element<false>(row, out[i], lp, y_k[i], y_0[i], clip, &sq[i]);
     }
     return 0;
 }

@@ -18,6 +18,9 @@
 //   kind 3  reverse-step noise z, step = the timestep index t[b]
 //   kind 4  batch assembly (the view store, batch_plan.h / batch.hip), step 0: see "Data draws" below
 //   kind 5  residual-block Dropout masks (elementwise.hip), step = (layer << 12) | view: see "Dropout masks" below
+//   kind 6  the noise of a noisy target in the evaluation of the variational bound (diffusion.hip, nll_noisy_kernel),
+//           step = the model timestep tau[k]: one Monte-Carlo draw per (sample, level), the same at a level whichever
+//           chain visits it, and never the noise a sampler (kinds 2, 3) or a training step (kind 1) gives that sample
 //
 // One Philox call gives four 32-bit words w0..w3.
 //   t = 1 + mulhi32(w0, T - 1)          in [1, T - 1] = the reference's randint(1, T); exact integer arithmetic
@@ -96,7 +99,7 @@
 #endif
 
 enum { VF_RNG_TRAIN_SCALARS = 0, VF_RNG_TRAIN_NOISE = 1, VF_RNG_START_NOISE = 2, VF_RNG_STEP_NOISE = 3, VF_RNG_DATA = 4,
-       VF_RNG_DROPOUT = 5 };
+       VF_RNG_DROPOUT = 5, VF_RNG_NLL_NOISE = 6 };
 
 VF_RNG_HD void vf_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]) {
     uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];

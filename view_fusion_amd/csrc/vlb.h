@@ -11,8 +11,15 @@
 //   KL   = 0.5 (((-1 + (lp - lo)) + expf(lo - lp)) + m2 expf(-lp)) / ln 2      in bits
 //   dKL / dlp = 0.5 ((1 - expf(lo - lp)) - m2 expf(-lp)) / ln 2
 //   dlp / do  = 0.5 (hi - lo)
-// Contraction is off inside every function here, so host and device round the same operations; expf is the accurate
-// library function on both sides (they agree to its last-place error).
+// The decoder term of the variational bound (the head of diffusion.hip, "Variational bound"; tests/nll_ref.py restates it):
+//   Phi(x) = 0.5 (1 + tanhf(sqrt(2/pi) (x + 0.044715 ((x x) x))))           (Improved DDPM's approx_standard_normal_cdf)
+//   is   = expf(-0.5 lp);  d = x - mean;  plus = is (d + 1/255);  minus = is (d - 1/255)
+//   ll   = logf(max(Phi(plus), 1e-12))                  where x < -0.999
+//          logf(max(1 - Phi(minus), 1e-12))             where x >  0.999
+//          logf(max(Phi(plus) - Phi(minus), 1e-12))     otherwise
+//   nll  = -ll / ln 2                                                          in bits
+// Contraction is off inside every function here, so host and device round the same operations; expf, logf and tanhf are
+// the accurate library functions on both sides (they agree to their last-place errors).
 #pragma once
 #include <math.h>
 
@@ -65,4 +72,29 @@ VF_VLB_HD float vf_vlb_dkl(float lp, float lo, float m2) {
     const float e2 = m2 * expf(-lp);
     const float s = (1.0f - e1) - e2;
     return (0.5f * s) * VF_VLB_INV_LN2;
+}
+
+// Phi(x), the tanh approximation of the standard normal distribution function
+VF_VLB_HD float vf_nll_cdf(float x) {
+#pragma clang fp contract(off)
+    const float x2 = x * x;
+    const float x3 = x2 * x;
+    const float c = 0.044715f * x3;
+    const float s = x + c;
+    const float u = 0.7978845608028654f * s;           // sqrt(2 / pi)
+    return 0.5f * (1.0f + tanhf(u));
+}
+
+// -log2 p(x | mean, lp): the discretised Gaussian likelihood of a pixel x in [-1, 1] with bins of +-1/255, in bits
+VF_VLB_HD float vf_nll_decoder(float x, float mean, float lp) {
+#pragma clang fp contract(off)
+    const float is = expf(-0.5f * lp);
+    const float d = x - mean;
+    const float plus = is * (d + 0.00392156862745098f);
+    const float minus = is * (d - 0.00392156862745098f);
+    float p;
+    if (x < -0.999f) p = vf_nll_cdf(plus);
+    else if (x > 0.999f) p = 1.0f - vf_nll_cdf(minus);
+    else p = vf_nll_cdf(plus) - vf_nll_cdf(minus);
+    return -(logf(fmaxf(p, 1e-12f)) * VF_VLB_INV_LN2);
 }

@@ -340,7 +340,7 @@ def _barrier():
 
 @torch.no_grad()
 def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ssim=False, seed=None, lpips=None,
-             guidance=None, threshold=None, threshold_max=None, guidance_rescale=None, **inject):
+             guidance=None, threshold=None, threshold_max=None, guidance_rescale=None, nll=False, **inject):
     """The eval reduction of Experiment.eval (experiment.py:314-370): every rank generates its shard of the validation
     batches (view_count ~ U[1, max_views] per sample), PSNR per image on the GPU (utils/metrics.py:6-8), mean over the
     rank's images, barrier, all_reduce(AVG) of the scalars, barrier.  `batches`: iterable of dicts with target (B,3,H,W),
@@ -358,7 +358,20 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ss
     guidance (default None: the unguided sampler): a classifier-free guidance scale for every generate() call -- which
     scale suits a checkpoint trained with set_cond_dropout is, likewise, what this function measures.
     threshold / threshold_max / guidance_rescale (default None: off): dynamic thresholding and guidance rescaling of
-    every generate() call (ViewFusion.generate) -- what keeps a sweep over g > 1 from measuring saturation alone."""
+    every generate() call (ViewFusion.generate) -- what keeps a sweep over g > 1 from measuring saturation alone.
+    nll=True (default False: today's launches and keys) adds "bpd", the variational bound of the targets in bits per
+    dimension on the full T-step chain (ViewFusion.bound_terms with the batch's view_count, seed and ids; bits_per_dim
+    below has the options and the per-step curves), through the same reduction.  ValueError together with guidance /
+    threshold / guidance_rescale (a guided model's "bound" is no bound) and for a model bound_terms refuses (a
+    self-conditioned or a CPU model), before the first generate() launches anything."""
+    if nll and (guidance is not None or threshold is not None or (guidance_rescale is not None and
+                                                                  float(guidance_rescale) > 0)):
+        raise ValueError("evaluate(nll=True) takes no guidance / threshold / guidance_rescale: the bound is that of the "
+                         "conditional model's own reverse process")
+    core = getattr(model, "module", model)
+    bpd = []
+    if nll:                                        # what bound_terms refuses is refused here, before the first generate()
+        core._check_bound(core.gammas.device)
     if guidance is not None:
         inject = dict(inject, guidance=guidance)
     for name, val in (("threshold", threshold), ("threshold_max", threshold_max), ("guidance_rescale", guidance_rescale)):
@@ -381,6 +394,9 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ss
             *_, samples = model(y_cond=b["cond"], view_count=vc, angle=b["angle"], generate=True, **inject)
             gen.append(samples)
             gt.append(b["target"])
+            if nll:
+                bpd.append(core.bound_terms(b["cond"], vc, b["angle"], b["target"], seed=seed,
+                                            sample_ids=inject.get("sample_ids") if seed is not None else None)["total_bpd"])
     _barrier()
     metrics = {"psnr": compute_psnr}
     if ssim:
@@ -389,6 +405,48 @@ def evaluate(model, batches, max_views=6, generator=None, extra_metrics=None, ss
         metrics["lpips"] = lambda a, t: compute_lpips(a, t, lpips)     # (a module global too, looked up at call time)
     metrics.update(extra_metrics or {})
     out = {k: torch.cat([fn(a, t) for a, t in zip(gen, gt)]).mean() for k, fn in metrics.items()}
+    if nll:
+        out["bpd"] = torch.cat(bpd).mean()
+    _barrier()
+    out = reduce_dict(out)
+    _barrier()
+    return out
+
+
+@torch.no_grad()
+def bits_per_dim(model, batches, seed=None, sample_steps=None, clip_denoised=True, fixed_variance="small"):
+    """The variational bound of held-out targets in bits per dimension (Improved DDPM's calc_bpd_loop on this engine):
+    every rank runs ViewFusion.bound_terms on its shard of `batches` -- the dicts of evaluate(): target (B,3,H,W), in the
+    model's own range [-1, 1], cond, angle and optionally view_count (default: every view of cond) and ids -- then mean
+    over the rank's images, barrier, all_reduce(AVG), barrier, as evaluate().  Returns the reduced dict {"bpd", "prior_bpd":
+    0-d tensors; "vb", "x0_mse", "eps_mse": (K,) curves over the steps of the chain}: vb[k] is the term of step k (the
+    decoder at k = 0), x0_mse / eps_mse the error of the recovered image / noise at that level -- the validation curve.
+    seed (default None: torch's device generator): the noisy targets come from the counter-based generator keyed by
+    batch["ids"] (kind 6, csrc/rng.h), so an image's terms do not depend on how the set is batched or sharded; without
+    "ids" a running index over this rank's images is used, as in evaluate().
+    sample_steps (default None: all T steps): the bound of the K-step stochastic chain -- what a strided chain loses.
+    clip_denoised / fixed_variance: ViewFusion.bound_terms."""
+    core = getattr(model, "module", model)
+    keys = ("total_bpd", "prior_bpd", "vb", "x0_mse", "eps_mse")
+    got = {k: [] for k in keys}
+    seen = 0
+    for b in batches:
+        n = b["target"].shape[0]
+        vc = b.get("view_count")
+        if vc is None:
+            vc = [b["cond"].shape[1]] * n
+        ids = None
+        if seed is not None:
+            ids = b.get("ids")
+            if ids is None:
+                ids = torch.arange(seen, seen + n)
+        seen += n
+        terms = core.bound_terms(b["cond"], vc, b["angle"], b["target"], seed=seed, sample_ids=ids,
+                                 sample_steps=sample_steps, clip_denoised=clip_denoised, fixed_variance=fixed_variance)
+        for k in keys:
+            got[k].append(terms[k])
+    _barrier()
+    out = {("bpd" if k == "total_bpd" else k): torch.cat(v).mean(dim=0) for k, v in got.items()}
     _barrier()
     out = reduce_dict(out)
     _barrier()

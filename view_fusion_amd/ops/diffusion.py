@@ -1078,6 +1078,117 @@ def self_cond_estimate(unet_out, off, level, B, weighting, prediction="eps", x=N
     return x_hat
 
 
+# ---- the variational bound in bits per dimension (csrc/diffusion.hip holds the definition) ----
+RNG_NLL_NOISE = 6                                                  # the kind of a noisy target's draw (csrc/rng.h)
+NLL_TABLE_NAMES = ("a", "b", "c0", "hi", "lo")
+
+
+def nll_scratch(B, device):
+    """What nll_terms / nll_prior keep between their two launches: the per-(sample, chunk) partial sums."""
+    return {"vb": torch.empty(B * 64, device=device, dtype=torch.float32),
+            "sq": torch.empty(B * 64, device=device, dtype=torch.float32)}
+
+
+def nll_noisy(y_0, kidx, tau, gammas, noise=None, seed=None, ids=None, out=None):
+    """The noisy targets of step k = kidx[b] of the chain tau (device int64 (K,)) on the fp32 `gammas` buffer:
+    y_k = sqrt(g) y_0 + sqrt(1 - g) n, g = gammas[tau[k]].  noise (B, K, 3, H, W) wins; else n is drawn in the kernel from
+    (seed, ids[b], kind 6, tau[k], element).  One launch; with out= no allocation."""
+    _check(y_0, gammas, noise, out)
+    B, _, H, W = y_0.shape
+    K = tau.numel()
+    _check_i64("kidx", kidx, B)
+    _check_i64("tau", tau, K)
+    if noise is None and seed is None:
+        raise ValueError("nll_noisy needs noise= or seed=")
+    if noise is not None and tuple(noise.shape) != (B, K, 3, H, W):
+        raise ValueError(f"noise must have shape {(B, K, 3, H, W)}, got {tuple(noise.shape)}")
+    if out is None:
+        out = torch.empty_like(y_0)
+    elif tuple(out.shape) != tuple(y_0.shape):
+        raise ValueError(f"out must have y_0's shape {tuple(y_0.shape)}, got {tuple(out.shape)}")
+    sd, idp = 0, None
+    if noise is None:
+        ids = sample_ids(y_0.device, B, ids)
+        _check_ids(ids, B)
+        sd, idp = _seed(seed), ctypes.c_void_p(ids.data_ptr())
+    _call("vf_nll_noisy", _ptr(y_0), _ptr(noise), sd, idp, ctypes.c_void_p(kidx.data_ptr()),
+          ctypes.c_void_p(tau.data_ptr()), _ptr(gammas), _ptr(out), B, H * W, K, gammas.numel(), _stream())
+    return out
+
+
+def nll_terms(unet_out, off, y_k, y_0, kidx, tables, B, weighting, learned=False, decoder=False, large=False, clip=True,
+              out=None, scratch=None):
+    """One term of the bound for every sample at step k = kidx[b] (device int64 (B,)): column k of vb (B, K), the term in
+    bits per dimension, and of x0_mse (B, K), the mean of (y0 - y_0)^2.  tables: the fp32 device tables a, b, c0, hi, lo
+    (K,) of schedule.nll_tables.  learned: a nine-channel unet_out whose composed channels 6..8 place lp between lo[k] and
+    hi[k]; else lp = hi[k] where large, lo[k] otherwise.  decoder: the discretised likelihood (the caller's k == 0)
+    instead of the KL.  out=(vb, x0_mse) and scratch=nll_scratch(B, device): no allocation.  Two launches."""
+    tabs = [tables[n] for n in NLL_TABLE_NAMES]
+    _check(unet_out, y_k, y_0, *tabs)
+    K = tabs[0].numel()
+    if any(t.numel() != K for t in tabs) or K < 1:
+        raise ValueError(f"nll_terms needs a, b, c0, hi and lo of one length, got {[t.numel() for t in tabs]}")
+    if learned:
+        _check_nine("nll_terms(learned=True)", unet_out)
+        if large:
+            raise ValueError("fixed_variance='large' on a learned variance: the model has its own")
+    _, Cout, H, W = unet_out.shape
+    if tuple(y_k.shape) != (B, 3, H, W) or tuple(y_0.shape) != (B, 3, H, W):
+        raise ValueError(f"nll_terms needs y_k and y_0 of shape {(B, 3, H, W)}")
+    _check_i64("kidx", kidx, B)
+    if out is None:
+        out = (torch.zeros(B, K, device=y_0.device, dtype=torch.float32),
+               torch.zeros(B, K, device=y_0.device, dtype=torch.float32))
+    vb, mse = out
+    _check(vb, mse)
+    if tuple(vb.shape) != (B, K) or tuple(mse.shape) != (B, K):
+        raise ValueError(f"out= needs two tensors of shape {(B, K)}")
+    if scratch is None:
+        scratch = nll_scratch(B, y_0.device)
+    if scratch["vb"].numel() < B * 64 or scratch["sq"].numel() < B * 64:
+        raise ValueError(f"scratch= holds fewer than {B * 64} partial sums")
+    _call("vf_nll_terms", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_k), _ptr(y_0),
+          ctypes.c_void_p(kidx.data_ptr()), *(_ptr(t) for t in tabs), _ptr(scratch["vb"]), _ptr(scratch["sq"]), _ptr(vb),
+          _ptr(mse), B, Cout, H * W, K, int(bool(weighting)), int(bool(clip)), int(bool(learned)), int(bool(decoder)),
+          int(bool(large)), _stream())
+    return vb, mse
+
+
+def nll_prior(y_0, gammas, out=None, scratch=None):
+    """The prior term L_T of every sample, (B,) in bits per dimension: the KL of q(y_T | y_0) from N(0, I) at
+    gammas[T - 1]; exactly 0 on a zero-terminal-SNR schedule.  out= and scratch=: no allocation.  Two launches."""
+    _check(y_0, gammas, out)
+    B, _, H, W = y_0.shape
+    if out is None:
+        out = torch.empty(B, device=y_0.device, dtype=torch.float32)
+    elif out.numel() != B:
+        raise ValueError(f"out= needs {B} elements")
+    if scratch is None:
+        scratch = nll_scratch(B, y_0.device)
+    if scratch["vb"].numel() < B * 64:
+        raise ValueError(f"scratch= holds fewer than {B * 64} partial sums")
+    _call("vf_nll_prior", _ptr(y_0), _ptr(gammas), _ptr(scratch["vb"]), _ptr(out), B, H * W, gammas.numel(), _stream())
+    return out
+
+
+def nll_terms_host(out, o, y_k, y_0, a, b, c0, hi, lo, learned=False, decoder=False, large=False, clip=True):
+    """The host mirror of one term of the bound: float tensors / sequences of one length (o: None unless learned) ->
+    (term in bits, (y0 - y_0)^2) float32 CPU tensors, per element, by the function the kernel runs.  No GPU."""
+    names = (out, y_k, y_0, a, b, c0, hi, lo) + ((o,) if learned else ())
+    arrs = [torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1).contiguous() for v in names]
+    n = arrs[0].numel()
+    if any(v.numel() != n for v in arrs):
+        raise ValueError("nll_terms_host needs inputs of one length")
+    outs = [torch.empty(n, dtype=torch.float32) for _ in range(2)]
+    p = lambda v: ctypes.c_void_p(v.data_ptr())                     # noqa: E731
+    rc = _lib.load().vf_nll_terms_host(p(arrs[0]), p(arrs[8]) if learned else None, *(p(v) for v in arrs[1:8]),
+                                       int(bool(learned)), int(bool(decoder)), int(bool(large)), int(bool(clip)),
+                                       p(outs[0]), p(outs[1]), n)
+    if rc != 0:
+        raise _lib.VFHipError(f"vf_nll_terms_host failed with {rc}")
+    return tuple(outs)
+
+
 def psnr(generated, target):
     """Per-image PSNR (B,) of (B,C,H,W) tensors in [0,1]."""
     generated, target = _c(generated), _c(target)

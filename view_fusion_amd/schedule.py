@@ -204,6 +204,47 @@ def variance_tables(betas, tau=None):
         return np.log(beta), np.log(np.maximum(beta * (1.0 - gp) / (1.0 - gt), 1e-20))
 
 
+# ---- the variational bound: the rows a term of the bound reads (csrc/diffusion.hip, "Variational bound") -------------
+FIXED_VARIANCES = ("small", "large")
+
+
+def nll_tables(betas, tau=None, prediction="eps", fixed_variance="small"):
+    """float64 betas (T,), tau (K,) (default 0..T-1) -> {a, b, c0, hi, lo}: float64 (K,) each (rounded to fp32 once, by the
+    caller).  With gt = gammas[tau[k]], gp = gammas[tau[k-1]] (1 at k = 0): a, b = prediction_tables gathered at tau;
+    c0[k] = sqrt(gp) (1 - gt/gp) / (1 - gt), the weight of y0 in the posterior mean; hi, lo = variance_tables.  On the full
+    chain these are schedule_tensors' own expressions, so rows k >= 1 equal posterior_mean_coef1, log(betas) and
+    posterior_log_variance_clipped value for value.  Row 0 is the decoder's: hi[0] = log(1 - gammas[tau[0]]) and lo[0] =
+    lo[1], the log posterior variance of step 1 (not the 1e-20 clipping, under which the likelihood degenerates);
+    a one-step chain has lo[0] = hi[0]; fixed_variance="large" (lp = hi) reads lo[0] at k = 0 as well, so its hi[0] = lo[0].
+    ValueError for an eps model on a level with gamma = 0, as sampler_tables."""
+    if fixed_variance not in FIXED_VARIANCES:
+        raise ValueError(f"unknown fixed_variance {fixed_variance!r}: one of {FIXED_VARIANCES}")
+    betas = np.asarray(betas, dtype=np.float64)
+    T = betas.shape[0]
+    gammas = np.cumprod(1.0 - betas, axis=0)
+    full = tau is None or np.array_equal(np.asarray(tau), np.arange(T))
+    tau = np.arange(T, dtype=np.int64) if full else np.asarray(tau, dtype=np.int64)
+    gt = gammas[tau]
+    if check_prediction(prediction) == "eps" and (gt == 0).any():
+        raise ValueError("an eps-prediction model cannot sample from a level with gamma = 0 (zero terminal SNR): "
+                         "g^-1/2 is infinite there; use prediction 'v' or 'x0'")
+    pa, pb = prediction_tables(betas, prediction)
+    hi, lo = variance_tables(betas, None if full else tau)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if full:                                   # schedule_tensors' very expression for posterior_mean_coef1
+            prev = np.append(1.0, gammas[:-1])
+            c0 = betas * np.sqrt(prev) / (1.0 - gammas)
+        else:
+            gp = np.append(1.0, gt[:-1])
+            c0 = np.sqrt(gp) * (1.0 - gt / gp) / (1.0 - gt)
+        hi, lo = hi.copy(), lo.copy()
+        hi[0] = np.log(1.0 - gt[0])
+        lo[0] = lo[1] if tau.shape[0] > 1 else hi[0]
+    if fixed_variance == "large":
+        hi[0] = lo[0]
+    return {"a": pa[tau], "b": pb[tau], "c0": c0, "hi": hi, "lo": lo}
+
+
 # ---- progressive distillation: the grids and the target weights of a K-step student of a 2K-step teacher ------------
 def distill_tables(betas, K, teacher_prediction="eps"):
     """float64 betas (T,), K student steps -> {tau_s (K,), tau_t (2K,) int64; w1, w2 float64 (K,); teacher, student: the two

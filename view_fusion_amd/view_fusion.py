@@ -572,6 +572,7 @@ class ViewFusion(nn.Module):
         self._plan = None
         self._pred_tabs = None
         self._lv_tabs = None
+        self._nll_plan = None                  # the tables of a bound evaluation (bound_terms), made on demand
         for name, val in _schedule.schedule_tensors(betas, device).items():
             if name in self._buffers:
                 self._buffers[name] = val
@@ -871,6 +872,109 @@ class ViewFusion(nn.Module):
         return y, ret, logit_arr, weight_arr, samples
 
     sample = generate
+
+    # -- the variational bound -----------------------------------------------------------------
+    def _nll_plan_for(self, tau, fixed_variance, dev):
+        """The device side of a bound evaluation: the fp32 tables of schedule.nll_tables, `tau` as int64, `level` = the
+        fp32 `gammas` buffer gathered at tau and `snr` = level / (1 - level) (formed in float64, rounded once).  The
+        last plan is kept (bits_per_dim asks for the same one per batch)."""
+        key = (tuple(int(v) for v in tau), self.prediction, fixed_variance, dev)
+        plan = getattr(self, "_nll_plan", None)
+        if plan is None or plan[0] != key:
+            tab = _schedule.nll_tables(self.betas64, tau, self.prediction, fixed_variance)
+            new = {k: torch.tensor(v, dtype=torch.float32, device=dev) for k, v in tab.items()}
+            new["tau"] = torch.tensor(list(key[0]), dtype=torch.int64, device=dev)
+            new["level"] = self.gammas[new["tau"]].contiguous()
+            g = new["level"].double()
+            new["snr"] = (g / (1.0 - g)).float()
+            plan = self._nll_plan = (key, new)
+        return plan[1]
+
+    def _check_bound(self, dev, fixed_variance="small", guidance=None, threshold=None, guidance_rescale=None):
+        """ValueError, before any launch, where the bound cannot be evaluated (bound_terms; drivers.evaluate(nll=True)
+        asks before its first generate()): `dev` is where the targets live."""
+        if guidance is not None or threshold is not None or \
+                (guidance_rescale is not None and float(guidance_rescale) > 0):
+            raise ValueError("bound_terms takes no guidance / threshold / guidance_rescale: the bound is that of the "
+                             "conditional model's own reverse process (DESIGN 8)")
+        if self._self_cond_p is not None:
+            raise ValueError("the bound of a self-conditioned model is not built (DESIGN 8): its reverse step depends on "
+                             "the chain's own history")
+        if fixed_variance not in _schedule.FIXED_VARIANCES:
+            raise ValueError(f"unknown fixed_variance {fixed_variance!r}: one of {_schedule.FIXED_VARIANCES}")
+        if self._lv_weight is not None and fixed_variance == "large":
+            raise ValueError("fixed_variance='large' on a model with a learned variance: the model has its own")
+        if torch.device(dev).type != "cuda" or self.gammas.device.type != "cuda":
+            raise ValueError("bound_terms runs on the GPU only (its terms are HIP kernels): move the model and the batch "
+                             "there")
+        if self._lv_weight is not None:
+            self._check_lv(dev)
+
+    @torch.no_grad()
+    def bound_terms(self, y_cond, view_count, angle, y_0, noise=None, seed=None, sample_ids=None, sample_steps=None,
+                    clip_denoised=True, fixed_variance="small", guidance=None, threshold=None, guidance_rescale=None):
+        """The variational bound on -log2 p(y_0) of held-out targets, term by term, in bits per dimension (Improved
+        DDPM's calc_bpd_loop on this engine; csrc/diffusion.hip holds the definition).  For every step k of the chain
+        -- 0..T-1, or sample_steps (K, or an explicit sequence: schedule.sample_timesteps) -- one noisy target y_k per
+        sample, one no-grad forward on the inference path at the level gammas[tau[k]] (no Dropout, whatever mode the model
+        is in) and one term: the KL of the true posterior from the model's reverse step for k >= 1, the discretised decoder
+        likelihood at k = 0; plus the prior term.  The model's variance: learned (set_learned_variance on a nine-channel
+        network), else fixed_variance "small" (the posterior variance, what the ancestral sampler uses) or "large" (beta).
+        noise (B, K, 3, H, W) wins; else seed= draws it from the counter-based generator (kind 6, keyed by sample_ids and
+        the model timestep, so a sample's targets do not depend on its batch); else torch's device generator.
+        Returns {"total_bpd" (B,), "prior_bpd" (B,), "vb" (B, K), "x0_mse" (B, K), "eps_mse" (B, K), "tau" (K,)}: device
+        tensors, no host sync inside the loop; x0_mse is the mean of (y0 - y_0)^2 and eps_mse = x0_mse g / (1 - g).
+        Launched eagerly, launch by launch (a captured step is not built).  Refused with ValueError before any launch:
+        guidance / threshold / guidance_rescale (a guided model's "bound" is no bound), a self-conditioned model,
+        fixed_variance="large" on a learned variance, a CPU model.  A nine-channel network with the learned variance off
+        is evaluated as a fixed variance; channels 6..8 are ignored, as the samplers do."""
+        from . import ops
+        dev = y_0.device
+        self._check_bound(dev, fixed_variance, guidance, threshold, guidance_rescale)
+        lv = self._lv_weight is not None
+        b, _, H, W = y_0.shape
+        T = self.num_timesteps
+        tau = list(range(T)) if sample_steps is None else _schedule.sample_timesteps(T, sample_steps).tolist()
+        K = len(tau)
+        if noise is not None and tuple(noise.shape) != (b, K, 3, H, W):
+            raise ValueError(f"noise must have shape {(b, K, 3, H, W)}, got {tuple(noise.shape)}")
+        if tuple(y_cond.shape[-2:]) != (H, W) or y_cond.shape[0] != b:
+            raise ValueError(f"y_cond {tuple(y_cond.shape)} does not go with y_0 {tuple(y_0.shape)}")
+        plan = self._nll_plan_for(tau, fixed_variance, dev)      # (ValueError: "eps" at a level with gamma = 0)
+        ids = None if seed is None or noise is not None else ops.sample_ids(dev, b, sample_ids)
+        off, S, _ = ops.view_offsets(view_count, dev)
+        y_0, y_cond, angle = y_0.contiguous(), y_cond.contiguous(), angle.contiguous()
+        w_on = bool(self.weighting_inference)
+        kidx = torch.zeros(b, device=dev, dtype=torch.int64)
+        vb = torch.zeros(b, K, device=dev, dtype=torch.float32)
+        mse = torch.zeros(b, K, device=dev, dtype=torch.float32)
+        scratch = ops.nll_scratch(b, dev)
+        y_k = torch.empty_like(y_0)
+        draw = dict(noise=noise.contiguous()) if noise is not None else dict(seed=seed, ids=ids)
+        z = zero = None
+        if noise is None and seed is None:                       # torch's device generator: one step's draw at a time
+            z = torch.empty(b, 1, 3, H, W, device=dev, dtype=torch.float32)
+            zero = torch.zeros(b, device=dev, dtype=torch.int64)
+        x = None
+        was = self.denoise_fn.training if isinstance(self.denoise_fn, nn.Module) else None
+        if was:
+            self.denoise_fn.eval()
+        try:
+            for k in reversed(range(K)):
+                kidx.fill_(k)
+                if z is not None:
+                    ops.nll_noisy(y_0, zero, plan["tau"][k:k + 1], self.gammas, noise=z.normal_(), out=y_k)
+                else:
+                    ops.nll_noisy(y_0, kidx, plan["tau"], self.gammas, out=y_k, **draw)
+                x, out = self._denoise(y_k, y_cond, angle, kidx, off, S, x=x, copy_cond=x is None, levels=plan["level"])
+                ops.nll_terms(out, off, y_k, y_0, kidx, plan, b, w_on, learned=lv, decoder=k == 0,
+                              large=fixed_variance == "large", clip=clip_denoised, out=(vb, mse), scratch=scratch)
+        finally:
+            if was:
+                self.denoise_fn.train(True)
+        prior = ops.nll_prior(y_0, self.gammas, scratch=scratch)
+        return {"total_bpd": prior + vb.sum(dim=1), "prior_bpd": prior, "vb": vb, "x0_mse": mse,
+                "eps_mse": mse * plan["snr"], "tau": plan["tau"]}
 
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
