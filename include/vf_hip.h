@@ -662,6 +662,16 @@ int vf_nll_prior(const float* y_0, const float* gammas, float* part, float* prio
 int vf_nll_terms_host(const float* out, const float* o, const float* y_k, const float* y_0, const float* a,
                       const float* b, const float* c0, const float* hi, const float* lo, int lv, int dec, int large,
                       int clip, float* term, float* sq, int n);
+/* ---- the analytic variance (csrc/diffusion.hip holds the definition): estimation only, one new kernel.  kidx: DEVICE
+ *      int64 [B], clamped into [0, K - 1]; the fp32 tables ea, eb [K] are schedule.eps_tables'. ---- */
+/* column k of m2 [B][K]: the mean over 3 HW elements of (ea[k] y_k + eb[k] out_b)^2, out_b the composition of channels
+ * 0..2 over the sample's views; part: [B * 64] scratch.  Two launches, no atomics. */
+int vf_eps_moments(const float* unet_out, const int* off, const float* y_k, const long long* kidx, const float* ea,
+                   const float* eb, float* part, float* m2, int B, int Cout, int HW, int K, int weighting,
+                   void* stream);
+/* Host mirror of one element (HOST pointers, no stream): eps[i] = ea[i] y_k[i] + eb[i] out[i], sq[i] = eps[i]^2 */
+int vf_eps_moment_host(const float* out, const float* y_k, const float* ea, const float* eb, float* eps, float* sq,
+                       int n);
 
 /* ---- batch assembly from a device-resident view store (csrc/batch.hip; data.ViewStore): the reference loader's
  *      process_sample + collate + H2D, data/nmr_dataset.py:10-52, as one launch.  store: planar uint8 [N][24][3][H][W],

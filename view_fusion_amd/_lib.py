@@ -194,6 +194,8 @@ SIGNATURES = {
     "vf_nll_terms": [_P] * 14 + [_I] * 9 + [_P],
     "vf_nll_prior": [_P, _P, _P, _P, _I, _I, _I, _P],
     "vf_nll_terms_host": [_P] * 9 + [_I, _I, _I, _I, _P, _P, _I],
+    "vf_eps_moments": [_P] * 8 + [_I] * 5 + [_P],
+    "vf_eps_moment_host": [_P] * 6 + [_I],
     "vf_rng_host_philox": [_P, _P, _P],
     "vf_rng_host_normal": [_U64, _P, _I, _I, _P, _I, _I],
     "vf_rng_host_train_scalars": [_U64, _P, _I, _P, _P, _I],

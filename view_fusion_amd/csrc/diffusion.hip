@@ -55,6 +55,8 @@
 //                   sibling), behind the self-conditioning kernels; the hybrid loss is the loss family's LV switch, above.
 //   the bound       nll_noisy_kernel<RNG>, nll_term_kernel<LV, DEC>, nll_prior_kernel, nll_finish_kernel: the terms of the
 //                   variational bound in bits per dimension (evaluation only), behind the loss family's launch tables.
+//   analytic variance  eps_moment_kernel (nll_term_kernel's sibling; its finish step is nll_finish_kernel): the second
+//                   moment of the recovered noise per (sample, level), behind the bound's kernels.
 //   C ABI           one extern "C" entry point per path (include/vf_hip.h).  The twelve tail entries vf_p_sample_tail* /
 //                   vf_sampler_step* {"", _cfg, _eps} x {"", _rng} each name one instantiation and forward to the one
 //                   launcher of their flavour (p_sample_tail, sampler_step), which holds the argument check.  The seven
@@ -246,6 +248,37 @@
 //   Reduction.  Two partial sums per (b, chunk) by block_sum<256>, then one thread per sample adds its partials in index
 //     order: no atomics, the same bits on every run and for every batch the sample stands in.
 //   Not built: a captured K-step loop, a guided bound, level resampling on L_vlb.
+//
+// Analytic variance (Bao et al., "Analytic-DPM", ICLR 2022, Theorem 1 and section 5): the KL-optimal variance of the
+// reverse step of any chain, for a pretrained six-channel model, without training.  This comment is the ONE written
+// definition; tests/analytic_ref.py restates it.  Opt-in and additive: one new kernel (eps_moment_kernel; its finish step
+// is nll_finish_kernel, unchanged), behind the bound's kernels; nothing above changes.
+//   Chain.  tau of K steps, gt = gammas[tau[k]], gp = gammas[tau[k-1]] (1 at k = 0), as the bound.
+//   Noise estimate, per element.  e = ea[k] y_k + eb[k] out_b: each product rounded, then added, contraction off.
+//     out_b = compose4 over the sample's real views of channels 0..2 (softmax of 3..5, or the mean); channels 6..8 of a
+//     nine-channel output are ignored.  (ea, eb) = schedule.eps_tables at tau, formed in float64 and rounded to fp32 once:
+//       eps: (0, 1)      v: (sqrt(1 - g), sqrt(g))      x0: (1 / sqrt(1 - g), -sqrt(g / (1 - g)))
+//     so for eps e is `out` to the bit.  No clamp: the theorem is about the model's raw mean.
+//   Moment.  m2[b, k] = the mean of e^2 over the sample's 3 H W elements (one block_sum<256> partial per (b, chunk), then
+//     one thread per sample adds its partials in index order: no atomics, the same bits on every run and for every batch
+//     the sample stands in).  M[t] = the mean of m2 over samples and draws at t = tau[k], in float64, on the host side of
+//     the driver (drivers.estimate_moments).  The noisy targets are the bound's (nll_noisy_kernel, Philox kind 6).
+//   Optimal variance.  With lambda^2[k] = sigma[k]^2 and c0[k] of schedule.sampler_tables(betas, tau, "ddim", eta) and
+//     Mc = clip(M[tau[k]], 0, 1):
+//       sigma*^2[k] = lambda^2[k] + c0[k]^2 (1 - gt) / gt (1 - Mc)
+//     -- the paper's lambda^2 + (sqrt(bbar_n / a_n) - sqrt(bbar_{n-1} - lambda^2))^2 (1 - bbar_n Gamma_n) in these tables.
+//     The clip is the paper's Theorem 2: lambda^2 <= sigma*^2 <= lambda^2 + c0^2 (1 - gt) / gt.  Sampling sets
+//     sigma*[0] = 0 (the last step returns its mean).  ValueError for a level with gamma = 0 (0 times inf) and for a NaN
+//     (not estimated) moment at a level the chain uses.  All of it float64 on the host (schedule.analytic_sigma2): the
+//     reverse step reads sigma*[k] where it read sigma[k], sampler_step_kernel unchanged.
+//   Bound.  fixed_variance="analytic": hi[k] = log sigma*^2[k] at eta = 1, where lambda^2 is the chain's posterior variance
+//     and c0 is nll_tables' own; hi[0], the decoder row, = log max(sigma*^2[0], exp(lo_dec)); lo[k] stays the true
+//     posterior's.  nll_term_kernel runs as it does for "large".
+//   Optimal trajectory (section 5).  J(r, s) = log(sigma*^2(r, s) / lambda^2(r, s)) at eta = 1 for a step from s down to
+//     r < s; schedule.optimal_trajectory minimises sum_{k >= 1} J(tau[k-1], tau[k]) over strictly increasing tau with
+//     tau[0] = first, tau[K-1] = T-1 by dynamic programming in float64.
+//   Not built: a captured estimation loop, moments of a guided model, a draw kind of its own (use another seed than for
+//     the bound on the same images), SN-DPM.
 #include "common.h"
 #include "level_sampler.h"
 #include "loss_weight.h"
@@ -1902,6 +1935,47 @@ __global__ __launch_bounds__(64) void nll_finish_kernel(const float* __restrict_
     }
 }
 
+// ---- the analytic variance (the head of this file holds the definition) ----
+// One element of the noise estimate: e = ea y + eb out, both products rounded, then added; returns e^2.  The kernel and
+// the host mirror (vf_eps_moment_host) both run this very function.
+__host__ __device__ inline float eps_moment_element(float ea, float eb, float out, float y, float* eps) {
+#pragma clang fp contract(off)
+    const float ay = ea * y;
+    const float bo = eb * out;
+    const float e = ay + bo;
+    *eps = e;
+    return e * e;
+}
+
+// The sum of e^2 per (b, chunk): nll_term_kernel's geometry and composition (channels 0..2 under the softmax of 3..5, or
+// the mean; channels 6.. are never read), the row k = kidx[b] of the two tables, one partial sum.
+__global__ __launch_bounds__(256) void eps_moment_kernel(const float* __restrict__ out, const int* __restrict__ off,
+                                                         const float* __restrict__ y_k,
+                                                         const long long* __restrict__ kidx,
+                                                         const float* __restrict__ tea, const float* __restrict__ teb,
+                                                         float* __restrict__ part, int Cout, int HW, int K,
+                                                         int weighting) {
+    __shared__ float red[4];
+    const int b = blockIdx.y;
+    const int v0 = off[b], v1 = off[b + 1];
+    const int n4 = 3 * HW / 4;
+    const long long k = nll_step(kidx, b, K);
+    const float ea = tea[k], eb = teb[k];
+    float acc = 0.f;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
+        const int c = (4 * i) / HW, p = 4 * i - c * HW;
+        const float4 e = compose4(out, Cout, HW, v0, v1, c, p, weighting, nullptr, nullptr);
+        const float4 y = *reinterpret_cast<const float4*>(y_k + (size_t)b * 3 * HW + 4 * (size_t)i);
+        const float es[4] = {e.x, e.y, e.z, e.w}, ys[4] = {y.x, y.y, y.z, y.w};
+        float t[4], eps;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = eps_moment_element(ea, eb, es[j], ys[j], &eps);
+        acc += (t[0] + t[1]) + (t[2] + t[3]);
+    }
+    acc = block_sum<256>(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2704,6 +2778,37 @@ int vf_nll_terms_host(const float* out, const float* o, const float* y_k, const 
         term[i] = dec ? nll_element<true>(row, out[i], lp, y_k[i], y_0[i], clip, &sq[i])
                       : nll_element<false>(row, out[i], lp, y_k[i], y_0[i], clip, &sq[i]);
     }
+    return 0;
+}
+
+// ---- the analytic variance (the head of this file) ----
+// The second moment of the noise estimate of every sample at step k = kidx[b] (DEVICE int64 [B], clamped into
+// [0, K - 1]) of the fp32 tables ea, eb [K] (schedule.eps_tables): m2 [B][K] receives column k -- the mean over the
+// sample's 3 HW elements of (ea[k] y_k + eb[k] out_b)^2, out_b the composition of channels 0..2 over the sample's views.
+// part: [B * 64] scratch.  Two launches (the second is the bound's finish kernel), no atomics.  Refused: a null pointer,
+// HW % 4, HW <= 0, K < 1, Cout < 3 (6 with weighting).  B <= 0 returns 0 first.
+int vf_eps_moments(const float* unet_out, const int* off, const float* y_k, const long long* kidx, const float* ea,
+                   const float* eb, float* part, float* m2, int B, int Cout, int HW, int K, int weighting,
+                   void* stream) {
+    if (B <= 0) return 0;
+    if ((HW & 3) || HW <= 0 || K < 1 || Cout < (weighting ? 6 : 3)) return (int)hipErrorInvalidValue;
+    if (!unet_out || !off || !y_k || !kidx || !ea || !eb || !part || !m2) return (int)hipErrorInvalidValue;
+    const int ch = chunks_for(3 * HW / 4);
+    hipLaunchKernelGGL(eps_moment_kernel, dim3(ch, B), dim3(256), 0, (hipStream_t)stream, unet_out, off, y_k, kidx, ea,
+                       eb, part, Cout, HW, K, weighting);
+    hipLaunchKernelGGL(nll_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, (const float*)part,
+                       (const float*)nullptr, kidx, m2, (float*)nullptr, B, ch, K, 1.0f / (float)(3 * HW));
+    VF_RETURN_LAST_ERROR();
+}
+
+// Host mirror of one element of the moment (HOST pointers, no stream): element i of n has its own composed prediction
+// out[i], y_k[i] and table row (ea, eb)[i]; eps[i] = the noise estimate and sq[i] = its square, by the very function the
+// kernel runs.  Refused: n < 0, and with n > 0 a null pointer.
+int vf_eps_moment_host(const float* out, const float* y_k, const float* ea, const float* eb, float* eps, float* sq,
+                       int n) {
+    if (n < 0) return (int)hipErrorInvalidValue;
+    if (n > 0 && (!out || !y_k || !ea || !eb || !eps || !sq)) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; ++i) sq[i] = eps_moment_element(ea[i], eb[i], out[i], y_k[i], &eps[i]);
     return 0;
 }
 

@@ -47,8 +47,8 @@ def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None
     experiment.py:472-488.
     cond (B,23,3,H,W), angle (B,1) -> (generated_batch (B,1+k,3,H,W), logit_arr, weight_arr, view_count).
     **inject reaches generate(): y_t, z_seq, seed, sample_ids, use_graph, sample_steps / solver / eta for a
-    few-step chain, guidance (a classifier-free guidance scale, or one per sample) and threshold / threshold_max /
-    guidance_rescale (ViewFusion.generate)."""
+    few-step chain, guidance (a classifier-free guidance scale, or one per sample), threshold / threshold_max /
+    guidance_rescale and variance ("analytic") (ViewFusion.generate)."""
     B = cond.shape[0]
     if view_count is None:
         view_count = torch.randint(max_views + 1, 24, (B,), generator=generator)
@@ -61,7 +61,7 @@ def extrapolate(model, cond, angle, max_views=6, view_count=None, generator=None
 @torch.no_grad()
 def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, seed=None, sample_ids=None,
                            sample_steps=None, solver="ddim", eta=0.0, guidance=None, threshold=None,
-                           threshold_max=None, guidance_rescale=None):
+                           threshold_max=None, guidance_rescale=None, variance=None):
     """Start from ONE view and synthesise the orbit view by view, feeding every sample back as an
     extra conditioning view (count = 1 .. steps; angle = 2*pi/24 * count), experiment.py:516-544.
     first_view (B,3,H,W) -> samples (B,steps,3,H,W).  y_t / z_seq: per-count lists of injected randomness.
@@ -69,7 +69,8 @@ def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, se
     defaults to arange(B)), so every step of every object has noise of its own, independent of the batch.
     sample_steps / solver / eta: the few-step sampler of every generate() call (`steps` is the rollout length).
     guidance: the classifier-free guidance scale of every generate() call (a number, or one per object).
-    threshold / threshold_max / guidance_rescale: likewise, of every generate() call (ViewFusion.generate)."""
+    threshold / threshold_max / guidance_rescale: likewise, of every generate() call (ViewFusion.generate).
+    variance: likewise ("analytic": the analytic variance of the model's moments, ViewFusion.generate)."""
     cond = first_view[:, None].contiguous()
     B = cond.shape[0]
     out = []
@@ -89,7 +90,7 @@ def autoregressive_rollout(model, first_view, steps=24, y_t=None, z_seq=None, se
             if guidance is not None:
                 inject.update(guidance=guidance)
             for name, val in (("threshold", threshold), ("threshold_max", threshold_max),
-                              ("guidance_rescale", guidance_rescale)):
+                              ("guidance_rescale", guidance_rescale), ("variance", variance)):
                 if val is not None:
                     inject[name] = val
             *_, sample = model(y_cond=cond, view_count=view_count, angle=angle, generate=True, **inject)
@@ -132,10 +133,18 @@ def save_checkpoint(path, model, optimizer, **extra):
     a progressive distillation (load_checkpoint); the teacher's weights are not part of the file.
     self_cond=model.self_cond records the self-conditioning setting, which state_dict() does not hold (only the stem's
     shape differs); learned_variance=model.learned_variance likewise records the vlb weight of a learned variance (only
-    the head's shape differs)."""
+    the head's shape differs).  moments=estimate_moments(...) (or a (T,) tensor: the model's own prediction is recorded
+    with it) records the per-level moments of the analytic variance, which state_dict() does not hold either; the file
+    gets {"moment" (T,) float64, "prediction", optionally "count"}."""
     out = dict(extra)
     if out.get("distill") is not None:
         _check_distill_extra(out["distill"])
+    if out.get("moments") is not None:
+        m = out["moments"]
+        m = dict(m) if isinstance(m, dict) else dict(moment=m)
+        m["moment"] = torch.as_tensor(m["moment"]).detach().to(device="cpu", dtype=torch.float64).reshape(-1).clone()
+        m.setdefault("prediction", getattr(model, "prediction", "eps"))
+        out["moments"] = m
     out["model"] = model.state_dict()
     out["optimizer"] = optimizer.state_dict()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
@@ -155,7 +164,11 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     extras: the caller builds the teacher and calls set_distill.  A "self_cond" entry (save_checkpoint(...,
     self_cond=model.self_cond): the self-conditioning probability, or None) must equal the model's own: ValueError
     otherwise, before anything is loaded.  A "learned_variance" entry (save_checkpoint(...,
-    learned_variance=model.learned_variance): the vlb weight, or None) likewise.  Files without the entry load as before."""
+    learned_variance=model.learned_variance): the vlb weight, or None) likewise.  A "moments" entry
+    (save_checkpoint(..., moments=...): the per-level moments of the analytic variance) must have been recorded for the
+    model's own prediction and number of timesteps: ValueError otherwise, before anything is loaded; it is handed back
+    with the other extras -- the caller calls model.set_moments(extras["moments"]).  Files without the entry load as
+    before."""
     sd = torch.load(path, map_location=device, weights_only=False)
     if sd.get("distill") is not None:
         _check_distill_extra(sd["distill"])
@@ -169,6 +182,17 @@ def load_checkpoint(path, model, optimizer=None, device=None):
     if "learned_variance" in sd and sd["learned_variance"] != getattr(model, "learned_variance", None):
         raise ValueError(f"the checkpoint was trained with a learned variance of vlb weight {sd['learned_variance']!r}, the "
                          f"model is set to {getattr(model, 'learned_variance', None)!r} (set_learned_variance)")
+    if sd.get("moments") is not None:
+        m = sd["moments"]
+        if not isinstance(m, dict) or "moment" not in m:
+            raise ValueError("the checkpoint's moments entry must be dict(moment=(T,), prediction=...)")
+        if m.get("prediction", mine) != mine:
+            raise ValueError(f"the checkpoint's moments were recorded for prediction {m.get('prediction')!r}, the model is "
+                             f"set to {mine!r}: the noise estimate differs")
+        T = getattr(model, "num_timesteps", None)
+        if T is not None and torch.as_tensor(m["moment"]).numel() != T:
+            raise ValueError(f"the checkpoint's moments hold {torch.as_tensor(m['moment']).numel()} levels, the model's "
+                             f"schedule {T}")
     model.load_state_dict(sd["model"])
     if optimizer is not None and "optimizer" in sd and sd["optimizer"].get("state"):
         optimizer.load_state_dict(sd["optimizer"])
@@ -451,3 +475,49 @@ def bits_per_dim(model, batches, seed=None, sample_steps=None, clip_denoised=Tru
     out = reduce_dict(out)
     _barrier()
     return out
+
+
+@torch.no_grad()
+def estimate_moments(model, batches, seed=None, levels=None):
+    """The statistic of the analytic variance (Analytic-DPM): M[t] = E |eps_hat(y_t)|^2 / d of the model's noise estimate,
+    per trained level, by Monte Carlo -- every rank runs ViewFusion.eps_moments on its shard of `batches` (the dicts of
+    bits_per_dim: target (B,3,H,W) in the model's own range, cond, angle, optionally view_count and ids), one draw per
+    (image, level); the per-sample moments are summed in float64 on the host side, after the loop (one sync per batch),
+    and sums and counts are all-reduced over the ranks.  Returns {"moment": (T,) float64 CPU tensor, NaN where no level
+    was visited; "count": (T,) int64 CPU tensor, the draws behind each level; "prediction": the model's}: hand it to
+    model.set_moments and to save_checkpoint(..., moments=).
+    seed (default None: torch's device generator): the noisy targets come from the counter-based generator keyed by
+    batch["ids"] (kind 6, the bound's: use another seed than for the bound on the same images), so an image's moments
+    do not depend on how the set is batched or sharded.
+    levels (default None: all T): K evenly strided levels or an explicit sequence (schedule.sample_timesteps) -- a chain
+    needs the moments of its own levels only, optimal_trajectory those of every level it may choose."""
+    core = getattr(model, "module", model)
+    T = core.num_timesteps
+    total = torch.zeros(T, dtype=torch.float64)
+    count = torch.zeros(T, dtype=torch.int64)
+    seen = 0
+    for b in batches:
+        n = b["target"].shape[0]
+        vc = b.get("view_count")
+        if vc is None:
+            vc = [b["cond"].shape[1]] * n
+        ids = None
+        if seed is not None:
+            ids = b.get("ids")
+            if ids is None:
+                ids = torch.arange(seen, seen + n)
+        seen += n
+        got = core.eps_moments(b["cond"], vc, b["angle"], b["target"], seed=seed, sample_ids=ids, levels=levels)
+        tau = got["tau"].cpu()
+        total[tau] += got["m2"].double().sum(dim=0).cpu()
+        count[tau] += n
+    _barrier()
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        dev = core.gammas.device
+        both = torch.cat([total, count.double()]).to(dev)
+        dist.all_reduce(both)
+        both = both.cpu()
+        total, count = both[:T], both[T:].round().to(torch.int64)
+    _barrier()
+    moment = torch.where(count > 0, total / count.clamp_min(1).double(), torch.full_like(total, float("nan")))
+    return {"moment": moment, "count": count, "prediction": core.prediction}

@@ -55,7 +55,8 @@ from .diffusion import (  # noqa: F401
     distill_begin, distill_step_host, distill_target,
     draw_self_cond, self_cond_coeffs_host, self_cond_draw_host, self_cond_estimate, self_cond_threshold,
     vlb_terms_host,
-    nll_noisy, nll_prior, nll_scratch, nll_terms, nll_terms_host
+    nll_noisy, nll_prior, nll_scratch, nll_terms, nll_terms_host,
+    eps_moment_host, eps_moments
 )
 from .lpips import (  # noqa: F401
     LPIPS_TAPS, LPIPS_WIDTHS, lpips

@@ -84,6 +84,7 @@ _CALL_KIND = {"vf_wino44_pack_weights": "pack", "vf_wino44_pack_weights_multi": 
               "vf_sampler_step_lv": "diffusion", "vf_sampler_step_lv_rng": "diffusion",
               "vf_sampler_step_lv_cfg": "diffusion", "vf_sampler_step_lv_cfg_rng": "diffusion",
               "vf_nll_noisy": "diffusion", "vf_nll_terms": "diffusion", "vf_nll_prior": "diffusion",
+              "vf_eps_moments": "diffusion",
               "vf_grad_sumsq_multi": "adam", "vf_grad_norm_finish": "adam", "vf_adam_multi_ex": "adam",
               "vf_adam_multi_ex_dev": "adam", "vf_adam_set_scalars_ex": "adam", "vf_swap_multi": "adam", "vf_grad_accum_multi": "adam"}
 

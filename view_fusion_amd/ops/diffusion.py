@@ -1189,6 +1189,55 @@ def nll_terms_host(out, o, y_k, y_0, a, b, c0, hi, lo, learned=False, decoder=Fa
     return tuple(outs)
 
 
+# ---- the analytic variance: the second moment of the noise estimate (csrc/diffusion.hip holds the definition) ----
+EPS_TABLE_NAMES = ("ea", "eb")
+
+
+def eps_moments(unet_out, off, y_k, kidx, tables, B, weighting, out=None, scratch=None):
+    """The second moment of the noise estimate of every sample at step k = kidx[b] (device int64 (B,)): column k of
+    m2 (B, K), the mean over the sample's 3 H W elements of (ea[k] y_k + eb[k] out_b)^2 with out_b the composition of
+    channels 0..2 over the sample's views (channels 6..8 of a nine-channel output are ignored).  tables: the fp32 device
+    tables ea, eb (K,) of schedule.eps_tables.  out=(B, K) and scratch=nll_scratch(B, device): no allocation; only
+    column k is written.  Two launches."""
+    tabs = [tables[n] for n in EPS_TABLE_NAMES]
+    _check(unet_out, y_k, *tabs)
+    K = tabs[0].numel()
+    if tabs[1].numel() != K or K < 1:
+        raise ValueError(f"eps_moments needs ea and eb of one length, got {[t.numel() for t in tabs]}")
+    _, Cout, H, W = unet_out.shape
+    if tuple(y_k.shape) != (B, 3, H, W):
+        raise ValueError(f"eps_moments needs y_k of shape {(B, 3, H, W)}, got {tuple(y_k.shape)}")
+    _check_i64("kidx", kidx, B)
+    if out is None:
+        out = torch.zeros(B, K, device=y_k.device, dtype=torch.float32)
+    _check(out)
+    if tuple(out.shape) != (B, K):
+        raise ValueError(f"out= needs a tensor of shape {(B, K)}")
+    if scratch is None:
+        scratch = nll_scratch(B, y_k.device)
+    if scratch["vb"].numel() < B * 64:
+        raise ValueError(f"scratch= holds fewer than {B * 64} partial sums")
+    _call("vf_eps_moments", _ptr(unet_out), ctypes.c_void_p(off.data_ptr()), _ptr(y_k), ctypes.c_void_p(kidx.data_ptr()),
+          _ptr(tabs[0]), _ptr(tabs[1]), _ptr(scratch["vb"]), _ptr(out), B, Cout, H * W, K, int(bool(weighting)),
+          _stream())
+    return out
+
+
+def eps_moment_host(out, y_k, ea, eb):
+    """The host mirror of one element of the moment: float tensors / sequences of one length -> (the noise estimate
+    ea y_k + eb out, its square) float32 CPU tensors, per element, by the function the kernel runs.  No GPU."""
+    arrs = [torch.as_tensor(v, dtype=torch.float32).detach().cpu().reshape(-1).contiguous() for v in (out, y_k, ea, eb)]
+    n = arrs[0].numel()
+    if any(v.numel() != n for v in arrs):
+        raise ValueError("eps_moment_host needs inputs of one length")
+    outs = [torch.empty(n, dtype=torch.float32) for _ in range(2)]
+    p = lambda v: ctypes.c_void_p(v.data_ptr())                     # noqa: E731
+    rc = _lib.load().vf_eps_moment_host(*(p(v) for v in arrs), p(outs[0]), p(outs[1]), n)
+    if rc != 0:
+        raise _lib.VFHipError(f"vf_eps_moment_host failed with {rc}")
+    return tuple(outs)
+
+
 def psnr(generated, target):
     """Per-image PSNR (B,) of (B,C,H,W) tensors in [0,1]."""
     generated, target = _c(generated), _c(target)

@@ -138,7 +138,7 @@ def check_sampler(solver, eta):
         raise ValueError("dpmpp2m is deterministic: eta must be 0")
 
 
-def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps"):
+def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps", moments=None):
     """float64 betas (T,), tau (K,) -> {a, b, cy, c0, c1, sigma}: float64 (K,) each (rounded to fp32 once, by the caller).
     prediction: a, b = prediction_tables gathered at tau; cy, c0, c1, sigma do not depend on it.  Where a level of the
     chain is 0 (zero terminal SNR) "eps" raises ValueError, and the other two give finite tables: the dpmpp2m step next
@@ -147,8 +147,14 @@ def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps"):
     ddim     DDIM with eps re-derived from the clamped y0; eta = 1 on the full schedule is the ancestral sampler.
     dpmpp2m  DPM-Solver++ 2M in lambda = log(alpha / sigma); the first executed step (k = K-1, no history yet) and the
              last (k = 0, onto the clean image) are first order, which is the ddim eta = 0 step.
+
+    moments (default None: the tables as before): the per-level second moment of the model's noise estimate, (T,) -- the
+    sigma row of the "ddim" tables becomes the analytic one (analytic_sampler_sigma: the KL-optimal noise scale around
+    the same mean, sigma*[0] = 0); every other row is unchanged.  ValueError with "dpmpp2m".
     """
     check_sampler(solver, eta)
+    if moments is not None and solver != "ddim":
+        raise ValueError("the analytic variance goes with solver 'ddim' alone: dpmpp2m is deterministic")
     betas = np.asarray(betas, dtype=np.float64)
     tau = np.asarray(tau, dtype=np.int64)
     gammas = np.cumprod(1.0 - betas, axis=0)
@@ -167,6 +173,8 @@ def sampler_tables(betas, tau, solver="ddim", eta=0.0, prediction="eps"):
         e2 = float(eta) ** 2
         d = np.sqrt((1.0 - gp) * ((1.0 - e2) + e2 * gt * (1.0 - gp) / (gp * (1.0 - gt))))
         out.update(cy=d / np.sqrt(1.0 - gt), c0=np.sqrt(gp) - d * np.sqrt(gt) / np.sqrt(1.0 - gt), sigma=sig)
+        if moments is not None:
+            out["sigma"] = analytic_sampler_sigma(betas, tau, moments, eta)
         return out
     with np.errstate(divide="ignore"):
         lam = 0.5 * np.log(gt / (1.0 - gt))
@@ -208,7 +216,11 @@ def variance_tables(betas, tau=None):
 FIXED_VARIANCES = ("small", "large")
 
 
-def nll_tables(betas, tau=None, prediction="eps", fixed_variance="small"):
+ANALYTIC_VARIANCE = "analytic"                    # the moment-based optimal variance (analytic_sigma2, below)
+BOUND_VARIANCES = FIXED_VARIANCES + (ANALYTIC_VARIANCE,)
+
+
+def nll_tables(betas, tau=None, prediction="eps", fixed_variance="small", moments=None):
     """float64 betas (T,), tau (K,) (default 0..T-1) -> {a, b, c0, hi, lo}: float64 (K,) each (rounded to fp32 once, by the
     caller).  With gt = gammas[tau[k]], gp = gammas[tau[k-1]] (1 at k = 0): a, b = prediction_tables gathered at tau;
     c0[k] = sqrt(gp) (1 - gt/gp) / (1 - gt), the weight of y0 in the posterior mean; hi, lo = variance_tables.  On the full
@@ -216,8 +228,16 @@ def nll_tables(betas, tau=None, prediction="eps", fixed_variance="small"):
     posterior_log_variance_clipped value for value.  Row 0 is the decoder's: hi[0] = log(1 - gammas[tau[0]]) and lo[0] =
     lo[1], the log posterior variance of step 1 (not the 1e-20 clipping, under which the likelihood degenerates);
     a one-step chain has lo[0] = hi[0]; fixed_variance="large" (lp = hi) reads lo[0] at k = 0 as well, so its hi[0] = lo[0].
-    ValueError for an eps model on a level with gamma = 0, as sampler_tables."""
-    if fixed_variance not in FIXED_VARIANCES:
+    ValueError for an eps model on a level with gamma = 0, as sampler_tables.
+    fixed_variance="analytic" with moments (T,) (the per-level second moment of the noise estimate,
+    drivers.estimate_moments): hi[k] = log sigma*^2[k], the Analytic-DPM optimal variance of the chain at eta = 1 --
+    lambda^2 the chain's posterior variance, c0 the column above -- and hi[0] = log max(sigma*^2[0], exp(lo[0])), never
+    below the decoder row "small" uses; lo stays the true posterior's.  The term kernel reads it as it reads "large".
+    ValueError there for a level with gamma = 0 or a NaN moment on the chain, and for moments without "analytic"."""
+    analytic = fixed_variance == ANALYTIC_VARIANCE
+    if analytic != (moments is not None):
+        raise ValueError("fixed_variance='analytic' and moments= come together")
+    if fixed_variance not in FIXED_VARIANCES and not analytic:
         raise ValueError(f"unknown fixed_variance {fixed_variance!r}: one of {FIXED_VARIANCES}")
     betas = np.asarray(betas, dtype=np.float64)
     T = betas.shape[0]
@@ -242,7 +262,126 @@ def nll_tables(betas, tau=None, prediction="eps", fixed_variance="small"):
         lo[0] = lo[1] if tau.shape[0] > 1 else hi[0]
     if fixed_variance == "large":
         hi[0] = lo[0]
+    if analytic:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if full:                               # the posterior variance as schedule_tensors forms it, unclipped
+                lam2 = betas * (1.0 - prev) / (1.0 - gammas)
+            else:
+                lam2 = (1.0 - gt / gp) * (1.0 - gp) / (1.0 - gt)
+        sig2 = _analytic_sigma2(lam2, c0, gt, _moments_at(moments, tau, T))
+        hi = np.log(np.maximum(sig2, 1e-20))       # (the clipping lo carries: hi >= lo in every row)
+        hi[0] = max(hi[0], lo[0])                  # max(sigma*^2[0], exp(lo_dec)), in logarithms
     return {"a": pa[tau], "b": pb[tau], "c0": c0, "hi": hi, "lo": lo}
+
+
+# ---- the analytic variance (Analytic-DPM; csrc/diffusion.hip, "Analytic variance") -----------------------------------
+def eps_tables(betas, tau=None, prediction="eps"):
+    """float64 betas (T,), tau (K,) (default 0..T-1) -> {ea, eb}: float64 (K,) each (rounded to fp32 once, by the caller):
+    the noise a network's output stands for, eps_hat = ea[k] y + eb[k] out at g = gammas[tau[k]] -- "eps": (0, 1);
+    "v": (sqrt(1 - g), sqrt(g)); "x0": (1 / sqrt(1 - g), -sqrt(g / (1 - g)))."""
+    check_prediction(prediction)
+    gammas = np.cumprod(1.0 - np.asarray(betas, dtype=np.float64), axis=0)
+    g = gammas if tau is None else gammas[np.asarray(tau, dtype=np.int64)]
+    if prediction == "eps":
+        return {"ea": np.zeros_like(g), "eb": np.ones_like(g)}
+    if prediction == "v":
+        return {"ea": np.sqrt(1.0 - g), "eb": np.sqrt(g)}
+    return {"ea": 1.0 / np.sqrt(1.0 - g), "eb": -np.sqrt(g / (1.0 - g))}
+
+
+def _moments_at(moments, tau, T):
+    """The moments of the chain's levels, float64 (K,), clipped into [0, 1]; ValueError for a table of another length
+    and for a NaN (not estimated) moment at a level the chain uses."""
+    if torch.is_tensor(moments):
+        moments = moments.detach().cpu().numpy()
+    m = np.asarray(moments, dtype=np.float64).reshape(-1)
+    if m.shape[0] != T:
+        raise ValueError(f"moments must hold one value per trained level ({T}), got {m.shape[0]}")
+    m = m[tau]
+    if np.isnan(m).any():
+        raise ValueError(f"no moment was estimated at the levels {np.asarray(tau)[np.isnan(m)].tolist()} of the chain")
+    return np.clip(m, 0.0, 1.0)
+
+
+def _check_gamma_nonzero(g):
+    if (np.asarray(g) == 0).any():
+        raise ValueError("the analytic variance is not defined on a level with gamma = 0 (zero terminal SNR): "
+                         "(1 - g) / g is infinite there")
+
+
+def _analytic_sigma2(lam2, c0, gt, mc):
+    """sigma*^2 = lambda^2 + c0^2 (1 - gt) / gt (1 - Mc), float64; ValueError for a level with gamma = 0 (0 times inf)."""
+    _check_gamma_nonzero(gt)
+    return lam2 + c0 * c0 * ((1.0 - gt) / gt) * (1.0 - mc)
+
+
+def analytic_sigma2(betas, tau, moments, eta=1.0):
+    """float64 betas (T,), tau (K,), moments (T,) -> sigma*^2 (K,) float64: the KL-optimal variance of the reverse step of
+    the chain tau (Analytic-DPM, Theorem 1) around the "ddim" mean at `eta`, for a model whose noise estimate has the
+    per-level second moment M[t] = E |eps_hat(y_t)|^2 / d (drivers.estimate_moments; NaN where not estimated).  With
+    lambda^2 = sigma^2 and c0 of sampler_tables(betas, tau, "ddim", eta) and Mc = clip(M[tau[k]], 0, 1):
+        sigma*^2[k] = lambda^2[k] + c0[k]^2 (1 - gt) / gt (1 - Mc)
+    so lambda^2 <= sigma*^2 <= lambda^2 + c0^2 (1 - gt) / gt (the paper's Theorem 2), and M = 1 gives lambda^2 exactly.
+    The sampler row is sqrt of this with row 0 set to 0 (analytic_sampler_sigma).  ValueError for a level with gamma = 0
+    and for a NaN moment at a level of the chain."""
+    betas = np.asarray(betas, dtype=np.float64)
+    tau = np.asarray(tau, dtype=np.int64)
+    gt = np.cumprod(1.0 - betas, axis=0)[tau]
+    mc = _moments_at(moments, tau, betas.shape[0])
+    _check_gamma_nonzero(gt)
+    tab = sampler_tables(betas, tau, "ddim", eta, "x0")   # (sigma and c0 do not depend on the prediction)
+    return _analytic_sigma2(tab["sigma"] ** 2, tab["c0"], gt, mc)
+
+
+def analytic_sampler_sigma(betas, tau, moments, eta=0.0):
+    """The sigma row of a sampler with the analytic variance, float64 (K,): sqrt(analytic_sigma2) with sigma*[0] = 0 --
+    the last step returns its mean, as every sampler here does.  eta = 0 is Analytic-DDIM, which is stochastic."""
+    sig = np.sqrt(analytic_sigma2(betas, tau, moments, eta))
+    sig[0] = 0.0
+    return sig
+
+
+def optimal_trajectory(betas, moments, K, first=0):
+    """The KL-optimal K-step sub-sequence of the trained levels (Analytic-DPM, section 5): the strictly increasing int64
+    tau (K,) with tau[0] = first and tau[K-1] = T-1 that minimises sum_{k >= 1} J(tau[k-1], tau[k]), where
+    J(r, s) = log(sigma*^2(r, s) / lambda^2(r, s)) is the cost, at eta = 1, of the step from level s down to r < s under
+    the analytic variance.  Dynamic programming over the vectorised T x T cost matrix, float64, K T^2 work; ties go to
+    the smaller timestep.  Needs a moment at every level in [first, T-1] and no level with gamma = 0 there (ValueError
+    otherwise).  The result is what sample_timesteps accepts as an explicit sequence: pass it as sample_steps=."""
+    betas = np.asarray(betas, dtype=np.float64)
+    T = betas.shape[0]
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or isinstance(first, bool) or \
+            not isinstance(first, (int, np.integer)):
+        raise ValueError(f"K and first must be integers, got {K!r}, {first!r}")
+    K, first = int(K), int(first)
+    if not 0 <= first <= T - 1 or not 1 <= K <= T - first or (K == 1) != (first == T - 1):
+        raise ValueError(f"no strictly increasing chain of {K} steps from {first} to {T - 1}")
+    lv = np.arange(first, T)
+    g = np.cumprod(1.0 - betas, axis=0)[lv]
+    m = _moments_at(moments, lv, T)
+    _check_gamma_nonzero(g)
+    n = lv.shape[0]
+    gp, gt = g[:, None], g[None, :]                       # J[r, s]: from s (column) down to r (row), r < s
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lam2 = (1.0 - gt / gp) * (1.0 - gp) / (1.0 - gt)
+        c0 = np.sqrt(gp) * (1.0 - gt / gp) / (1.0 - gt)
+        J = np.log((lam2 + c0 * c0 * ((1.0 - gt) / gt) * (1.0 - m[None, :])) / lam2)
+    J[np.tril_indices(n)] = np.inf                        # r >= s is no step
+    cost = np.full(n, np.inf)
+    cost[0] = 0.0
+    back = np.zeros((K, n), dtype=np.int64)
+    for j in range(1, K):
+        via = cost[:, None] + J                           # via[r, s]
+        back[j] = np.argmin(via, axis=0)
+        cost = via[back[j], np.arange(n)]
+    if not np.isfinite(cost[n - 1]):
+        raise ValueError(f"no strictly increasing chain of {K} steps from {first} to {T - 1}")
+    tau = np.empty(K, dtype=np.int64)
+    s = n - 1
+    for j in range(K - 1, -1, -1):
+        tau[j] = lv[s]
+        s = back[j][s]
+    return tau
 
 
 # ---- progressive distillation: the grids and the target weights of a K-step student of a 2K-step teacher ------------

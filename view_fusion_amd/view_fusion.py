@@ -98,6 +98,49 @@ class ViewFusion(nn.Module):
         self._lv_weight = None
         self.last_sample_vlb = None
         self._lv_tabs = None
+        # the analytic variance (set_moments): the per-level second moment of the noise estimate, float64 on the host
+        # (None: not set), and a counter the cached plans key on: plain attributes too
+        self._moments = None
+        self._moments_gen = 0
+
+    # -- the analytic variance ----------------------------------------------------------------
+    def set_moments(self, moments=None):
+        """The per-level second moment of this model's noise estimate, M[t] = E |eps_hat(y_t)|^2 / d: (T,) values
+        (drivers.estimate_moments' "moment"; NaN where a level was not estimated), or None, the default: not set.
+        What generate(variance="analytic") and bound_terms(fixed_variance="analytic") build the Analytic-DPM optimal
+        variance from (schedule.analytic_sigma2; csrc/diffusion.hip holds the definition).  A plain attribute
+        (`moments` reads it back, a float64 CPU tensor): no buffer, no parameter, state_dict() is unchanged -- save it as
+        save_checkpoint(..., moments=...).  They are the moments of the model as it is now -- its weights, its
+        prediction, its schedule -- and of the unguided model; nothing checks that.  ValueError for anything but one
+        value per trained level."""
+        self._moments_gen += 1
+        if moments is None:
+            self._moments = None
+            return
+        if isinstance(moments, dict):
+            moments = moments["moment"]
+        m = torch.as_tensor(moments).detach().to(device="cpu", dtype=torch.float64).reshape(-1).clone()
+        T = getattr(self, "num_timesteps", None)
+        if T is not None and m.numel() != T:
+            raise ValueError(f"moments must hold one value per trained level ({T}), got {m.numel()}")
+        self._moments = m
+
+    @property
+    def moments(self):
+        """The moments of set_moments (float64 CPU tensor (T,)), None while they are not set."""
+        return self._moments
+
+    def _check_analytic(self, dev, what):
+        """ValueError, before any launch, where the analytic variance cannot be used (`what` names the caller)."""
+        if self._lv_weight is not None:
+            raise ValueError(f"{what} on a model with a learned variance: the model has its own (DESIGN 8)")
+        if self._moments is None:
+            raise ValueError(f"{what} needs the model's moments: drivers.estimate_moments, then set_moments (DESIGN 8)")
+        if self._moments.numel() != self.num_timesteps:
+            raise ValueError(f"the moments hold {self._moments.numel()} levels, the schedule {self.num_timesteps}")
+        if torch.device(dev).type != "cuda" or self.gammas.device.type != "cuda":
+            raise ValueError(f"{what} runs on the GPU only (its reverse step and its terms are HIP kernels): move the "
+                             "model and the batch there")
 
     # -- a learned variance -------------------------------------------------------------------
     def set_learned_variance(self, vlb_weight=1e-3):
@@ -573,6 +616,7 @@ class ViewFusion(nn.Module):
         self._pred_tabs = None
         self._lv_tabs = None
         self._nll_plan = None                  # the tables of a bound evaluation (bound_terms), made on demand
+        self._eps_plan = None                  # the tables of a moment estimation (eps_moments), made on demand
         for name, val in _schedule.schedule_tensors(betas, device).items():
             if name in self._buffers:
                 self._buffers[name] = val
@@ -599,13 +643,17 @@ class ViewFusion(nn.Module):
             raise ValueError("an eps-prediction model cannot sample on a zero-terminal-SNR schedule (gamma_T = 0: g^-1/2 "
                              "is infinite there); use set_prediction('v') or 'x0'")
 
-    def _sampler_plan(self, tau, solver, eta, device):
+    def _sampler_plan(self, tau, solver, eta, device, variance=None):
         """The device side of a few-step chain: the fp32 tables of schedule.sampler_tables, `tau` as int64 and
         `level` = the fp32 `gammas` buffer gathered at tau (the network sees the very levels of the full chain).
-        `noisy[k]`: sigma[k] != 0, on the host.  The last plan is kept (evaluate() asks for the same one per batch)."""
-        key = (tuple(int(v) for v in tau), solver, float(eta), device, self.prediction)
+        `noisy[k]`: sigma[k] != 0, on the host.  The last plan is kept (evaluate() asks for the same one per batch).
+        variance="analytic": the sigma row is the analytic one of the model's moments (set_moments), and `noisy` follows
+        it; the moments are part of the key."""
+        key = (tuple(int(v) for v in tau), solver, float(eta), device, self.prediction,
+               None if variance is None else (variance, self._moments_gen))
         if self._plan is None or self._plan[0] != key:
-            tab = _schedule.sampler_tables(self.betas64, tau, solver, eta, self.prediction)
+            tab = _schedule.sampler_tables(self.betas64, tau, solver, eta, self.prediction,
+                                           **({} if variance is None else dict(moments=self._moments)))
             host = {k: torch.tensor(v, dtype=torch.float32) for k, v in tab.items()}
             plan = {k: v.to(device) for k, v in host.items()}
             plan["tau"] = torch.tensor(tau, dtype=torch.int64, device=device)
@@ -686,11 +734,20 @@ class ViewFusion(nn.Module):
 
     @torch.no_grad()
     def p_sample(self, y_t, y_cond, view_count, angle, t, clip_denoised=True, z=None, guidance=None, threshold=None,
-                 threshold_max=None, guidance_rescale=None, self_cond=None):
-        """self_cond (B,3,H,W; a self-conditioned model): the estimate shown to the network; None is zeros."""
+                 threshold_max=None, guidance_rescale=None, self_cond=None, variance=None):
+        """self_cond (B,3,H,W; a self-conditioned model): the estimate shown to the network; None is zeros.
+        variance="analytic" (default None: the step as before): the ancestral step with the analytic noise scale of the
+        model's moments in place of the posterior one -- step t of generate(variance="analytic") on the full chain, through
+        the table-driven tail, which clamps y0_hat (clip_denoised=False is refused)."""
         from . import ops
         ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None, clip_denoised)
         self._check_samplable()
+        if variance is not None:
+            if variance != _schedule.ANALYTIC_VARIANCE:
+                raise ValueError(f"unknown variance {variance!r}: None or {_schedule.ANALYTIC_VARIANCE!r}")
+            self._check_analytic(y_t.device, "variance='analytic'")
+            if not clip_denoised:
+                raise ValueError("the table-driven step clamps y0_hat: clip_denoised=False is not built")
         if self._lv_weight is not None:
             self._check_lv(y_t.device, threshold, guidance_rescale)
             if not clip_denoised:
@@ -710,6 +767,10 @@ class ViewFusion(nn.Module):
             y, weights = ops.sampler_step(out, off, y_t, z, t, plan, y_t.shape[0], max_v, w_on, guidance=gs, S=S,
                                           variance=(plan["hi"], plan["lo"]))
             return y, (self._logits(out, S) if w_on else None), weights
+        if variance is not None:          # the "ddim", eta = 1 tables of the full chain with the analytic sigma row
+            plan = self._sampler_plan(list(range(self.num_timesteps)), "ddim", 1.0, y_t.device, variance)
+            y, weights = ops.sampler_step(out, off, y_t, z, t, plan, y_t.shape[0], max_v, w_on, guidance=gs, S=S, **dyn)
+            return y, (out[:S, 3:, ...] if w_on else None), weights
         y, _, weights = ops.p_sample_tail(out, off, y_t, z, t, self._sched(), y_t.shape[0], max_v, w_on,
                                           clip=clip_denoised, guidance=gs, S=S, **dyn)
         return y, (out[:S, 3:, ...] if w_on else None), weights
@@ -717,7 +778,7 @@ class ViewFusion(nn.Module):
     @torch.no_grad()
     def generate(self, y_cond, view_count, angle, y_t=None, sample_num=8, z_seq=None, use_graph=None, seed=None,
                  sample_ids=None, sample_steps=None, solver="ddim", eta=0.0, guidance=None, threshold=None,
-                 threshold_max=None, guidance_rescale=None):
+                 threshold_max=None, guidance_rescale=None, variance=None):
         """Reverse diffusion over all T steps (reference view_fusion.py:179-214).
 
         use_graph (default: on for GPU tensors with S <= 16 stacked views): one reverse step -- level gather, re-stack of
@@ -756,12 +817,30 @@ class ViewFusion(nn.Module):
         the first step; with dpmpp2m the tail's own history is that same buffer.  Only the table-driven tail hands y0 back,
         so sample_steps=None runs as sample_steps=T, solver="ddim", eta=1.0: the ancestral chain through that tail (the
         sampler tests pin the two to each other within the chain tolerance).  Everything above combines with it unchanged.
+
+        variance (default None: everything above, launch for launch and bit for bit): "analytic" -- the Analytic-DPM
+        optimal variance (Bao et al.; csrc/diffusion.hip holds the definition).  The table-driven chain with
+        solver="ddim" at the given eta, its mean unchanged and its sigma row replaced by the KL-optimal one of the
+        model's moments (set_moments; schedule.analytic_sigma2), sigma*[0] = 0: the same launches as that chain, only a
+        table row differs.  eta = 0 is Analytic-DDIM, which is STOCHASTIC (sigma*^2 = c0^2 (1 - g)/g (1 - M) > 0): it
+        draws z where "ddim", eta = 0 draws none.  sample_steps=None runs as sample_steps=T, solver="ddim", eta=1.0.
+        The moments are those of the unguided model without thresholding: guidance / threshold / guidance_rescale run
+        (only a table row differs) but nothing is claimed for them.  ValueError before any launch: solver="dpmpp2m", no
+        moments set, a learned-variance model, a CPU model.
         """
         from . import ops
         q_on, _, phi = ops.threshold_settings(threshold, threshold_max, guidance_rescale, guidance is not None)
         dyn = {}
         plan = tau = None
         self._check_samplable()
+        if variance is not None:                          # only the table-driven tail reads a sigma row
+            if variance != _schedule.ANALYTIC_VARIANCE:
+                raise ValueError(f"unknown variance {variance!r}: None or {_schedule.ANALYTIC_VARIANCE!r}")
+            if sample_steps is not None and solver != "ddim":
+                raise ValueError("variance='analytic' goes with solver='ddim' alone: dpmpp2m is deterministic (DESIGN 8)")
+            self._check_analytic(y_cond.device, "variance='analytic'")
+            if sample_steps is None:
+                sample_steps, solver, eta = self.num_timesteps, "ddim", 1.0
         lv_on = self._lv_weight is not None
         if lv_on:                                         # only the table-driven tail has the learned-variance flavour
             self._check_lv(y_cond.device, threshold, guidance_rescale)
@@ -775,6 +854,8 @@ class ViewFusion(nn.Module):
         if sample_steps is not None:                      # argument errors first: nothing has been launched yet
             _schedule.check_sampler(solver, eta)
             tau = _schedule.sample_timesteps(self.num_timesteps, sample_steps).tolist()
+            if variance is not None:                      # a level with gamma = 0 or without a moment: refused here
+                _schedule.analytic_sampler_sigma(self.betas64, tau, self._moments, eta)
         b = y_cond.shape[0]
         gs = None if guidance is None else ops.guidance_scales(y_cond.device, b, guidance)
         guided = gs is not None
@@ -799,7 +880,7 @@ class ViewFusion(nn.Module):
         levels, hist = self.gammas, None
         if tau is not None:
             lv_step = lv_on and solver == "ddim" and float(eta) == 1.0
-            plan = self._lv_plan(tau, dev) if lv_step else self._sampler_plan(tau, solver, eta, dev)
+            plan = self._lv_plan(tau, dev) if lv_step else self._sampler_plan(tau, solver, eta, dev, variance)
             lv = dict(variance=(plan["hi"], plan["lo"])) if lv_step else {}
             levels = plan["level"]
             # y0 of the step before; the multistep tail never reads it first ...
@@ -878,10 +959,12 @@ class ViewFusion(nn.Module):
         """The device side of a bound evaluation: the fp32 tables of schedule.nll_tables, `tau` as int64, `level` = the
         fp32 `gammas` buffer gathered at tau and `snr` = level / (1 - level) (formed in float64, rounded once).  The
         last plan is kept (bits_per_dim asks for the same one per batch)."""
-        key = (tuple(int(v) for v in tau), self.prediction, fixed_variance, dev)
+        analytic = fixed_variance == _schedule.ANALYTIC_VARIANCE
+        key = (tuple(int(v) for v in tau), self.prediction, fixed_variance, dev, self._moments_gen if analytic else None)
         plan = getattr(self, "_nll_plan", None)
         if plan is None or plan[0] != key:
-            tab = _schedule.nll_tables(self.betas64, tau, self.prediction, fixed_variance)
+            tab = _schedule.nll_tables(self.betas64, tau, self.prediction, fixed_variance,
+                                       **(dict(moments=self._moments) if analytic else {}))
             new = {k: torch.tensor(v, dtype=torch.float32, device=dev) for k, v in tab.items()}
             new["tau"] = torch.tensor(list(key[0]), dtype=torch.int64, device=dev)
             new["level"] = self.gammas[new["tau"]].contiguous()
@@ -900,8 +983,10 @@ class ViewFusion(nn.Module):
         if self._self_cond_p is not None:
             raise ValueError("the bound of a self-conditioned model is not built (DESIGN 8): its reverse step depends on "
                              "the chain's own history")
-        if fixed_variance not in _schedule.FIXED_VARIANCES:
-            raise ValueError(f"unknown fixed_variance {fixed_variance!r}: one of {_schedule.FIXED_VARIANCES}")
+        if fixed_variance not in _schedule.BOUND_VARIANCES:
+            raise ValueError(f"unknown fixed_variance {fixed_variance!r}: one of {_schedule.BOUND_VARIANCES}")
+        if fixed_variance == _schedule.ANALYTIC_VARIANCE:
+            self._check_analytic(dev, "fixed_variance='analytic'")
         if self._lv_weight is not None and fixed_variance == "large":
             raise ValueError("fixed_variance='large' on a model with a learned variance: the model has its own")
         if torch.device(dev).type != "cuda" or self.gammas.device.type != "cuda":
@@ -919,7 +1004,9 @@ class ViewFusion(nn.Module):
         sample, one no-grad forward on the inference path at the level gammas[tau[k]] (no Dropout, whatever mode the model
         is in) and one term: the KL of the true posterior from the model's reverse step for k >= 1, the discretised decoder
         likelihood at k = 0; plus the prior term.  The model's variance: learned (set_learned_variance on a nine-channel
-        network), else fixed_variance "small" (the posterior variance, what the ancestral sampler uses) or "large" (beta).
+        network), else fixed_variance "small" (the posterior variance, what the ancestral sampler uses), "large" (beta) or
+        "analytic" (the Analytic-DPM optimal variance of the model's moments, set_moments: the term kernel runs as for
+        "large" on another hi row, schedule.nll_tables; refused on a learned variance and without moments).
         noise (B, K, 3, H, W) wins; else seed= draws it from the counter-based generator (kind 6, keyed by sample_ids and
         the model timestep, so a sample's targets do not depend on its batch); else torch's device generator.
         Returns {"total_bpd" (B,), "prior_bpd" (B,), "vb" (B, K), "x0_mse" (B, K), "eps_mse" (B, K), "tau" (K,)}: device
@@ -968,7 +1055,7 @@ class ViewFusion(nn.Module):
                     ops.nll_noisy(y_0, kidx, plan["tau"], self.gammas, out=y_k, **draw)
                 x, out = self._denoise(y_k, y_cond, angle, kidx, off, S, x=x, copy_cond=x is None, levels=plan["level"])
                 ops.nll_terms(out, off, y_k, y_0, kidx, plan, b, w_on, learned=lv, decoder=k == 0,
-                              large=fixed_variance == "large", clip=clip_denoised, out=(vb, mse), scratch=scratch)
+                              large=fixed_variance != "small", clip=clip_denoised, out=(vb, mse), scratch=scratch)
         finally:
             if was:
                 self.denoise_fn.train(True)
@@ -976,16 +1063,104 @@ class ViewFusion(nn.Module):
         return {"total_bpd": prior + vb.sum(dim=1), "prior_bpd": prior, "vb": vb, "x0_mse": mse,
                 "eps_mse": mse * plan["snr"], "tau": plan["tau"]}
 
+    # -- the analytic variance: the statistic -----------------------------------------------------
+    def _eps_plan_for(self, tau, dev):
+        """The device side of a moment estimation: the fp32 tables of schedule.eps_tables, `tau` as int64 and `level`
+        = the fp32 `gammas` buffer gathered at tau.  The last plan is kept (estimate_moments asks for the same one per
+        batch)."""
+        key = (tuple(int(v) for v in tau), self.prediction, dev)
+        plan = getattr(self, "_eps_plan", None)
+        if plan is None or plan[0] != key:
+            tab = _schedule.eps_tables(self.betas64, tau, self.prediction)
+            new = {k: torch.tensor(v, dtype=torch.float32, device=dev) for k, v in tab.items()}
+            new["tau"] = torch.tensor(list(key[0]), dtype=torch.int64, device=dev)
+            new["level"] = self.gammas[new["tau"]].contiguous()
+            plan = self._eps_plan = (key, new)
+        return plan[1]
+
+    def _check_moments(self, dev, guidance=None, threshold=None, guidance_rescale=None):
+        """ValueError, before any launch, where the moments cannot be estimated (eps_moments,
+        drivers.estimate_moments): `dev` is where the targets live."""
+        if guidance is not None or threshold is not None or \
+                (guidance_rescale is not None and float(guidance_rescale) > 0):
+            raise ValueError("eps_moments takes no guidance / threshold / guidance_rescale: the moments are those of the "
+                             "conditional model's own raw prediction (DESIGN 8)")
+        if self._self_cond_p is not None:
+            raise ValueError("the moments of a self-conditioned model are not built (DESIGN 8): its prediction depends "
+                             "on the chain's own history")
+        if torch.device(dev).type != "cuda" or self.gammas.device.type != "cuda":
+            raise ValueError("eps_moments runs on the GPU only (the moment is a HIP kernel): move the model and the "
+                             "batch there")
+
+    @torch.no_grad()
+    def eps_moments(self, y_cond, view_count, angle, y_0, noise=None, seed=None, sample_ids=None, levels=None,
+                    guidance=None, threshold=None, guidance_rescale=None):
+        """The statistic of the analytic variance (Analytic-DPM; csrc/diffusion.hip holds the definition): per sample
+        and level the second moment of the model's noise estimate, m2[b, k] = mean over 3 H W of eps_hat(y_k)^2 with
+        eps_hat = ea[k] y_k + eb[k] out_b for the model's own prediction (eps: `out_b` itself; no clamp) and y_k one
+        noisy version of the target y_0 at the level gammas[tau[k]].  The loop of bound_terms: for every level -- all T
+        (levels=None), K evenly strided ones, or an explicit sequence (schedule.sample_timesteps) -- the bound's noisy
+        target (noise (B, K, 3, H, W) wins; else seed= draws it from the counter-based generator, kind 6, keyed by
+        sample_ids and the model timestep: use another seed than for the bound on the same images; else torch's device
+        generator), one no-grad forward on the inference path and the moment kernel.  A nine-channel network's channels
+        6..8 are ignored.  Returns {"m2" (B, K), "tau" (K,)}: device tensors, no host sync inside the loop; launched
+        eagerly.  drivers.estimate_moments averages it into M[t].  Refused with ValueError before any launch: guidance /
+        threshold / guidance_rescale, a self-conditioned model, a CPU model."""
+        from . import ops
+        dev = y_0.device
+        self._check_moments(dev, guidance, threshold, guidance_rescale)
+        b, _, H, W = y_0.shape
+        T = self.num_timesteps
+        tau = list(range(T)) if levels is None else _schedule.sample_timesteps(T, levels).tolist()
+        K = len(tau)
+        if noise is not None and tuple(noise.shape) != (b, K, 3, H, W):
+            raise ValueError(f"noise must have shape {(b, K, 3, H, W)}, got {tuple(noise.shape)}")
+        if tuple(y_cond.shape[-2:]) != (H, W) or y_cond.shape[0] != b:
+            raise ValueError(f"y_cond {tuple(y_cond.shape)} does not go with y_0 {tuple(y_0.shape)}")
+        plan = self._eps_plan_for(tau, dev)
+        ids = None if seed is None or noise is not None else ops.sample_ids(dev, b, sample_ids)
+        off, S, _ = ops.view_offsets(view_count, dev)
+        y_0, y_cond, angle = y_0.contiguous(), y_cond.contiguous(), angle.contiguous()
+        w_on = bool(self.weighting_inference)
+        kidx = torch.zeros(b, device=dev, dtype=torch.int64)
+        m2 = torch.zeros(b, K, device=dev, dtype=torch.float32)
+        scratch = ops.nll_scratch(b, dev)
+        y_k = torch.empty_like(y_0)
+        draw = dict(noise=noise.contiguous()) if noise is not None else dict(seed=seed, ids=ids)
+        z = zero = None
+        if noise is None and seed is None:                       # torch's device generator: one level's draw at a time
+            z = torch.empty(b, 1, 3, H, W, device=dev, dtype=torch.float32)
+            zero = torch.zeros(b, device=dev, dtype=torch.int64)
+        x = None
+        was = self.denoise_fn.training if isinstance(self.denoise_fn, nn.Module) else None
+        if was:
+            self.denoise_fn.eval()
+        try:
+            for k in reversed(range(K)):
+                kidx.fill_(k)
+                if z is not None:
+                    ops.nll_noisy(y_0, zero, plan["tau"][k:k + 1], self.gammas, noise=z.normal_(), out=y_k)
+                else:
+                    ops.nll_noisy(y_0, kidx, plan["tau"], self.gammas, out=y_k, **draw)
+                x, out = self._denoise(y_k, y_cond, angle, kidx, off, S, x=x, copy_cond=x is None, levels=plan["level"])
+                ops.eps_moments(out, off, y_k, kidx, plan, b, w_on, out=m2, scratch=scratch)
+        finally:
+            if was:
+                self.denoise_fn.train(True)
+        return {"m2": m2, "tau": plan["tau"]}
+
     # -- training ---------------------------------------------------------------------------
     def forward(self, y_cond, view_count, angle, y_0=None, noise=None, generate=False, t=None, u=None, y_t=None,
                 z_seq=None, use_graph=None, seed=None, sample_ids=None, sample_steps=None, solver="ddim", eta=0.0,
                 guidance=None, cond_drop=None, threshold=None, threshold_max=None, guidance_rescale=None, distill_z=None,
-                distill_level=None, distill_eps=None, distill_x0=None, self_cond=None):
+                distill_level=None, distill_eps=None, distill_x0=None, self_cond=None, variance=None):
         if generate:                      # generate() wrapped in forward for DDP, as in the reference
             return self.generate(y_cond, view_count, angle, y_t=y_t, z_seq=z_seq, use_graph=use_graph, seed=seed,
                                  sample_ids=sample_ids, sample_steps=sample_steps, solver=solver, eta=eta,
                                  guidance=guidance, threshold=threshold, threshold_max=threshold_max,
-                                 guidance_rescale=guidance_rescale)
+                                 guidance_rescale=guidance_rescale, variance=variance)
+        if variance is not None:
+            raise ValueError("variance= belongs to sampling (generate=True): a training step has no reverse variance")
         from . import ops
         b = y_0.shape[0]
         dev = y_0.device
